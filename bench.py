@@ -16,7 +16,13 @@ table only, the (delay, freq, |peak|) rows all-gathered over RCCL inside the tim
 rank.  The default (and what the driver's fixed command line measures) stays C2, the configuration
 BASELINE.json's metric is quoted on.
 
-Prints ONE JSON line on rank 0.
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0 (the headline, the per-stage
+times and the roofline of the timed launches).  --full adds what takes runs of its own: the untimed side figures
+(no_surface, surface_t), the CPU baselines and, with N > 1 ranks, the collective timed alone.
+
+--dump-outputs DIR writes what the last timed step computed, as a caller of the path receives it, to DIR/<name>.npy
+(float32 / float64, at most 64 MB in all: the peak, and fixed seeded samples of the per-delay results and of the surface
+rows).  The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 
 import argparse
@@ -196,6 +202,54 @@ def cpu_baseline_same_algorithm(rx_host, tmpl_host, bins, budget_s=10.0):
     }
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def sample_delays(S, k, seed):
+    """A fixed, seeded sample of about k of the S delays (sorted, unique) plus the 64 around the planted peak."""
+    pick = np.random.default_rng(seed).integers(0, S, size=k)
+    near = np.arange(max(D0 - 32, 0), min(D0 + 32, S))
+    return np.unique(np.concatenate((pick, near)))
+
+
+def peak_outputs(delay, freq, val_bits):
+    """The engine's peak arrays (delay, frequency index, value as int32 bits) as float arrays."""
+    return {"peak_delay": np.asarray(delay, dtype=np.float64).reshape(-1),
+            "peak_freq": np.asarray(freq, dtype=np.float64).reshape(-1),
+            "peak_val": np.ascontiguousarray(np.asarray(val_bits, dtype=np.int32).reshape(-1)).view(np.float32).copy()}
+
+
+def caf_outputs(torch, S, t_surface, t_rowmax, t_rowarg, t_peak):
+    """What CAFPlan.run hands its caller after a step, as host arrays: the peak, and seeded samples of the per-delay
+    results (~2^20 delays) and of the surface rows (~2^14 delays).  The whole outputs (a 17 GB surface, 2 x 67 MB of
+    per-delay results at C2) exceed the dump's bound; the sampled delays are written beside them."""
+    pk = t_peak.cpu().numpy()
+    out = peak_outputs(pk[0:1], pk[1:2], pk[2:3])
+    rows = sample_delays(S, 1 << 20, 1)
+    r = torch.from_numpy(rows).to(t_rowmax.device)
+    out["row_delays"] = rows.astype(np.float64)
+    out["row_max"] = t_rowmax[0].index_select(0, r).cpu().numpy()
+    out["row_arg"] = t_rowarg[0].index_select(0, r).cpu().numpy().astype(np.float64)
+    if t_surface is not None:
+        srows = sample_delays(S, 1 << 14, 2)
+        out["surface_delays"] = srows.astype(np.float64)
+        out["surface"] = t_surface[0].index_select(0, torch.from_numpy(srows).to(t_surface.device)).cpu().numpy()
+    return out
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy, float32 or float64 only, at most 64 MB in all."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte bound" % (total, DUMP_LIMIT_BYTES))
+    bad = [k for k, a in arrays.items() if a.dtype not in (np.float32, np.float64)]
+    if bad:
+        raise SystemExit("--dump-outputs: %r are not float32 / float64" % bad)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 C4_BINS = 512
 
 
@@ -280,6 +334,7 @@ def run_c4(args, torch, dist, device, world, rank, rehearse):
     rank_ms, gather_ms = None, None
     if world > 1:
         elapsed, rank_ms = rank_times(torch, dist, elapsed, args.steps, world, rehearse, device)
+    if world > 1 and args.full:
         fence()
         tg = []
         for _ in range(5):  # the collective alone (the engine's three output arrays, read in place)
@@ -290,6 +345,8 @@ def run_c4(args, torch, dist, device, world, rank, rehearse):
         gather_ms = {"first": tg[0], "median_of_5": float(np.median(tg))}
     if rank != 0:
         return
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, peak_outputs(tb[:, 0], tb[:, 1], tb[:, 2]))  # the all-gathered (T, 3) table
     dt = elapsed / args.steps
     B, step_len, nb = plan.block, plan.step, plan.blocks_per_batch
     ms, n = stages["spectral_conj_multiply"]
@@ -340,6 +397,7 @@ def run_c4(args, torch, dist, device, world, rank, rehearse):
     }
     if rank_ms is not None:
         out["per_rank_ms_per_step"] = {"min": min(rank_ms), "max": max(rank_ms), "ranks": rank_ms}
+    if gather_ms is not None:
         out["peak_table_allgather_ms"] = gather_ms
     print(json.dumps(out))
 
@@ -413,6 +471,12 @@ def run_c2_freq_shard(args, torch, dist, device, world, rank, rehearse):
         elapsed, rank_ms = rank_times(torch, dist, elapsed, args.steps, world, rehearse, device)
     if rank != 0:
         return
+    if args.dump_outputs:
+        # rank 0's per-delay results and surface over its own block of bins; the peak is the reduced global one
+        arrays = caf_outputs(torch, S, t_surface, t_rowmax, t_rowarg, t_peak)
+        d, f, v = state["peak"]
+        arrays.update(peak_outputs([d], [f], np.float32(v).reshape(1).view(np.int32)))
+        write_outputs(args.dump_outputs, arrays)
     dt = elapsed / args.steps
     B, step_len, nb = plan.block, plan.step, plan.blocks_per_batch
     ms, n = stages["spectral_conj_multiply"]
@@ -572,13 +636,20 @@ def main():
                          "measures); 'freq' = ONE template, its 256 bins block-distributed over the ranks (strong scaling)")
     ap.add_argument("--engine", default="auto", choices=["auto", "persistent", "fused", "rocfft"])
     ap.add_argument("--no-surface", action="store_true", help="peak-only mode (no CAF surface written)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the side figures, the CPU baselines and, with several "
+                         "ranks, the collective alone (a plain run times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32/float64, <= 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--rx-log2", type=int, default=24,
                     help="log2 of the rx length (24 = BASELINE's configuration; smaller values are for rehearsals and "
                          "tests only and say so in config.workload)")
     ap.add_argument("--no-side-figure", action="store_true",
-                    help="skip the untimed no-surface side run (profiling: only the measured configuration launches)")
+                    help="with --full: skip the untimed side runs (profiling: only the measured configuration launches)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     # --gpus N without a launcher: this process becomes the launcher.  It starts one child per rank (before anything
     # here touches the GPU), waits for them and forwards rank 0's JSON line; see launch_ranks().
@@ -708,10 +779,17 @@ def main():
         if int(np.argmax(row)) != int(pk[1]) or row.max() != np.float32(got[2]) or row.max() != t_rowmax[0, D0].item() \
                 or not (0.0 <= far.max() < 20.0 / N_TMPL):
             raise SystemExit("rank %d: the surface written by the timed steps does not hold the reported peak" % rank)
+    # (before any side run below writes into the same buffers)
+    if args.dump_outputs and rank == 0:
+        arrays = caf_outputs(torch, S, t_surface, t_rowmax, t_rowarg, t_peak)
+        if world > 1:
+            tb = gathered["table"].cpu().numpy()
+            arrays.update({"table_" + k: v for k, v in peak_outputs(tb[:, 0], tb[:, 1], tb[:, 2]).items()})
+        write_outputs(args.dump_outputs, arrays)
 
-    # side figure (not the metric): the same job when only the per-delay argmax and the peak are wanted
+    # side figure (--full; not the metric): the same job when only the per-delay argmax and the peak are wanted
     extra = None
-    if world == 1 and surface_on and not args.no_side_figure:
+    if args.full and world == 1 and surface_on and not args.no_side_figure:
         stream = torch.cuda.current_stream().cuda_stream
         for _ in range(2):
             plan.run(rx, surface=False, rows=True, peak=True, stream=stream, out=res)
@@ -724,10 +802,11 @@ def main():
         extra = {"ms_per_step": dt * 1e3, "value": S / dt / 1e6, "unit": "Msamples/s",
                  "what": "same workload without the CAF surface (per-delay argmax + peak only)"}
 
-    # second side figure: the same surface written hypothesis-major ([F][S]: the FFT items write their own row segments, no
-    # |y|^2 tiles, no tile role) -- what the host-returning entry points run since round 5 (xcorrRoutines._host_surface)
+    # second side figure (--full): the same surface written hypothesis-major ([F][S]: the FFT items write their own row
+    # segments, no |y|^2 tiles, no tile role) -- what the host-returning entry points run since round 5 (xcorrRoutines._host_surface)
     extra_t = None
-    if world == 1 and surface_on and not args.no_side_figure and plan.engine_used == "persistent" and plan.block == 16384:
+    if args.full and world == 1 and surface_on and not args.no_side_figure and plan.engine_used == "persistent" \
+            and plan.block == 16384:
         stream = torch.cuda.current_stream().cuda_stream
         t_surface = None  # (the delay-major surface is checked and done with: its 17 GB go back to torch's allocator)
         res.surface = None
@@ -759,6 +838,7 @@ def main():
         tb = gathered["table"].cpu().numpy()
         if not all(int(r[0]) == D0 and int(bins[r[1]]) == K0 for r in tb):
             raise SystemExit("gathered peak table is wrong: %r" % (tb,))
+    if world > 1 and args.full:
         rows = t_peak.view(1, 3).cpu() if rehearse else t_peak.view(1, 3)
         fence()
         tg = []
@@ -883,8 +963,9 @@ def main():
             out["surface_t"] = extra_t
         if rank_ms is not None:
             out["per_rank_ms_per_step"] = {"min": min(rank_ms), "max": max(rank_ms), "ranks": rank_ms}
+        if gather_ms is not None:
             out["peak_table_allgather_ms"] = gather_ms
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             rx_h, tm_h = rx[: min(M_RX, D0 + 560000)].cpu().numpy(), tmpl.cpu().numpy()
             out["cpu_baseline"] = cpu_baseline(rx_h, tm_h, bins)
             out["cpu_baseline_threaded"] = cpu_baseline_threaded(rx_h, tm_h)

@@ -7,7 +7,7 @@ LOG=gpurun_out/r3/ab_${A}_${B}.log
 : > $LOG
 for lib in $A $B $A $B; do
   echo "== $lib" >> $LOG
-  env CAF_LIBRARY=$lib timeout -k 10 200 python bench.py --steps 20 --warmup 3 --no-cpu-baseline "$@" 2>&1 | grep "^{" | python -c "
+  env CAF_LIBRARY=$lib timeout -k 10 200 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline "$@" 2>&1 | grep "^{" | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); print('   ', j['engine'], round(j['value'],1), 'Msamples/s', round(j['ms_per_step'],2), 'ms; kernel', round(j['stages_ms_per_step']['spectral_conj_multiply'],3), '; no surface', round(j.get('no_surface',{}).get('ms_per_step',0),2))" >> $LOG || exit 1
 done

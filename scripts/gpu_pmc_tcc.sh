@@ -14,7 +14,7 @@ for cfg in h64 h16; do
   i=0
   for grp in "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_DRAM_sum TCC_EA0_RDREQ_LEVEL_sum" "TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum TCC_EA0_WRREQ_DRAM_sum TCC_EA0_WRREQ_LEVEL_sum" "TCC_EA0_WRREQ_STALL_sum TCC_EA0_RDREQ_DRAM_CREDIT_STALL_sum TCC_EA0_WRREQ_DRAM_CREDIT_STALL_sum GRBM_GUI_ACTIVE" "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_BUBBLE_sum"; do
     i=$((i+1))
-    rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $OUT/$cfg/g$i -- python3 $REPO/bench.py --steps 1 --warmup 1 --no-cpu-baseline > $OUT/$cfg.b$i.json 2> $OUT/$cfg.e$i.err || { tail -5 $OUT/$cfg.e$i.err; exit 1; }
+    rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $OUT/$cfg/g$i -- python3 $REPO/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline > $OUT/$cfg.b$i.json 2> $OUT/$cfg.e$i.err || { tail -5 $OUT/$cfg.e$i.err; exit 1; }
   done
 done
 cd $REPO
