@@ -351,6 +351,18 @@ CAF_EXPORT int32_t caf_zoom_czt(caf_plan plan, int32_t template_index, const flo
 CAF_EXPORT int32_t caf_fir_lfilter(const float* d_x, int64_t n, const float* d_taps, int32_t num_taps,
                                    const float* d_delay, int32_t delay_len, int32_t dsr, int32_t ds_phase, float* d_out,
                                    int64_t out_len, void* stream);
+/* WOLA polyphase channeliser: filterRoutines.wola (filterRoutines.py:578-632), cpuWola.cpu_threaded_wola
+ * (cpuWola.py:19-70 over cpuWolaDll.c:38-178) and the history of filterRoutines.Channeliser (filterRoutines.py:636-690).
+ * Input = the hist_len complex64 samples of d_hist (carried-in history, NULL/0 for none) followed by the n samples of d_x;
+ * output row r < rows (rows <= n / dec) is taken at d_x[r * dec]:
+ *   v[a] = sum_{b < L/N} d_taps[b N + a] * input[r dec - b N - a]   (zero before the history),  a < N = num_channels
+ *   out[r][k] = sum_a v[a] e^{+j 2 pi a k / N}                        (no 1/N), negated at odd k on odd r when N == 2 dec.
+ * num_channels must be dec or 2 * dec and num_taps (L) a multiple of it.  layout 0: d_out is (rows, N) time-major (the
+ * reference's); 1: (N, rows) channel-major, one channel a contiguous rx.  N a power of two 64..16384 with L/N <= 64 runs
+ * one fused kernel; anything else runs polyphase sums + batched rocFFT rows (CAF_WOLA_FUSED=0 forces that).  (ABI 1.10) */
+CAF_EXPORT int32_t caf_wola(const float* d_x, int64_t n, const float* d_hist, int64_t hist_len, const float* d_taps,
+                            int64_t num_taps, int32_t num_channels, int32_t dec, int32_t layout, float* d_out, int64_t rows,
+                            void* stream);
 /* upfirdn_naive / upfirdn_sm (upfirdn.cu:6-182) == scipy.signal.upfirdn(taps, x, up, down) per row */
 CAF_EXPORT int32_t caf_upfirdn(const float* d_x, int64_t rows, int64_t n, const float* d_taps, int32_t num_taps,
                                int32_t up, int32_t down, float* d_out, float* d_out_abs, int64_t out_len, void* stream);

@@ -154,6 +154,7 @@ _SIGNATURES = {
     "caf_gather_b32": [_P, _I64, _P, _I64, _P, _P],
     "caf_gather_f32_f64": [_P, _I64, _P, _I64, _P, _P],
     "caf_fir_lfilter": [_P, _I64, _P, _I32, _P, _I32, _I32, _I32, _P, _I64, _P],
+    "caf_wola": [_P, _I64, _P, _I64, _P, _I64, _I32, _I32, _I32, _P, _I64, _P],
     "caf_upfirdn": [_P, _I64, _I64, _P, _I32, _I32, _I32, _P, _P, _I64, _P],
     "caf_czt_run_many": [_P, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P],
     "caf_argmax3d_u32": [_P, _I64, _I32, _I32, _I32, _P, _P, _P],

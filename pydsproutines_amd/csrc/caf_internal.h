@@ -218,6 +218,16 @@ void launch_zoom_finish(const float* trace, const int32_t* row_arg, const double
                         int32_t* o_count, int32_t* o_delay, int32_t* o_cidx, float* o_cqf2, int32_t* o_fidx, double* o_ffreq,
                         float* o_fqf2, hipStream_t st);
 
+// caf_wola.hip: WOLA channeliser.  Fused in-LDS kernel for N = 2^6 .. 2^14 and P = L / N <= WOLA_FUSED_PMAX; the polyphase
+// sums of any N for the rocFFT rows (rotation of the odd rows folded in), and the (rows, N) -> (N, rows) transpose
+constexpr int WOLA_FUSED_PMAX = 64;
+bool wola_fused_ok(int32_t N, int64_t P);
+int launch_wola_fused(const float2* x, const float2* hist, int64_t hlen, const float* taps, int32_t P, int32_t N, int32_t dec,
+                      int32_t layout, float2* out, int64_t rows, hipStream_t st);
+int launch_wola_poly(const float2* x, const float2* hist, int64_t hlen, const float* taps, int32_t P, int32_t N, int32_t dec,
+                     float2* V, int64_t rows, hipStream_t st);
+int launch_wola_transpose(const float2* src, int64_t rows, int32_t N, float2* dst, hipStream_t st);
+
 // caf_firos.hip: overlap-save FIR (fused in-LDS form for <= 8192 taps; gather / scatter kernels for the rocFFT rows)
 int fir_os_fused_block(int32_t ntaps);
 // rows > 1: independent signals x + r x_row_stride -> out + r out_row_stride in one launch (no carried-in history)

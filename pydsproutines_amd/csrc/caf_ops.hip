@@ -572,6 +572,46 @@ int32_t caf_fir_lfilter(const float* d_x, int64_t n, const float* d_taps, int32_
     return CAF_OK;
 }
 
+int32_t caf_wola(const float* d_x, int64_t n, const float* d_hist, int64_t hist_len, const float* d_taps, int64_t num_taps,
+                 int32_t num_channels, int32_t dec, int32_t layout, float* d_out, int64_t rows, void* stream) {
+    const int32_t N = num_channels;
+    CAF_REQUIRE(N >= 1 && dec >= 1 && (N == dec || N == 2 * dec),
+                "caf_wola: num_channels must equal dec or 2 * dec (the reference's phase correction)");
+    CAF_REQUIRE(num_taps >= 1 && num_taps % N == 0, "caf_wola: num_taps must be a positive multiple of num_channels");
+    CAF_REQUIRE(layout == 0 || layout == 1, "caf_wola: layout must be 0 (rows, N) or 1 (N, rows)");
+    CAF_REQUIRE(n >= 0 && rows >= 0 && rows <= n / dec, "caf_wola: rows must be <= n / dec");
+    CAF_REQUIRE(hist_len >= 0 && (hist_len == 0 || d_hist), "caf_wola: hist_len > 0 needs d_hist");
+    if (rows == 0) return CAF_OK;
+    CAF_REQUIRE(d_x && d_taps && d_out, "caf_wola: NULL buffer");
+    const int64_t P = num_taps / N;
+    CAF_REQUIRE(P <= 0x7fffffff, "caf_wola: too many taps");
+    hipStream_t st = (hipStream_t)stream;
+    const float2* x = (const float2*)d_x;
+    const float2* h = (const float2*)d_hist;
+    float2* out = (float2*)d_out;
+    // CAF_WOLA_FUSED=0 forces the rocFFT rows (A/B and cross-checks); read per call like CAF_JIT
+    const char* ef = std::getenv("CAF_WOLA_FUSED");
+    const bool fused = wola_fused_ok(N, P) && !(ef && ef[0] == '0');
+    if (const char* ed = std::getenv("CAF_WOLA_DEBUG"))
+        if (ed[0] == '1')
+            std::fprintf(stderr, "[caf wola] path=%s N=%d dec=%d P=%lld rows=%lld layout=%d\n", fused ? "fused" : "rocfft", (int)N,
+                         (int)dec, (long long)P, (long long)rows, (int)layout);
+    if (fused) return launch_wola_fused(x, h, hist_len, d_taps, (int32_t)P, N, dec, layout, out, rows, st);
+    // general path: polyphase sums (rotation folded in) -> batched backward rocFFT in place -> (layout 1) transpose
+    Scratch sc;
+    float2* V = out;
+    int rc;
+    if (layout == 1 && (rc = sc.get(&V, rows * (int64_t)N))) return rc;
+    if ((rc = launch_wola_poly(x, h, hist_len, d_taps, (int32_t)P, N, dec, V, rows, st))) return rc;
+    if ((rc = fft_rows(V, V, rows, N, true, st))) return rc;
+    if (layout == 1) {
+        if ((rc = launch_wola_transpose(V, rows, N, out, st))) return rc;
+        if (st != nullptr) CAF_HIP_TRY(hipStreamSynchronize(st));  // scratch: see fir_overlap_save
+    }
+    CAF_HIP_TRY(hipGetLastError());
+    return CAF_OK;
+}
+
 int32_t caf_iq16_fir_decimate(const int16_t* d_iq, int64_t num_samples, float scale, const float* d_taps, int32_t num_taps,
                               const int16_t* d_delay, int32_t delay_len, int32_t dsr, int32_t ds_phase, float* d_out,
                               int64_t out_len, void* stream) {

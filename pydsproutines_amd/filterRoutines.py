@@ -4,7 +4,8 @@
 Semantics pinned by the reference itself: FIR == scipy.signal.lfilter(taps, 1, x)
 (benchmark_filterkernels.py:72-74), upfirdn == scipy.signal.upfirdn
 (benchmark_upfirdnkernels.py:58-67), moving average == lfilter(ones(L)/L)
-(filterRoutines.py:1256), moving complex sum == |np.convolve(x, ones(L), 'valid')|^2 (:1358).
+(filterRoutines.py:1256), moving complex sum == |np.convolve(x, ones(L), 'valid')|^2 (:1358),
+WOLA channeliser == filterRoutines.wola (:578-632) and its streaming wrapper Channeliser (:636-690).
 CUDA launch-tuning kwargs are accepted and ignored.
 """
 
@@ -189,4 +190,118 @@ def cupyComplexMovingSum(x, sumLength, NUM_PER_THREAD=33, THREADS_PER_BLK=32, su
     return d_out
 
 
-__all__ = ["CupyKernelFilter", "cupyMultiMovingAverage", "cupyMovingAverage", "cupyComplexMovingSum", "DeviceArray"]
+# -- WOLA channeliser -------------------------------------------------------------------------
+_LAYOUTS = {"time": 0, "channel": 1}
+
+
+def _wola_device(d_x, f_tap, N, Dec, d_hist=None, layout="time"):
+    """caf_wola on a complex64 DeviceArray: (rows, N) ("time") or (N, rows) ("channel"), rows = len(x) // Dec,
+    history d_hist (DeviceArray or None) in front of d_x.  Returns a DeviceArray."""
+    if layout not in _LAYOUTS:
+        raise ValueError("layout must be 'time' or 'channel'.")
+    _lib.require_device()
+    requireDtype(np.complex64, d_x)
+    N, Dec = int(N), int(Dec)
+    rows = d_x.size // Dec
+    d_out = empty((rows, N) if layout == "time" else (N, rows), np.complex64)
+    if rows == 0:
+        return d_out
+    d_taps = asarray(np.ascontiguousarray(f_tap, dtype=np.float32).ravel())
+    _lib.check(_lib.load().caf_wola(_p(d_x), d_x.size, _p(d_hist), d_hist.size if d_hist is not None else 0, _p(d_taps),
+                                    d_taps.size, N, Dec, _LAYOUTS[layout], _p(d_out), rows, None), "caf_wola")
+    return d_out
+
+
+def wola(f_tap, x, Dec, N=None, dtype=np.complex64):
+    """WOLA channeliser (ref: filterRoutines.py:578-632): (floor(len(x) / Dec), N) channel outputs, N = Dec by default
+    (non-overlapping channels) or 2 Dec.  Computed on the GPU in float32; a complex128 ``dtype`` is a cast of that result."""
+    if N == None:  # noqa: E711 (the reference's own test: an explicit N must compare unequal to None)
+        N = Dec
+        print("Defaulting to " + str(N))
+    elif N / Dec != 2:
+        raise Exception("Only supporting up to N/Dec = 2.")
+    if len(f_tap) % N != 0:
+        raise Exception("Length must be integer multiple of N.")
+    print("N = %i, Dec = %i" % (N, Dec))
+    d_x = x if isinstance(x, DeviceArray) else asarray(np.asarray(x, dtype=np.complex64).ravel())
+    out = _wola_device(d_x, f_tap, int(N), int(Dec)).get()
+    return out.astype(dtype, copy=False)
+
+
+class Channeliser:
+    """Streaming WOLA channeliser (ref: filterRoutines.py:636-690): keeps the last L = len(f_tap) input samples and
+    channelises [history, x], returning rows L / Dec onwards.  As in the reference, the odd-row phase correction
+    (N == 2 Dec) restarts with every call, so chunked calls equal one long call only for chunk lengths that are
+    multiples of 2 Dec.
+
+    Host input runs through the staging lanes and returns a numpy array.  DeviceArray input keeps the history on the
+    device and returns a DeviceArray; ``layout="channel"`` (an extension, not in the reference) returns it
+    channel-major, (numChannels, rows), so that one channel is a contiguous rx for ``CAFPlan.run``."""
+
+    def __init__(self, numTaps, numChannels, Dec, NUM_THREADS=4, f_tap=None):
+        if f_tap is None:
+            import scipy.signal as sps  # only for the default taps
+
+            self.f_tap = sps.firwin(numTaps, 1.0 / Dec).astype(np.float32)
+        else:
+            self.f_tap = f_tap.astype(np.float32)
+        self.numChannels = int(numChannels)
+        self.Dec = int(Dec)
+        self.NUM_THREADS = int(NUM_THREADS)  # accepted, ignored
+        self.reset()
+        self.jump = int(self.f_tap.size / self.Dec)
+
+    def reset(self):
+        self.delay = np.zeros(self.f_tap.size, dtype=np.complex64)
+        self._d_delay = None  # device copy of the history (device input), made from self.delay on first use
+
+    def channelise(self, x, layout="time"):
+        from .cpuWola import _check_args
+
+        if layout not in _LAYOUTS:
+            raise ValueError("layout must be 'time' or 'channel'.")
+        if _check_args(self.f_tap.size, self.numChannels, self.Dec):
+            # the reference unpacks cpu_threaded_wola's bare `return 1`
+            raise TypeError("cannot unpack non-iterable int object")
+        L = self.f_tap.size
+        if isinstance(x, DeviceArray):
+            requireDtype(np.complex64, x)
+            if x.size % self.Dec != 0:  # np.empty(int(siglen / Dec * fftlen)).reshape(...) in the reference
+                raise ValueError("cannot reshape array of size %d into shape (%d,%d)"
+                                 % (int((x.size + L) / self.Dec * self.numChannels), (x.size + L) // self.Dec, self.numChannels))
+            if self._d_delay is None:
+                self._d_delay = asarray(self.delay)
+            d_out = _wola_device(x, self.f_tap, self.numChannels, self.Dec, d_hist=self._d_delay, layout=layout)
+            if x.size < L:
+                raise ValueError("could not broadcast input array from shape (%d,) into shape (%d,)" % (x.size, L))
+            # the new history: the last L input samples, device to device, behind the kernel on the same stream
+            lib = _lib.load()
+            _lib.check(lib.caf_d2d(_p(self._d_delay), ct.c_void_p(x.ptr + (x.size - L) * 8), L * 8, None))
+            _lib.check(lib.caf_stream_sync(None))
+            return d_out
+        x = np.asarray(x)
+        if x.size % self.Dec != 0:
+            raise ValueError("cannot reshape array of size %d into shape (%d,%d)"
+                             % (int((x.size + L) / self.Dec * self.numChannels), (x.size + L) // self.Dec, self.numChannels))
+        if self._d_delay is not None:
+            self.delay[:] = self._d_delay.get()
+            self._d_delay = None
+        d_out = _wola_device(asarray(x.astype(np.complex64, copy=False).ravel()), self.f_tap, self.numChannels, self.Dec,
+                             d_hist=asarray(self.delay), layout=layout)
+        channels = d_out.get()
+        self.delay[:] = x[-self.delay.size:]  # (raises for len(x) < L, as the reference's copy does)
+        return channels
+
+    def channelFreqs(self, fs: float = 1.0):
+        """Returns the centre frequency for each channel."""
+        from .signalCreationRoutines import makeFreq
+
+        return makeFreq(self.numChannels, fs)
+
+    def channelFs(self, fs: float = 1.0):
+        """Returns the new sampling rate for each channel."""
+        return fs / self.Dec
+
+
+__all__ = ["CupyKernelFilter", "cupyMultiMovingAverage", "cupyMovingAverage", "cupyComplexMovingSum", "DeviceArray", "wola",
+           "Channeliser"]
