@@ -1306,8 +1306,12 @@ __global__ __launch_bounds__(256) void k_transpose_norm_argmax(
 // ----------------------------------------------------------------------------------------
 // What the publish / consume pair below relies on (measured on gfx950 / ROCm 7.2: MI355X_MICROARCH.md, "Workgroup
 // dispatch, XCD placement & inter-workgroup visibility", valid forms + the table of measured hand-offs; NOT
-// guarantees of the HSA memory model -- which is why tests/test_gpu_persistent_protocol.py runs the residency
-// matrix in every suite run):
+// guarantees of the HSA memory model -- which is why tests/test_gpu_persistent_protocol.py runs, in every suite run,
+// every producer / consumer pair below (fused_item KIND 0 / 1 / 5, persistent_fft_item2, persistent_fft_item2f with
+// and without partitions -> transpose_wave<SURF, 1|2>, transpose_wave_f1<1|2>, reduce_wave_nosurf) over a residency
+// matrix, one block per launch and two plans on two streams, with CAF_PERSIST_POISON=1 (the tile buffer holds a fixed
+// pattern before each launch), sentinel-filled outputs and alternating inputs, bit for bit against the default
+// residency: a tile read before it was published, or never written, shows in the outputs):
 //   producer (persistent_fft_item):
 //     P1 every |y|^2 / (value, hypothesis) store of the item is an sc1 (write-through) store: the bytes leave the
 //        XCD's L2 towards memory instead of staying dirty in it (gst1_wt / __hip_atomic_store relaxed, agent scope);

@@ -20,6 +20,9 @@ void set_error(const std::string& msg) { g_last_error = msg; }
 
 using namespace caf;
 
+// CAF_PERSIST_POISON: the fill of the tile / pair buffer (~1e30 as a float; as an int32 hypothesis number far past any plan's)
+constexpr uint32_t POISON_VT = 0x7149F2CAu;
+
 // Auxiliary stream + fork/join events of a plan, checked out of a small per-device list: creating and destroying
 // a HIP stream costs ~1 ms, as much as a whole small CAF job, and the per-call entry points of the host layer
 // build a plan per call.  A released set is idle (the plan synchronises the device before releasing).
@@ -1040,6 +1043,13 @@ int32_t caf_plan_execute2(caf_plan p, const float* d_rx, int64_t rx_len, int64_t
                     (out->d_row_max || out->d_surface || (want_peak && f1_pk_env));
         f1_item_peaks = f1_direct && want_peak && f1_pk_env;
         const int nb_launch = ns_gpt ? p->nb_nosurf : p->nb;  // blocks per launch
+        // CAF_PERSIST_POISON=1 (diagnostic, for the protocol tests): the tile / pair buffer is filled with POISON_VT before every
+        // launch that has tile items, so that a tile read before its producer published it is wrong data, not the same bits
+        // left behind by an earlier call.  Read on every call (a test switches it on and off).  The whole allocation is
+        // filled: it holds the |y|^2 tiles of nb blocks, and the vmax / imax pairs of nb_nosurf blocks fit in it as well.
+        const char* poison_env = getenv("CAF_PERSIST_POISON");
+        const bool poison = poison_env && atoi(poison_env);
+        const size_t vt_count = (size_t)p->nb * p->tiles_per_blk * T * F * 64;
         for (int64_t b0 = 0; p->persistent && b0 < nblk; b0 += nb_launch) {
             const int32_t nbk = (int32_t)std::min<int64_t>(nb_launch, nblk - b0);
             PersistParams h;
@@ -1107,6 +1117,7 @@ int32_t caf_plan_execute2(caf_plan p, const float* d_rx, int64_t rx_len, int64_t
                 std::memset(h_dbg, 0, sizeof(int32_t) * 8 * (size_t)p->n_cus);
                 (void)hipHostGetDevicePointer((void**)&h.dbg, h_dbg, 0);
             }
+            if (poison && h.n_tr > 0) CAF_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)p->d_vt, (int)POISON_VT, vt_count, st));
             p->stage_begin(3, st);
             launch_caf_persistent(&h, p->d_params, p->n_cus, st);
             p->stage_end(st);
@@ -1181,6 +1192,7 @@ int32_t caf_plan_execute2(caf_plan p, const float* d_rx, int64_t rx_len, int64_t
         }
         for (int64_t b0 = 0; !p->persistent && b0 < nblk; b0 += p->nb) {
             const int32_t nbk = (int32_t)std::min<int64_t>(p->nb, nblk - b0);
+            if (poison) CAF_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)p->d_vt, (int)POISON_VT, vt_count, st));
             p->stage_begin(3, st);
             launch_fused_caf(p->d_xb + b0 * (int64_t)p->B, p->d_hc, p->d_shifts, p->d_tw1, p->d_tw23,
                              p->mul_mode == 2 ? 1 : 0, F, T * F, p->hyp_per_wg, nbk, p->tiles_per_blk, p->d_vt, st);
