@@ -363,6 +363,44 @@ CAF_EXPORT int32_t caf_fir_lfilter(const float* d_x, int64_t n, const float* d_t
 CAF_EXPORT int32_t caf_wola(const float* d_x, int64_t n, const float* d_hist, int64_t hist_len, const float* d_taps,
                             int64_t num_taps, int32_t num_channels, int32_t dec, int32_t layout, float* d_out, int64_t rows,
                             void* stream);
+/* ---- burst detection (filterRoutines.py:701-1088, thresholding.cu:27-225).  Added after ABI 1.10 without a version bump:
+ * clients detect these entry points by symbol.  dtype / is_f64 select float32 (0) or float64 (1) real input. ---- */
+/* BurstDetector.medfilt (:805-819): d_abs = |x| (hypot for complex), d_ampsq = d_abs * d_abs in the same precision
+ * (not re^2 + im^2).  dtype 0 complex64 -> float32, 1 complex128 -> float64, 2 float32, 3 float64 (abs only). */
+CAF_EXPORT int32_t caf_abs_ampsq(const void* d_x, int64_t n, int32_t dtype, void* d_abs, void* d_ampsq, void* stream);
+/* cupyx.scipy.signal.medfilt as called by BurstDetector.medfilt / energyDetection (:819, :1073): d_out[i] = the order
+ * statistic kernel_size / 2 of x[i - W/2 .. i + W/2], samples outside [0, n) counted as +0.0 (== scipy.signal.medfilt).
+ * kernel_size odd >= 1, may exceed n.  Small windows select in registers; larger ones (or CAF_MEDFILT_GENERAL=1) query a
+ * wavelet matrix built in pool scratch. */
+CAF_EXPORT int32_t caf_medfilt(const void* d_x, int64_t n, int32_t is_f64, int64_t kernel_size, void* d_out, void* stream);
+/* thresholdEdges (thresholding.cu:27-156) in the reference's layout: B = threads_per_block - 2, rows = ceil(n / B);
+ * sample i >= 1 belongs to row (i - 1) / B; m[j] = x[j] > threshold, m[n] = 0; +i for a left edge (m[i] && !m[i-1] &&
+ * m[i+1]), -i for a right edge (m[i] && m[i-1] && !m[i+1]).  d_edges (rows, edges_max): each row's first edges_max edges
+ * in ascending order, then zeros; d_counts[row] = the row's true count.  3 <= threads_per_block <= 1024, n < 2^31. */
+CAF_EXPORT int32_t caf_threshold_edges(const float* d_x, int64_t n, float threshold, int32_t threads_per_block,
+                                       int32_t edges_max, int32_t* d_edges, int32_t* d_counts, void* stream);
+/* gatherThresholdEdgesResults (thresholding.cu:159-225): the stored edges of rows with a non-zero count (the first
+ * min(count, edges_max) entries, zeros skipped), row-major, through the pairing state machine (left = 0; a left edge sets
+ * left; a right edge R emits (left, R) when min_len <= R - left <= max_len and resets left to 0).  Writes the first
+ * min(K, capacity) int32 pairs to d_pairs[K][2]; *h_num_pairs = K (host).  Synchronises the stream. */
+CAF_EXPORT int32_t caf_gather_edges(const int32_t* d_edges, int64_t rows, int32_t edges_max, const int32_t* d_counts,
+                                    int32_t min_len, int32_t max_len, int32_t* d_pairs, int64_t capacity,
+                                    int64_t* h_num_pairs, void* stream);
+/* BurstDetector.detectViaThreshold (:843-852): the K int64 indices with x > threshold (threshold cast to the array's
+ * dtype) and, for each of the R maximal runs of consecutive indices, the position in that index array where it starts.
+ * h_counts[0] = K, h_counts[1] = R (host).  d_idx == NULL: counts only.  Synchronises the stream. */
+CAF_EXPORT int32_t caf_threshold_indices(const void* d_x, int64_t n, int32_t is_f64, double threshold, int64_t* d_idx,
+                                         int64_t idx_cap, int64_t* d_run_starts, int64_t runs_cap, int64_t* h_counts,
+                                         void* stream);
+/* cp.histogram(x, edges)[0] of autoDetectThreshold (:911) == np.histogram: bins [e_i, e_i+1), the last one closed,
+ * compared in float64; values outside the edges and NaN are not counted.  d_edges increasing, num_edges >= 2;
+ * d_counts int64[num_edges - 1]. */
+CAF_EXPORT int32_t caf_histogram(const void* d_x, int64_t n, int32_t is_f64, const double* d_edges, int64_t num_edges,
+                                 int64_t* d_counts, void* stream);
+/* the column means of detectRegularSections (:964-967): d_out[c] = mean_r (absolute ? |x[r][c]| : x[r][c]) of a
+ * (rows, cols) matrix, accumulated in float64. */
+CAF_EXPORT int32_t caf_column_means(const void* d_x, int64_t rows, int64_t cols, int32_t is_f64, int32_t absolute,
+                                    double* d_out, void* stream);
 /* upfirdn_naive / upfirdn_sm (upfirdn.cu:6-182) == scipy.signal.upfirdn(taps, x, up, down) per row */
 CAF_EXPORT int32_t caf_upfirdn(const float* d_x, int64_t rows, int64_t n, const float* d_taps, int32_t num_taps,
                                int32_t up, int32_t down, float* d_out, float* d_out_abs, int64_t out_len, void* stream);

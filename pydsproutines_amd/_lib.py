@@ -155,6 +155,13 @@ _SIGNATURES = {
     "caf_gather_f32_f64": [_P, _I64, _P, _I64, _P, _P],
     "caf_fir_lfilter": [_P, _I64, _P, _I32, _P, _I32, _I32, _I32, _P, _I64, _P],
     "caf_wola": [_P, _I64, _P, _I64, _P, _I64, _I32, _I32, _I32, _P, _I64, _P],
+    "caf_abs_ampsq": [_P, _I64, _I32, _P, _P, _P],
+    "caf_medfilt": [_P, _I64, _I32, _I64, _P, _P],
+    "caf_threshold_edges": [_P, _I64, ct.c_float, _I32, _I32, _P, _P, _P],
+    "caf_gather_edges": [_P, _I64, _I32, _P, _I32, _I32, _P, _I64, ct.POINTER(_I64), _P],
+    "caf_threshold_indices": [_P, _I64, _I32, ct.c_double, _P, _I64, _P, _I64, ct.POINTER(_I64), _P],
+    "caf_histogram": [_P, _I64, _I32, _P, _I64, _P, _P],
+    "caf_column_means": [_P, _I64, _I64, _I32, _I32, _P, _P],
     "caf_upfirdn": [_P, _I64, _I64, _P, _I32, _I32, _I32, _P, _P, _I64, _P],
     "caf_czt_run_many": [_P, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P],
     "caf_argmax3d_u32": [_P, _I64, _I32, _I32, _I32, _P, _P, _P],

@@ -5,8 +5,11 @@ Semantics pinned by the reference itself: FIR == scipy.signal.lfilter(taps, 1, x
 (benchmark_filterkernels.py:72-74), upfirdn == scipy.signal.upfirdn
 (benchmark_upfirdnkernels.py:58-67), moving average == lfilter(ones(L)/L)
 (filterRoutines.py:1256), moving complex sum == |np.convolve(x, ones(L), 'valid')|^2 (:1358),
-WOLA channeliser == filterRoutines.wola (:578-632) and its streaming wrapper Channeliser (:636-690).
-CUDA launch-tuning kwargs are accepted and ignored.
+WOLA channeliser == filterRoutines.wola (:578-632) and its streaming wrapper Channeliser (:636-690),
+burst detection == cupyThresholdEdges / cupyGatherEdges / BurstDetector / energyDetection (:701-1088) with the
+median of cupyx.scipy.signal.medfilt (== scipy.signal.medfilt) as ``medfilt``.
+CUDA launch-tuning kwargs are accepted and ignored (except THREADS_PER_BLOCK / edgesMaxPerBlock of cupyThresholdEdges,
+which set its output layout).
 """
 
 import ctypes as ct
@@ -303,5 +306,293 @@ class Channeliser:
         return fs / self.Dec
 
 
+# -- burst detection (filterRoutines.py:701-1088) ---------------------------------------------------------------------
+_REAL_OF = {np.dtype(np.complex64): (0, np.float32), np.dtype(np.complex128): (1, np.float64),
+            np.dtype(np.float32): (2, np.float32), np.dtype(np.float64): (3, np.float64)}
+
+
+def _is_f64(d_x):
+    requireDtype((np.float32, np.float64), d_x)
+    return 1 if d_x.dtype == np.float64 else 0
+
+
+def medfilt(d_x, kernel_size=None):
+    """cupyx.scipy.signal.medfilt for a 1-D float32 / float64 DeviceArray: out[i] = the median of
+    x[i - W//2 .. i + W//2] with zeros outside the array (== scipy.signal.medfilt, exactly).  Host arrays are uploaded.
+    Deviation: cupyx would filter a 2-D array with a 2-D window; here 2-D input raises ValueError."""
+    import warnings
+
+    W = 3 if kernel_size is None else kernel_size
+    if np.ndim(W) != 0:
+        if len(W) != 1:
+            raise ValueError("kernel_size must have one element per dimension of a 1-D array.")
+        W = W[0]
+    W = int(W)
+    if W % 2 != 1:
+        raise ValueError("Each element of kernel_size should be odd.")
+    if not isinstance(d_x, DeviceArray):
+        d_x = np.asarray(d_x)
+    if d_x.ndim != 1:
+        raise ValueError("medfilt: only 1-D arrays are supported (got %d-D)." % d_x.ndim)
+    is_f64 = _is_f64(d_x)
+    if W > d_x.shape[0]:
+        warnings.warn("kernel_size exceeds volume extent: the volume will be zero-padded.")
+    _lib.require_device()
+    d_x = asarray(d_x)
+    d_out = empty(d_x.shape, d_x.dtype)
+    _lib.check(_lib.load().caf_medfilt(_p(d_x), d_x.size, is_f64, W, _p(d_out), None), "caf_medfilt")
+    return d_out
+
+
+def _abs_ampsq(d_x):
+    """(|x|, |x| * |x|) in one pass: the cp.abs(x) and d_absx * d_absx of BurstDetector.medfilt (:817-818)."""
+    if d_x.dtype not in _REAL_OF:
+        raise TypeError("Must be one of complex64, complex128, float32, float64, found %s" % d_x.dtype)
+    code, rdt = _REAL_OF[d_x.dtype]
+    d_abs, d_sq = empty(d_x.shape, rdt), empty(d_x.shape, rdt)
+    _lib.check(_lib.load().caf_abs_ampsq(_p(d_x), d_x.size, code, _p(d_abs), _p(d_sq), None), "caf_abs_ampsq")
+    return d_abs, d_sq
+
+
+def cupyThresholdEdges(d_x, threshold, THREADS_PER_BLOCK=128, edgesMaxPerBlock=None, ignoreEdgesCountCheck=True):
+    """ref: filterRoutines.py:701-747, thresholding.cu:27-156.  Returns (d_edges (rows, edgesMaxPerBlock) int32,
+    d_edgeBlockCounts (rows,) int32) with rows = ceil(n / (THREADS_PER_BLOCK - 2)): row r holds the edges of samples
+    r B + 1 .. r B + B (B = THREADS_PER_BLOCK - 2) in ascending order, +i for a left edge and -i for a right edge, then
+    zeros; the counts are the true ones (edges past edgesMaxPerBlock are dropped).  THREADS_PER_BLOCK and
+    edgesMaxPerBlock set that layout and are honoured.  Deviation: a run reaching the last sample ends in a right edge
+    at n - 1 (the sample past the end counts as below the threshold; the reference reads uninitialised memory)."""
+    if d_x.dtype != np.float32:
+        raise TypeError("d_x must be float32.")
+    tpb = int(THREADS_PER_BLOCK)
+    if not 3 <= tpb <= 1024:
+        raise ValueError("THREADS_PER_BLOCK must be in [3, 1024].")
+    emax = tpb if edgesMaxPerBlock is None else int(edgesMaxPerBlock)
+    if emax < 1:
+        raise ValueError("edgesMaxPerBlock must be >= 1.")
+    n = d_x.size
+    if n >= 2 ** 31:
+        raise ValueError("cupyThresholdEdges: d_x must have fewer than 2^31 samples (edges are int32).")
+    _lib.require_device()
+    B = tpb - 2
+    rows = -(-n // B)
+    d_edges = empty((rows, emax), np.int32)
+    d_counts = empty(rows, np.int32)
+    _lib.check(_lib.load().caf_threshold_edges(_p(d_x), n, float(np.float32(threshold)), tpb, emax, _p(d_edges),
+                                               _p(d_counts), None), "caf_threshold_edges")
+    if not ignoreEdgesCountCheck and rows and np.any(d_counts.get() > emax):
+        raise RuntimeError("Some blocks have dropped their edges!")
+    return d_edges, d_counts
+
+
+def cupyGatherEdges(d_edges, d_edgeBlockCounts, minimumLength=0, maximumLength=2147483647):
+    """ref: filterRoutines.py:750-794, thresholding.cu:159-225: the stored edges, row by row, through the reference's
+    pairing state machine.  Returns a (K, 2) int32 DeviceArray of (start, end) pairs, ends inclusive."""
+    requireDtype(np.int32, d_edges)
+    requireDtype(np.int32, d_edgeBlockCounts)
+    if d_edges.ndim != 2 or d_edgeBlockCounts.size != d_edges.shape[0]:
+        raise ValueError("d_edges must be (rows, edgesMaxPerBlock) with one count per row.")
+    _lib.require_device()
+    rows, emax = d_edges.shape
+    lib = _lib.load()
+    cap = max(d_edges.size, 1)
+    d_tmp = empty((cap, 2), np.int32)
+    K = ct.c_int64(0)
+    _lib.check(lib.caf_gather_edges(_p(d_edges), rows, max(emax, 1), _p(d_edgeBlockCounts), int(minimumLength),
+                                    int(maximumLength), _p(d_tmp), cap, ct.byref(K), None), "caf_gather_edges")
+    d_out = empty((K.value, 2), np.int32)
+    if K.value:
+        _lib.check(lib.caf_d2d(_p(d_out), _p(d_tmp), d_out.nbytes, None), "caf_d2d")
+        _lib.check(lib.caf_stream_sync(None), "sync")
+    return d_out
+
+
+def _threshold_runs(d_x, threshold):
+    """(int64 indices of x > threshold, host array of the positions where each run of consecutive indices starts)."""
+    is_f64 = _is_f64(d_x)
+    lib = _lib.load()
+    counts = (ct.c_int64 * 2)()
+    _lib.check(lib.caf_threshold_indices(_p(d_x), d_x.size, is_f64, float(threshold), None, 0, None, 0, counts, None),
+               "caf_threshold_indices")
+    d_idx, d_starts = empty(counts[0], np.int64), empty(counts[1], np.int64)
+    if counts[0]:
+        _lib.check(lib.caf_threshold_indices(_p(d_x), d_x.size, is_f64, float(threshold), _p(d_idx), counts[0],
+                                             _p(d_starts), counts[1], counts, None), "caf_threshold_indices")
+    return d_idx, d_starts.get()
+
+
+def _split_indices(signalIndices):
+    """np.split at every jump of more than one sample (:848-851)."""
+    splitIndices = np.argwhere(np.diff(signalIndices) > 1).flatten() + 1
+    return np.split(signalIndices, splitIndices)
+
+
+class BurstDetector:
+    """ref: filterRoutines.py:797-1035.  Arrays stay on the device (DeviceArray); the k-means of detectSingleEmitter and
+    detectRegularSections runs on the host with scipy.cluster.vq, as in the reference.  pgplot / plotAutoThreshold
+    (plotting) are not provided."""
+
+    def __init__(self, medfiltlen: int):
+        self.medfiltlen = medfiltlen
+
+        # Placeholders for later results
+        self.d_absx = None
+        self.d_ampSq = None
+        self.d_medfiltered = None
+        self.threshold = None
+        self.codebook = None
+        self.counts = None  # Used in auto threshold detection
+        self.edges = None  # Used in auto threshold detection
+
+    def medfilt(self, x):
+        """|x|, |x|^2 (computed as |x| * |x|) and the median filter of |x|^2 (:805-819)."""
+        d_x = x if isinstance(x, DeviceArray) else np.asarray(x)
+        if d_x.dtype not in _REAL_OF:
+            raise TypeError("Must be one of complex64, complex128, float32, float64, found %s" % d_x.dtype)
+        W = 3 if self.medfiltlen is None else int(self.medfiltlen)
+        if W % 2 != 1:
+            raise ValueError("Each element of kernel_size should be odd.")
+        _lib.require_device()
+        self.d_absx, self.d_ampSq = _abs_ampsq(asarray(d_x))
+        self.d_medfiltered = medfilt(self.d_ampSq, self.medfiltlen)
+
+    @staticmethod
+    def imposeSignalLengthLimits(signalIndices: list, minLength: int = 0, maxLength: int = None):
+        """
+        Use this after signalIndices are returned from the detection methods
+        in order to weed out the nonsense ones.
+        """
+        if maxLength is None:
+            maxLength = 4294967295  # arbitrarily gonna set uint32 4294967295 as the max
+        return [i for i in signalIndices if i.size >= minLength and i.size <= maxLength]
+
+    @staticmethod
+    def getStartAndEndIdx(signalIdx):
+        return signalIdx[0], signalIdx[-1]
+
+    def detectViaThreshold(self, threshold: float):
+        """A list of int64 DeviceArray views, one per run of consecutive indices above the threshold (the threshold cast
+        to the array's dtype), into one index array; [empty] when nothing is above it (:843-852)."""
+        self.threshold = threshold  # Kept for plotting
+        _lib.require_device()
+        d_idx, starts = _threshold_runs(self.d_medfiltered, threshold)
+        if starts.size == 0:
+            return [d_idx]
+        bounds = list(starts[1:]) + [d_idx.size]
+        return [d_idx[int(a):int(b)] for a, b in zip(starts, bounds)]
+
+    def detectViaThresholdWithLengthLimits(self, threshold: float, minLength: int = 0, maxLength: int = 2147483647):
+        """(K, 2) int32 DeviceArray of (start, end) pairs, ends inclusive (:854-889).  Kept from the reference: the
+        length limits compare end - start (imposeSignalLengthLimits compares end - start + 1), runs of one sample are
+        dropped, and cupyCopySlicesToMatrix_32fc copies x[start:end], i.e. without the end sample."""
+        self.threshold = threshold
+        d_edges, d_edgeBlockCounts = cupyThresholdEdges(self.d_medfiltered, threshold, edgesMaxPerBlock=32,
+                                                        ignoreEdgesCountCheck=True)
+        return cupyGatherEdges(d_edges, d_edgeBlockCounts, minimumLength=minLength, maximumLength=maxLength)
+
+    def autoDetectThreshold(self, noiseLevels, multiplier: float = 1.0):
+        """The first histogram bin of the median-filtered power that is lower than both neighbours (:891-919).
+        self.counts (int64) and self.edges (float64) stay on the device; noiseLevels may be host or device."""
+        nl = noiseLevels.get() if isinstance(noiseLevels, DeviceArray) else np.asarray(noiseLevels)
+        edges = np.asarray(nl, dtype=np.float64).ravel()
+        if edges.size < 2:
+            raise ValueError("noiseLevels must hold at least two bin edges.")
+        if np.any(edges[:-1] > edges[1:]):
+            raise ValueError("`bins` must increase monotonically, when an array")
+        _lib.require_device()
+        d_x = self.d_medfiltered
+        self.edges = asarray(edges)
+        self.counts = empty(edges.size - 1, np.int64)
+        _lib.check(_lib.load().caf_histogram(_p(d_x), d_x.size, _is_f64(d_x), _p(self.edges), edges.size, _p(self.counts),
+                                             None), "caf_histogram")
+        counts = self.counts.get()
+
+        # We iterate from 1, because the 0 index shouldn't be compared to the end
+        for i in range(1, counts.size - 1):
+            if counts[i] < counts[i - 1] and counts[i] < counts[i + 1]:
+                detectedThreshold = nl[i]
+                return detectedThreshold * multiplier
+
+        return None  # Otherwise return None for failure
+
+    def detectSingleEmitter(self, ratio: float):
+        """Two-cluster k-means of the median-filtered power on the host (:921-943)."""
+        import scipy.cluster.vq as spc
+
+        x = self.d_medfiltered.get()
+        bigClusterSeed = np.max(x)
+        smallClusterSeed = x[x < (bigClusterSeed / ratio)][0]
+        codebook, distortion = spc.kmeans(x, np.array([smallClusterSeed, bigClusterSeed]))
+        self.codebook = np.sort(codebook)
+        self.threshold = np.mean(codebook)
+        # Codify the samples
+        codes, dists = spc.vq(x, self.codebook)
+        # Match to the big cluster
+        signalIndices = np.argwhere(codes == 1).reshape(-1)
+        return _split_indices(signalIndices)
+
+    def detectRegularSections(self, sectionSizeRange):
+        """Period search (:945-1008): the column means of the (rows, partitionSize) reshape on the device (float64
+        accumulation, returned in the array's dtype as cp.mean does), the k-means on the host; two lines printed per
+        partition."""
+        import scipy.cluster.vq as spc
+
+        _lib.require_device()
+        d_x = self.d_medfiltered
+        is_f64 = _is_f64(d_x)
+        sectionSizeRange = np.asarray(sectionSizeRange)
+        metric = np.zeros((sectionSizeRange.size, 2))
+        codebooks = np.zeros((sectionSizeRange.size, 2))
+        d_means = empty(int(np.max(sectionSizeRange)) if sectionSizeRange.size else 0, np.float64)
+        for i, partitionSize in enumerate(sectionSizeRange):
+            P = int(partitionSize)
+            rows = d_x.size // P
+            if rows == 0:
+                raise ValueError("cannot reshape array of size 0 into shape (%d)" % P)
+            _lib.check(_lib.load().caf_column_means(_p(d_x), rows, P, is_f64, 1, _p(d_means), None), "caf_column_means")
+            x = d_means.get()[:P].astype(d_x.dtype)
+
+            ratio = 1.5
+            bigClusterSeed = np.max(x)
+            try:
+                smallClusterSeed = x[x < (bigClusterSeed / ratio)][0]
+            except IndexError:
+                smallClusterSeed = np.min(x)
+            codebook, distortion = spc.kmeans(x, np.array([smallClusterSeed, bigClusterSeed]))
+            codebook = np.sort(codebook)
+            codebooks[i, :] = codebook
+
+            # Codify the samples
+            codes, dists = spc.vq(x, codebook)
+
+            print("partitionSize = %d, codebook clustering = %f, distortion = %f"
+                  % (partitionSize, np.diff(codebook)[0], distortion))
+            print("num0s = %d, num1s = %d" % (np.argwhere(codes == 0).size, np.argwhere(codes == 1).size))
+            metric[i, 0] = np.diff(codebook)[0]
+            metric[i, 1] = distortion
+
+        return metric, codebooks
+
+
+def energyDetection(ampSq, medfiltlen, snrReqLinear=4.0, noiseIndices=None, splitSignalIndices=True):
+    """ref: filterRoutines.py:1038-1088: the median filter on the device, the rest on the host; returns
+    (noiseIndices, meanNoise, reqPower, medfiltered (host), signalIndices)."""
+    if noiseIndices is None:
+        noiseIndices = np.arange(100000)
+        print("Noise indices defaulting to [%d, %d]" % (noiseIndices[0], noiseIndices[-1]))
+
+    d_ampSq = ampSq if isinstance(ampSq, DeviceArray) else asarray(np.asarray(ampSq))
+    medfiltered = medfilt(d_ampSq, medfiltlen).get()
+
+    # Detect the energy requirements
+    sampleNoise = medfiltered[noiseIndices]
+    meanNoise = np.mean(sampleNoise)
+    reqPower = meanNoise * snrReqLinear
+    signalIndices = np.argwhere(medfiltered > reqPower).flatten()
+    if splitSignalIndices:
+        signalIndices = _split_indices(signalIndices)
+
+    return noiseIndices, meanNoise, reqPower, medfiltered, signalIndices
+
+
 __all__ = ["CupyKernelFilter", "cupyMultiMovingAverage", "cupyMovingAverage", "cupyComplexMovingSum", "DeviceArray", "wola",
-           "Channeliser"]
+           "Channeliser", "medfilt", "cupyThresholdEdges", "cupyGatherEdges", "BurstDetector", "energyDetection"]
