@@ -459,6 +459,71 @@ CAF_EXPORT int32_t caf_sum_groups_qf2(const float* d_planes, int32_t num_groups,
                                       const float* d_phase, const double* d_row_norm, double ynormsq, double* d_out,
                                       void* stream);
 
+/* ---- PSK demodulation of bursts (demodulationRoutines.py:44-590, 626-1206; custom_kernels/demodulation.cu, eyeOpeningKernel.cu) --
+ * One row = one burst, zero-padded to the matrix width.  Sums are float32 in a fixed order that depends on the row alone. */
+#define CAF_DEMOD_LOCK_EIG 0       /* leading eigenvector of the 2x2 moment matrix of x^(m/2) (lockPhase)           */
+#define CAF_DEMOD_LOCK_POWERSUM 1  /* arg(sum x^m) / m (demod_qpsk, demod_b_or_q_psk)                                  */
+#define CAF_DEMOD_LOCK_NONE 2      /* no rotation at all: the row is mapped as it is (mapSyms alone)                   */
+#define CAF_DEMOD_MAP_CLASS 0      /* SimpleDemodulatorBPSK / QPSK / 8PSK.mapSyms (comparisons with 0; QPSK at +pi/4)  */
+#define CAF_DEMOD_MAP_GENERIC 1    /* SimpleDemodulatorPSK.mapSyms: arg max of the dot product with pskdicts[m]        */
+#define CAF_DEMOD_MAP_SIGNBITS 2   /* demod_qpsk / demod_b_or_q_psk: anticlockwise 0..3 from the sign bits             */
+#define CAF_DEMOD_MAP_GRAYBATCH 3  /* lockPhase_mapSyms_singleBlkKernel_qpsk: ((re >= +0) << 1) | (im >= +0)           */
+typedef struct caf_demod_desc {
+    const float* d_x;        /* (rows, xlength) complex64                                                             */
+    int64_t rows, xlength;
+    int32_t osr;             /* samples per symbol, 1..32; a row has xlength / osr symbols                            */
+    int32_t m;               /* 2, 4 or 8 for every row, unless d_m is given                                          */
+    const uint8_t* d_m;      /* NULL or rows orders; a row whose order is not 2 / 4 / 8 is left untouched             */
+    const int32_t* d_lengths;/* NULL or the valid samples of each row (the rest of the row is padding)                */
+    const float* d_abs;      /* NULL or |x| (rows, xlength); when NULL |x| is formed in the kernel                    */
+    int32_t lock, map;       /* CAF_DEMOD_LOCK_*, CAF_DEMOD_MAP_*                                                     */
+    uint8_t* d_syms;         /* (rows, xlength / osr)                                                                 */
+    int32_t* d_eo_index;     /* optional outputs from here on: rows                                                   */
+    float* d_eo_metric;      /* (rows, osr): the SUM of |x| of every phase                                            */
+    float* d_angle;          /* rows: the eigenvector's angle, or arg(sum x^m)                                        */
+    float* d_svd;            /* rows: lambda2 / lambda1 (eigen form)                                                  */
+    float* d_moments;        /* (rows, 3): S00, S01, S11 (eigen form) or Re, Im of the power sum and 0                */
+    float* d_reimc;          /* (rows, xlength / osr) complex64: the rotated symbols                                  */
+    float* d_xeo;            /* (rows, xeo_pitch) complex64: the winning phase, copied                                */
+    int64_t xeo_pitch;
+    int32_t eye_only;        /* (set by caf_eye_opening_batch)                                                        */
+    int32_t num_preambles;   /* 0: no preamble stage                                                                  */
+    const uint8_t* d_preambles;          /* the preambles, concatenated (preamble_total bytes)                        */
+    const int32_t* d_preamble_lengths;   /* num_preambles lengths                                                     */
+    int32_t preamble_total, max_preamble_length;
+    int32_t search_start, search_end;
+    uint32_t* d_best;        /* (rows, 4): preamble, sample (search_start + index), rotation, matches                 */
+    uint8_t* d_payload;      /* (rows, out_length): gray[(sym + rotation) mod m] from sample + preamble length        */
+    uint32_t* d_count;       /* rows: symbols in the row after the preamble (NULL: not wanted)                        */
+    int64_t out_length;
+    float scaling;           /* > 0: max(eo_metric) of the 8PSK threshold (mapSyms alone); 0: this row's own eye-opening mean */
+    int32_t reserved;
+} caf_demod_desc;
+/* eye opening -> phase lock -> symbol map, and with preambles compare -> arg max -> cut / rotate / gray, in ONE launch.
+ * 8PSK rows skip the preamble stage (no gray map is defined for them).  (ABI 1.10, detected by symbol) */
+CAF_EXPORT int32_t caf_psk_demod_rows(const caf_demod_desc* desc, void* stream);
+/* getEyeOpening_batch (eyeOpeningKernel.cu:5-83): d_abs may be NULL; d_eo_index / d_eo_metric (rows, osr sums) optional */
+CAF_EXPORT int32_t caf_eye_opening_batch(const float* d_abs, const float* d_x, int64_t rows, int64_t xlength, int32_t osr,
+                                         float* d_xeo, int64_t xeo_pitch, int32_t* d_eo_index, float* d_eo_metric, void* stream);
+/* compareIntegerPreambles (demodulation.cu:547-661): d_matches[row][preamble][search][r] (uint32) = the number of j with
+ * (preamble[j] - syms[search_start + search + j]) mod m == r; rows whose d_psk_m (optional) differs from m are not written */
+CAF_EXPORT int32_t caf_compare_int_preambles(const uint8_t* d_syms, int64_t rows, int64_t syms_length, int32_t search_start,
+                                             int32_t search_end, const uint8_t* d_preambles, int32_t preamble_total,
+                                             const int32_t* d_preamble_lengths, int32_t num_preambles,
+                                             int32_t max_preamble_length, int32_t m, const uint8_t* d_psk_m,
+                                             uint32_t* d_matches, void* stream);
+/* cutAndRotatePSKSymbolsFromPossiblePreambles_Gray (demodulation.cu:41-115): d_index (rows, 3) = key, sample, rotation */
+CAF_EXPORT int32_t caf_cut_rotate_gray(const uint32_t* d_index, int64_t rows, const uint8_t* d_syms, int64_t syms_length,
+                                       const uint32_t* d_key_lengths, int32_t num_keys, const uint32_t* d_sample_stops,
+                                       int32_t m, int64_t out_length, uint8_t* d_out, uint32_t* d_count,
+                                       const uint8_t* d_psk_m, void* stream);
+/* the amble search and bit unpacking of lockPhase_mapSyms_singleBlkKernel_qpsk (demodulation.cu:985-1088) on the uint8
+ * gray symbols of caf_psk_demod_rows(CAF_DEMOD_MAP_GRAYBATCH); d_amble is int32 as in the reference */
+CAF_EXPORT int32_t caf_amble_search_bits(const uint8_t* d_syms, int64_t rows, int64_t syms_length, const int32_t* d_amble,
+                                         int32_t amble_length, int32_t search_start, int32_t search_length,
+                                         uint32_t* d_syms_out, int32_t* d_best_matches, int32_t* d_best_rotations,
+                                         int32_t* d_best_idx, uint8_t* d_bits, int64_t bits_length, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -103,6 +103,52 @@ class CafZoomOutputs(ct.Structure):
     ]
 
 
+class CafDemodDesc(ct.Structure):
+    _fields_ = [
+        ("d_x", ct.c_void_p),
+        ("rows", ct.c_int64),
+        ("xlength", ct.c_int64),
+        ("osr", ct.c_int32),
+        ("m", ct.c_int32),
+        ("d_m", ct.c_void_p),
+        ("d_lengths", ct.c_void_p),
+        ("d_abs", ct.c_void_p),
+        ("lock", ct.c_int32),
+        ("map", ct.c_int32),
+        ("d_syms", ct.c_void_p),
+        ("d_eo_index", ct.c_void_p),
+        ("d_eo_metric", ct.c_void_p),
+        ("d_angle", ct.c_void_p),
+        ("d_svd", ct.c_void_p),
+        ("d_moments", ct.c_void_p),
+        ("d_reimc", ct.c_void_p),
+        ("d_xeo", ct.c_void_p),
+        ("xeo_pitch", ct.c_int64),
+        ("eye_only", ct.c_int32),
+        ("num_preambles", ct.c_int32),
+        ("d_preambles", ct.c_void_p),
+        ("d_preamble_lengths", ct.c_void_p),
+        ("preamble_total", ct.c_int32),
+        ("max_preamble_length", ct.c_int32),
+        ("search_start", ct.c_int32),
+        ("search_end", ct.c_int32),
+        ("d_best", ct.c_void_p),
+        ("d_payload", ct.c_void_p),
+        ("d_count", ct.c_void_p),
+        ("out_length", ct.c_int64),
+        ("scaling", ct.c_float),
+        ("reserved", ct.c_int32),
+    ]
+
+
+CAF_DEMOD_LOCK_EIG = 0
+CAF_DEMOD_LOCK_POWERSUM = 1
+CAF_DEMOD_LOCK_NONE = 2
+CAF_DEMOD_MAP_CLASS = 0
+CAF_DEMOD_MAP_GENERIC = 1
+CAF_DEMOD_MAP_SIGNBITS = 2
+CAF_DEMOD_MAP_GRAYBATCH = 3
+
 _P = ct.c_void_p
 _I32 = ct.c_int32
 _I64 = ct.c_int64
@@ -181,6 +227,11 @@ _SIGNATURES = {
     "caf_zoom_num_bins": [ct.c_double, ct.c_double, ct.POINTER(_I32)],
     "caf_zoom_czt": [_P, _I32, _P, _I64, _P, _P, _I64, _I64, _I32, ct.c_float, ct.c_double, ct.c_double,
                      ct.POINTER(CafZoomOutputs), _P],
+    "caf_psk_demod_rows": [ct.POINTER(CafDemodDesc), _P],
+    "caf_eye_opening_batch": [_P, _P, _I64, _I64, _I32, _P, _I64, _P, _P, _P],
+    "caf_compare_int_preambles": [_P, _I64, _I64, _I32, _I32, _P, _I32, _P, _I32, _I32, _I32, _P, _P, _P],
+    "caf_cut_rotate_gray": [_P, _I64, _P, _I64, _P, _I32, _P, _I32, _I64, _P, _P, _P, _P],
+    "caf_amble_search_bits": [_P, _I64, _I64, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I64, _P],
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
