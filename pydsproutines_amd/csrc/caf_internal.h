@@ -143,13 +143,14 @@ void launch_find_local_maxima(const float* x, int64_t n, float min_height, int32
                               int32_t* idx, int32_t* count, hipStream_t st);
 void launch_gather_b32(const void* x, int64_t xlen, const int32_t* idx, int64_t n, void* out, hipStream_t st);
 void launch_gather_f32_f64(const float* x, int64_t xlen, const int32_t* idx, int64_t n, double* out, hipStream_t st);
-void launch_fir(const float2* x, int64_t n, const float* taps, int32_t ntaps, const float2* delay, int32_t dlen,
+// (these three return the name of the kernel they launched, for the CAF_FIR_DEBUG report)
+const char* launch_fir(const float2* x, int64_t n, const float* taps, int32_t ntaps, const float2* delay, int32_t dlen,
                 int32_t dsr, int32_t phase, float2* out, int64_t nout, hipStream_t st);
 bool fir_decim_ok(int32_t ntaps, int32_t dsr);
 bool fir_poly_fits(int32_t ntaps, int32_t dsr);  // ... and the register-tiled polyphase kernel takes it (small decimation factors)
-void launch_iq16_fir(const int16_t* iq, int64_t n, float scale, const float* taps, int32_t ntaps, const int16_t* delay,
+const char* launch_iq16_fir(const int16_t* iq, int64_t n, float scale, const float* taps, int32_t ntaps, const int16_t* delay,
                      int32_t dlen, int32_t dsr, int32_t phase, float2* out, int64_t nout, hipStream_t st);
-void launch_upfirdn(const float2* x, int64_t rows, int64_t n, const float* taps, int32_t ntaps, int32_t up, int32_t down,
+const char* launch_upfirdn(const float2* x, int64_t rows, int64_t n, const float* taps, int32_t ntaps, int32_t up, int32_t down,
                     int64_t nout, float2* out, float* out_abs, hipStream_t st);
 void launch_rows_mul_vec(const float2* x, int64_t in_pitch, int64_t in_off, const float2* v, int64_t len, float2* y,
                          int64_t out_pitch, int64_t pad_to, int64_t rows, float scale, hipStream_t st);

@@ -115,13 +115,34 @@ bool fir_use_overlap_save(int32_t ntaps, int32_t dsr, int32_t direct_limit) {
     return ntaps > direct_limit || (int64_t)ntaps > (int64_t)min_taps * dsr;
 }
 
+// CAF_FIR_DEBUG=1 (read per call, like CAF_WOLA_DEBUG): one stderr line per caf_fir_lfilter / caf_iq16_fir_decimate /
+// caf_upfirdn call naming the kernel that ran (and the transform length B of the overlap-save forms), so that a test can
+// assert the path it means to test
+bool fir_debug() {
+    const char* e = std::getenv("CAF_FIR_DEBUG");
+    return e && e[0] == '1';
+}
+void fir_report(const char* call, bool is_iq16, const char* kernel, int64_t B, int32_t ntaps, int32_t up, int32_t dsr,
+                int32_t phase, int64_t rows, int64_t n, int64_t nout) {
+    char blk[32] = "";
+    if (B) std::snprintf(blk, sizeof(blk), " B=%lld", (long long)B);
+    std::fprintf(stderr, "[caf fir] call=%s path=%s%s%s ntaps=%d up=%d down=%d phase=%d rows=%lld n=%lld out=%lld\n", call,
+                 is_iq16 ? "iq16_" : "", kernel, blk, (int)ntaps, (int)up, (int)dsr, (int)phase, (long long)rows, (long long)n,
+                 (long long)nout);
+}
+
 // is_iq16: x / delay are interleaved int16 IQ pairs scaled by `scale`, else complex64
 int fir_overlap_save(const void* x, int64_t n, bool is_iq16, float scale, const float* taps, int32_t ntaps, const void* delay,
                      int32_t dlen, int32_t dsr, int32_t phase, float2* out, int64_t nout, hipStream_t st) {
-    if (nout <= 0) return CAF_OK;
+    const char* call = is_iq16 ? "iq16_fir_decimate" : "fir_lfilter";
+    if (nout <= 0) {
+        if (fir_debug()) fir_report(call, is_iq16, "none", 0, ntaps, 1, dsr, phase, 1, n, nout);
+        return CAF_OK;
+    }
     Scratch sc;
     int rc;
     if (const int fb = fir_os_fused_block(ntaps)) {
+        if (fir_debug()) fir_report(call, is_iq16, "os_fused", fb, ntaps, 1, dsr, phase, 1, n, nout);
         float2* ht = nullptr;
         if ((rc = sc.get(&ht, fb))) return rc;
         rc = is_iq16 ? launch_iq16_fir_os_fused((const int16_t*)x, n, scale, taps, ntaps, (const int16_t*)delay, dlen, dsr, phase,
@@ -134,6 +155,7 @@ int fir_overlap_save(const void* x, int64_t n, bool is_iq16, float scale, const 
         int64_t B = 65536;
         while (B < 4 * (int64_t)ntaps) B <<= 1;
         CAF_REQUIRE(B <= ((int64_t)1 << 26), "overlap-save FIR: more than 2^24 taps");
+        if (fir_debug()) fir_report(call, is_iq16, "os_rocfft", B, ntaps, 1, dsr, phase, 1, n, nout);
         const int64_t L = B - ntaps + 1;
         const int64_t last = phase + (nout - 1) * (int64_t)dsr;
         const int64_t nblk = last / L + 1;
@@ -566,8 +588,9 @@ int32_t caf_fir_lfilter(const float* d_x, int64_t n, const float* d_taps, int32_
     if (fir_use_overlap_save(num_taps, dsr, 4096))  // long tap sets: frequency-domain blocks (any length)
         return fir_overlap_save(d_x, n, false, 1.0f, d_taps, num_taps, d_delay, delay_len, dsr, ds_phase, (float2*)d_out, out_len,
                                 (hipStream_t)stream);
-    launch_fir((const float2*)d_x, n, d_taps, num_taps, (const float2*)d_delay, delay_len, dsr, ds_phase, (float2*)d_out,
-               out_len, (hipStream_t)stream);
+    const char* kernel = launch_fir((const float2*)d_x, n, d_taps, num_taps, (const float2*)d_delay, delay_len, dsr, ds_phase,
+                                    (float2*)d_out, out_len, (hipStream_t)stream);
+    if (fir_debug()) fir_report("fir_lfilter", false, kernel, 0, num_taps, 1, dsr, ds_phase, 1, n, out_len);
     CAF_HIP_TRY(hipGetLastError());
     return CAF_OK;
 }
@@ -625,8 +648,9 @@ int32_t caf_iq16_fir_decimate(const int16_t* d_iq, int64_t num_samples, float sc
     if (!fir_decim_ok(num_taps, dsr) || fir_use_overlap_save(num_taps, dsr, 2048))
         return fir_overlap_save(d_iq, num_samples, true, scale, d_taps, num_taps, d_delay, delay_len, dsr, ds_phase,
                                 (float2*)d_out, out_len, (hipStream_t)stream);
-    launch_iq16_fir(d_iq, num_samples, scale, d_taps, num_taps, d_delay, delay_len, dsr, ds_phase, (float2*)d_out, out_len,
-                    (hipStream_t)stream);
+    const char* kernel = launch_iq16_fir(d_iq, num_samples, scale, d_taps, num_taps, d_delay, delay_len, dsr, ds_phase,
+                                         (float2*)d_out, out_len, (hipStream_t)stream);
+    if (fir_debug()) fir_report("iq16_fir_decimate", true, kernel, 0, num_taps, 1, dsr, ds_phase, 1, num_samples, out_len);
     CAF_HIP_TRY(hipGetLastError());
     return CAF_OK;
 }
@@ -642,9 +666,11 @@ int32_t caf_upfirdn(const float* d_x, int64_t rows, int64_t n, const float* d_ta
     // taps, up = down = 1: 0.38 ms through the polyphase kernel (0.09 of the HBM bound), the same job as caf_fir_lfilter otherwise
     if (up == 1 && d_out && !d_out_abs && fir_os_fused_block(num_taps) && fir_use_overlap_save(num_taps, down, 1 << 30)) {
         hipStream_t st = (hipStream_t)stream;
+        const int fb = fir_os_fused_block(num_taps);  // (launch_fir_os_fused picks its kernel by the same function)
+        if (fir_debug()) fir_report("upfirdn", false, "os_fused", fb, num_taps, 1, down, 0, rows, n, out_len);
         Scratch sc;
         float2* ht = nullptr;
-        int rc = sc.get(&ht, fir_os_fused_block(num_taps));
+        int rc = sc.get(&ht, fb);
         if (rc) return rc;
         rc = launch_fir_os_fused((const float2*)d_x, n, d_taps, num_taps, nullptr, 0, down, 0, (float2*)d_out, out_len, ht, st, rows, n,
                                  out_len);
@@ -653,8 +679,9 @@ int32_t caf_upfirdn(const float* d_x, int64_t rows, int64_t n, const float* d_ta
         CAF_HIP_TRY(hipGetLastError());
         return CAF_OK;
     }
-    launch_upfirdn((const float2*)d_x, rows, n, d_taps, num_taps, up, down, out_len, (float2*)d_out, d_out_abs,
-                   (hipStream_t)stream);
+    const char* kernel = launch_upfirdn((const float2*)d_x, rows, n, d_taps, num_taps, up, down, out_len, (float2*)d_out, d_out_abs,
+                                        (hipStream_t)stream);
+    if (fir_debug()) fir_report("upfirdn", false, kernel, 0, num_taps, up, down, 0, rows, n, out_len);
     CAF_HIP_TRY(hipGetLastError());
     return CAF_OK;
 }

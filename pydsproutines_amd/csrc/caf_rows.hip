@@ -1755,10 +1755,11 @@ bool fir_poly_fits(int32_t ntaps, int32_t dsr) {
     return dsr >= 1 && smp <= 64 * 1024 && (size_t)ncols * dsr <= (size_t)FIRP_MAXSPAN + 4 * FIRP_R * dsr;
 }
 
+// (the launchers of the FIR family return the name of the kernel they chose: the CAF_FIR_DEBUG report of caf_ops.hip)
 template <typename TIn>
-static void launch_fir_decim(const TIn* x, int64_t n, float scale, const float* taps, int32_t ntaps, const TIn* delay,
-                             int32_t dlen, int32_t dsr, int32_t phase, float2* out, int64_t nout, hipStream_t st) {
-    if (nout <= 0) return;
+static const char* launch_fir_decim(const TIn* x, int64_t n, float scale, const float* taps, int32_t ntaps, const TIn* delay,
+                                    int32_t dlen, int32_t dsr, int32_t phase, float2* out, int64_t nout, hipStream_t st) {
+    if (nout <= 0) return "none";
     {   // register-tiled polyphase form when its tile window fits the LDS (small decimation factors)
         int ncols = 0;
         const size_t smp = fir_poly_lds(ntaps, dsr, &ncols);
@@ -1798,7 +1799,7 @@ static void launch_fir_decim(const TIn* x, int64_t n, float scale, const float* 
     } while (0)
             if (ept <= 8) CAF_FIR_POLY(8); else if (ept <= 16) CAF_FIR_POLY(16); else if (ept <= 24) CAF_FIR_POLY(24); else CAF_FIR_POLY(32);
 #undef CAF_FIR_POLY
-            return;
+            return ept <= 8 ? "fir_poly E=8" : (ept <= 16 ? "fir_poly E=16" : (ept <= 24 ? "fir_poly E=24" : "fir_poly E=32"));
         }
     }
     // kept outputs per thread: the window (tile - 1) * dsr + ntaps stays below ~6200 samples (LDS < 64 KB with the taps)
@@ -1809,33 +1810,33 @@ static void launch_fir_decim(const TIn* x, int64_t n, float scale, const float* 
     if (nout > 0)
         hipLaunchKernelGGL(k_fir_decim<TIn>, dim3(cdiv(nout, tile)), dim3(256), sm, st, x, n, scale, taps, ntaps, delay,
                            dlen, dsr, phase, per, out, nout);
+    return "fir_decim";
 }
 
-void launch_fir(const float2* x, int64_t n, const float* taps, int32_t ntaps, const float2* delay, int32_t dlen,
+const char* launch_fir(const float2* x, int64_t n, const float* taps, int32_t ntaps, const float2* delay, int32_t dlen,
                 int32_t dsr, int32_t phase, float2* out, int64_t nout, hipStream_t st) {
     if (dsr == 1 && phase == 0 && nout >= n && ntaps <= 2048) {  // undecimated: the register-tiled kernel (LDS < 64 KB)
         const int ntp = (ntaps + FIRF_R - 1) / FIRF_R * FIRF_R;
         const int pitch = (FIRF_TILE + ntp) / FIRF_R + 1;
         const size_t smf = (size_t)ntp * sizeof(float) + (size_t)FIRF_R * pitch * sizeof(float2);
         hipLaunchKernelGGL(k_fir_fast, dim3(cdiv(n, FIRF_TILE)), dim3(256), smf, st, x, n, taps, ntaps, delay, dlen, out);
-        return;
+        return "fir_fast";
     }
-    if (fir_decim_ok(ntaps, dsr)) {  // decimating: only the kept outputs are computed
-        launch_fir_decim(x, n, 1.0f, taps, ntaps, delay, dlen, dsr, phase, out, nout, st);
-        return;
-    }
+    if (fir_decim_ok(ntaps, dsr))  // decimating: only the kept outputs are computed
+        return launch_fir_decim(x, n, 1.0f, taps, ntaps, delay, dlen, dsr, phase, out, nout, st);
     const size_t sm = (size_t)((ntaps + 1) & ~1) * sizeof(float) + (size_t)(FIR_TILE + ntaps) * sizeof(float2);
     hipLaunchKernelGGL(k_fir, dim3(cdiv(n, FIR_TILE)), dim3(256), sm, st, x, n, taps, ntaps, delay, dlen, dsr, phase, out,
                        nout);
+    return "fir";
 }
 
-void launch_iq16_fir(const int16_t* iq, int64_t n, float scale, const float* taps, int32_t ntaps, const int16_t* delay,
+const char* launch_iq16_fir(const int16_t* iq, int64_t n, float scale, const float* taps, int32_t ntaps, const int16_t* delay,
                      int32_t dlen, int32_t dsr, int32_t phase, float2* out, int64_t nout, hipStream_t st) {
-    launch_fir_decim(reinterpret_cast<const short2*>(iq), n, scale, taps, ntaps, reinterpret_cast<const short2*>(delay),
-                     dlen, dsr, phase, out, nout, st);
+    return launch_fir_decim(reinterpret_cast<const short2*>(iq), n, scale, taps, ntaps, reinterpret_cast<const short2*>(delay),
+                            dlen, dsr, phase, out, nout, st);
 }
 
-void launch_upfirdn(const float2* x, int64_t rows, int64_t n, const float* taps, int32_t ntaps, int32_t up, int32_t down,
+const char* launch_upfirdn(const float2* x, int64_t rows, int64_t n, const float* taps, int32_t ntaps, int32_t up, int32_t down,
                     int64_t nout, float2* out, float* out_abs, hipStream_t st) {
     if (up <= UFP_MAXUP) {
         // polyphase form: 256 groups of `up` outputs per workgroup; taps of a phase split by residue of the tap number
@@ -1850,19 +1851,21 @@ void launch_upfirdn(const float2* x, int64_t rows, int64_t n, const float* taps,
             const int64_t ngroups = (nout + up - 1) / up;
             hipLaunchKernelGGL(k_upfirdn_poly, dim3(cdiv(ngroups, 256), (unsigned)rows), dim3(256), lds, st, x, n, taps, ntaps, up,
                                down, nout, ntip, (int32_t)pitch, (int32_t)span, out, out_abs);
-            return;
+            return "upfirdn_poly";
         }
     }
     // input window of 256 consecutive outputs; staged in LDS when it fits beside the taps (<= 64 KB)
     const int64_t span = (255 * (int64_t)down + ntaps - 1) / up + 3;
     const size_t tap_bytes = (size_t)((ntaps + 1) & ~1) * sizeof(float);
-    if (tap_bytes + (size_t)span * sizeof(float2) <= 64 * 1024)
+    if (tap_bytes + (size_t)span * sizeof(float2) <= 64 * 1024) {
         hipLaunchKernelGGL(k_upfirdn<true>, dim3(cdiv(nout, 256), (unsigned)rows), dim3(256),
                            tap_bytes + (size_t)span * sizeof(float2), st, x, n, taps, ntaps, up, down, nout, (int32_t)span, out,
                            out_abs);
-    else
-        hipLaunchKernelGGL(k_upfirdn<false>, dim3(cdiv(nout, 256), (unsigned)rows), dim3(256), tap_bytes, st, x, n, taps,
-                           ntaps, up, down, nout, 0, out, out_abs);
+        return "upfirdn_lds";
+    }
+    hipLaunchKernelGGL(k_upfirdn<false>, dim3(cdiv(nout, 256), (unsigned)rows), dim3(256), tap_bytes, st, x, n, taps,
+                       ntaps, up, down, nout, 0, out, out_abs);
+    return "upfirdn_global";
 }
 
 void launch_rows_mul_vec(const float2* x, int64_t in_pitch, int64_t in_off, const float2* v, int64_t len, float2* y,

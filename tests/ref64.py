@@ -166,3 +166,293 @@ def complex_ratio(got, ref, bound, axis_s):
     r = np.abs(got - ref) / np.reshape(bound, shape)
     r = r[~nan_r]
     return float(r.max()) if r.size else 0.0
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# The front end: FIR (lfilter), upfirdn and the WOLA channeliser in float64, the units of their error bounds, float32
+# stand-ins of the two transform-based algorithms (which calibrate C_FIR_OS and C_WOLA) and the records and
+# tap sets that tests/test_ref64.py (CPU) and tests/test_gpu_f64_frontend.py (GPU) share.
+
+C_FIR_OS = 32.0  # overlap-save FIR: smallest power of two >= 4x the stand-in's worst ratio over seeds 0 .. 9 (6.32, test_ref64.py)
+C_WOLA = 4.0     # WOLA: the same rule (stand-in's worst ratio 0.866)
+C_FIR_OS_IMPULSE = 1.0  # overlap-save FIR on an impulse, unit without the 1 / sqrt(B) spreading: the same rule (worst 0.177)
+
+
+def _as64(a):
+    a = np.asarray(a)
+    return a.astype(np.complex128 if np.iscomplexobj(a) else np.float64)
+
+
+def _conv_full(x, h):
+    """Full linear convolution in float64 / complex128: np.convolve for small jobs, one FFT otherwise.  Behind the FFT, an
+    output whose whole tap window holds only zero samples is set to exactly zero (as the direct sum gives)."""
+    x, h = _as64(x), _as64(h)
+    if x.size * h.size <= (1 << 27):
+        return np.convolve(x, h)
+    n = x.size + h.size - 1
+    L = sfft.next_fast_len(n)
+    if np.iscomplexobj(x) or np.iscomplexobj(h):
+        y = sfft.ifft(sfft.fft(x, L, workers=_WORKERS) * sfft.fft(h, L, workers=_WORKERS), workers=_WORKERS)[:n]
+    else:
+        y = sfft.irfft(sfft.rfft(x, L, workers=_WORKERS) * sfft.rfft(h, L, workers=_WORKERS), L, workers=_WORKERS)[:n]
+    nz = np.concatenate(([0], np.cumsum(x != 0)))
+    i = np.arange(n)
+    y[nz[np.minimum(i + 1, x.size)] - nz[np.clip(i - h.size + 1, 0, x.size)] == 0] = 0
+    return y
+
+
+def _with_history(x, ntaps, delay):
+    """[the ntaps - 1 samples in front of x : x]: the tail of `delay`, zeros where it is shorter."""
+    x = _as64(x)
+    hist = np.zeros(ntaps - 1, x.dtype)
+    if delay is not None and ntaps > 1:
+        d = _as64(delay)[-(ntaps - 1):]
+        if d.size:
+            hist[-d.size:] = d
+    return np.concatenate((hist, x))
+
+
+def fir64(x, taps, delay=None, dsr=1, phase=0):
+    """lfilter(taps, 1, [delay; x]) restricted to x, kept outputs [phase::dsr]; float64 / complex128 throughout."""
+    taps = _as64(taps)
+    xe = _with_history(x, taps.size, delay)
+    return _conv_full(xe, taps)[taps.size - 1 : xe.size][phase::dsr]
+
+
+def upfirdn64(x, taps, up, down):
+    """scipy.signal.upfirdn(taps, x, up, down) per row of a 1-D or 2-D x; float64 / complex128 throughout."""
+    x = _as64(x)
+    if x.ndim == 2:
+        return np.stack([upfirdn64(r, taps, up, down) for r in x])
+    xu = np.zeros((x.size - 1) * up + 1, x.dtype)
+    xu[::up] = x
+    return _conv_full(xu, taps)[::down]
+
+
+def direct_unit(x, taps, delay=None, dsr=1, phase=0, up=None, down=None):
+    """2^-24 * A[n], A[n] = sum_k |h_k| |x_{n-k}| in float64: the same filter applied to the moduli.  A float32 sum of K
+    products, in any order, with or without FMA, is within (K + 2) * this of the exact sum."""
+    ax = np.abs(_as64(x))
+    at = np.abs(_as64(taps))
+    if up is not None:
+        return EPS32 * upfirdn64(ax, at, up, down)
+    return EPS32 * fir64(ax, at, None if delay is None else np.abs(_as64(delay)), dsr, phase)
+
+
+def fir_os_unit(x, taps, B, delay=None, dsr=1, phase=0, spread=True):
+    """2^-24 * log2(B) * ||h||_2 * sqrt(E_tr(n) / B) per kept output: E_tr(n) is the energy of every input sample, carried-in
+    history included, that can share a B-point block with output n, [n - B + 1, n + B) clipped (amp_bound's construction).
+
+    spread=False leaves the 1 / sqrt(B) out: 2^-24 * log2(B) * ||h||_2 * sqrt(E_tr(n)).  The division describes noise, whose
+    transform error arrives from B samples of the same size and adds like a random walk; the error of a block that holds ONE
+    sample of amplitude a is that of a's own B spectral lines, each a * |H| in size, and does not shrink with B.  This is
+    the unit of the impulse cases (E_tr = |a|^2 where the impulse can share a block with the output, 0 -- exact -- elsewhere)."""
+    taps = _as64(taps)
+    xe = _with_history(x, taps.size, delay)
+    off = taps.size - 1
+    p = _prefix(xe)
+    n = off + np.arange(np.asarray(x).size)[phase::dsr]
+    e_tr = p[np.clip(n + B, 0, xe.size)] - p[np.clip(n - B + 1, 0, xe.size)]
+    return EPS32 * np.log2(B) * np.sqrt(np.sum(taps ** 2)) * np.sqrt(np.maximum(e_tr, 0.0) / (B if spread else 1))
+
+
+def fir_os32(x, taps, B, delay=None):
+    """float32 stand-in of the overlap-save FIR: complex64 scipy.fft blocks of B points, L = B - K + 1 outputs per block."""
+    taps = np.asarray(taps, np.float32)
+    K = taps.size
+    L = B - K + 1
+    xe = _with_history(x, K, delay).astype(np.complex64)
+    n = np.asarray(x).size
+    H = sfft.fft(np.concatenate((taps, np.zeros(B - K, np.float32))).astype(np.complex64))
+    assert H.dtype == np.complex64
+    nblk = -(-n // L)
+    seg = np.zeros((nblk, B), np.complex64)
+    for b in range(nblk):
+        s = xe[b * L : b * L + B]
+        seg[b, : s.size] = s
+    y = sfft.ifft(sfft.fft(seg, axis=1, workers=_WORKERS) * H, axis=1, workers=_WORKERS)
+    assert y.dtype == np.complex64
+    return y[:, K - 1 :].reshape(-1)[:n]
+
+
+def _wola_poly(taps, x, dec, N, hist, dtype):
+    """v[r][a] = sum_b taps[b N + a] xe[r dec - b N - a] (rows, N), odd rows rotated by N/2 when N == 2 dec; summed in dtype."""
+    taps = np.asarray(taps).astype(np.zeros(0, dtype).real.dtype)
+    x = np.asarray(x).astype(dtype)
+    L = taps.size
+    P = L // N
+    h = np.zeros(0, dtype) if hist is None else np.asarray(hist).astype(dtype)
+    xe = np.concatenate((np.zeros(L, dtype), h, x))
+    off = L + h.size
+    rows = x.size // dec
+    if rows == 0:
+        return np.zeros((0, N), dtype)
+    # window of row r: xe[off + r dec - L + 1 .. off + r dec], newest sample last
+    win = np.lib.stride_tricks.sliding_window_view(xe[off - L + 1 :], L)[::dec][:rows]
+    # window element i meets tap L - 1 - i: both reversed, so that the (rows, P, N) split of the windows stays a view
+    v = np.einsum("rpn,pn->rn", win.reshape(rows, P, N), taps[::-1].reshape(P, N))[:, ::-1].copy()
+    if N == 2 * dec:
+        v[1::2] = np.roll(v[1::2], -N // 2, axis=1)
+    return v.astype(dtype, copy=False)
+
+
+def wola64(taps, x, dec, N, hist=None):
+    """float64 restatement: rows floor(len(x) / dec) at x[r dec], history in front, odd rows rotated by N/2 (N == 2 dec)."""
+    return sfft.ifft(_wola_poly(taps, x, dec, N, hist, np.complex128), axis=1, workers=_WORKERS) * N
+
+
+def wola_unit(taps, x, dec, N, hist=None):
+    """Per output row: 2^-24 * (log2(N) ||v||_2 + (P + 2) ||a||_2), v the float64 polyphase vector of the row and a the same
+    sums over the moduli."""
+    v = _wola_poly(taps, x, dec, N, hist, np.complex128)
+    a = _wola_poly(np.abs(np.asarray(taps, np.float64)), np.abs(_as64(x)), dec, N, None if hist is None else np.abs(_as64(hist)),
+                   np.float64)
+    P = np.asarray(taps).size // N
+    return EPS32 * (np.log2(N) * np.sqrt(np.sum(np.abs(v) ** 2, axis=1)) + (P + 2) * np.sqrt(np.sum(a ** 2, axis=1)))
+
+
+def wola32(taps, x, dec, N, hist=None):
+    """float32 stand-in of the channeliser: complex64 polyphase sums, then a complex64 ifft * N."""
+    v = _wola_poly(taps, x, dec, N, hist, np.complex64)
+    y = sfft.ifft(v, axis=1, workers=_WORKERS)
+    assert v.dtype == np.complex64 and y.dtype == np.complex64
+    return y * np.float32(N)
+
+
+def fir_direct32(x, taps, delay, idx):
+    """Sequential float32 direct form (tap 0 first, no FMA) at the output indices idx: the plainest kernel one could write."""
+    taps = np.asarray(taps, np.float32)
+    xe = _with_history(x, taps.size, delay).astype(np.complex64)
+    out = np.zeros(len(idx), np.complex64)
+    for j, i in enumerate(idx):
+        w = xe[i : i + taps.size][::-1]
+        re, im = np.float32(0), np.float32(0)
+        for k in range(taps.size):
+            re = np.float32(re + np.float32(taps[k] * w[k].real))
+            im = np.float32(im + np.float32(taps[k] * w[k].imag))
+        out[j] = re + 1j * im
+    return out
+
+
+def fe_noise(rng, n):
+    return ((rng.standard_normal(n) + 1j * rng.standard_normal(n)) / np.sqrt(2)).astype(np.complex64)
+
+
+def fe_record(rng, n, block, ntaps):
+    """Unit-power noise of n samples with, in random order and separated by noise, a stretch of 3000 samples 60 dB louder,
+    a stretch 40 dB quieter of 2 * block + 100 samples and a run of ntaps + 50 exact zeros."""
+    lens = [3000, 2 * block + 100, ntaps + 50]
+    spare = n - sum(lens)
+    assert spare >= 400, "record too short for its three stretches: %d" % n
+    x = fe_noise(rng, n)
+    gaps = rng.multinomial(spare - 400, [0.25] * 4) + 100  # noise in front, between and behind
+    at = gaps[0]
+    for k in rng.permutation(3):
+        if k == 0:
+            x[at : at + lens[0]] *= np.float32(1000.0)
+        elif k == 1:
+            x[at : at + lens[1]] *= np.float32(0.01)
+        else:
+            x[at : at + lens[2]] = 0
+        at += lens[k] + gaps[k + 1]
+    return x
+
+
+def fe_taps(rng, kind, K):
+    """float32 tap sets: 'firwin' (low-pass, 60-100 dB between centre and ends), 'gauss' (i.i.d., unit energy), 'ends' (Gaussian
+    with the first and the last tap the largest)."""
+    if kind == "firwin":
+        import scipy.signal as sps
+
+        return sps.firwin(K, 0.2).astype(np.float32)
+    t = rng.standard_normal(K) / np.sqrt(K)
+    if kind == "ends":
+        big = 2.0 * np.max(np.abs(t))
+        t[0], t[-1] = big, -1.25 * big
+    else:
+        assert kind == "gauss"
+    return t.astype(np.float32)
+
+
+FE_KINDS = ("firwin", "gauss", "ends")
+
+# overlap-save FIR cases (ntaps, transform length B the dispatch picks for it): either side of 256 / 1024 / 8192 taps, the
+# smallest overlap-save tap count at dsr 1, and the rocFFT rows
+FIR_OS_CASES = [(97, 1024), (256, 1024), (257, 4096), (1024, 4096), (1025, 16384), (8192, 16384), (8193, 65536), (65536, 262144)]
+
+
+def fir_os_case(seed, ntaps, B, kind):
+    """(x, taps) of an overlap-save case: a record of 5 blocks + the three stretches."""
+    rng = np.random.default_rng(1000 * seed + ntaps + FE_KINDS.index(kind))
+    n = 3000 + 2 * B + 100 + ntaps + 50 + 2 * B + int(rng.integers(400, 1400))
+    return fe_record(rng, n, B, ntaps), fe_taps(rng, kind, ntaps)
+
+
+def fir_os_impulse_case(seed, ntaps, B, kind):
+    """(n, taps, cuts, positions) of the impulse cases of an overlap-save shape: a record of 3 blocks' outputs + 5 samples that
+    the streaming callers cut into three chunks at `cuts`; impulse positions 0, either side of the block boundaries (L = B -
+    ntaps + 1 new outputs per block), either side of the chunk cuts, and in the last ntaps samples."""
+    rng = np.random.default_rng(1000 * seed + ntaps + 77 + FE_KINDS.index(kind))
+    L = B - ntaps + 1
+    n = 3 * L + 5
+    cuts = [0, L + 2, 2 * L + 3, n]  # (every chunk at least L >= ntaps - 1 samples: the streaming callers keep that many)
+    pos = [0, 1, L - 1, L, L + 1, 2 * L - 1, 2 * L, cuts[1] - 1, cuts[1], cuts[1] + 1, cuts[2] - 1, cuts[2], n - ntaps, n - ntaps // 2 - 1, n - 1]
+    return n, fe_taps(rng, kind, ntaps), cuts, sorted(set(p for p in pos if 0 <= p < n))
+
+
+def impulse(n, p, amp):
+    x = np.zeros(n, np.complex64)
+    x[p] = amp
+    return x
+
+
+def impulse_fir64(n, p, amp, taps, dsr=1, phase=0):
+    """lfilter of impulse(n, p, amp), exactly: amp * taps from output p on (every product is exact in float64), zeros elsewhere."""
+    taps = np.asarray(taps)
+    y = np.zeros(n + taps.size, np.complex128)
+    y[p : p + taps.size] = np.complex128(amp) * taps.astype(np.float64)
+    return y[:n][phase::dsr]
+
+
+IMPULSE_AMP = np.complex64(2.0 ** 5 * (1 - 0.5j))
+
+
+# WOLA cases (N, ratio = N / dec, P): the fused kernel's corners, then the rocFFT rows
+WOLA_CASES = [(N, r, P) for N in (64, 1024, 16384) for r in (1, 2) for P in (1, 63, 64)] + \
+             [(64, 2, 65), (1024, 1, 65), (48, 1, 4), (48, 2, 3), (1000, 2, 16), (32768, 1, 2), (32768, 2, 1)]
+
+
+def wola_case(seed, N, ratio, P, with_hist=False):
+    """(x, taps, hist) of a channeliser case.  Rows, in order: the P * ratio partly filled ones (none with history) and 3
+    more of noise, a run of zeros of L + 2 dec samples (at least one all-zero row), 3 rows of noise, a stretch 40 dB
+    quieter of 2 N + 100 samples, 2 rows of noise, up to 3000 samples 60 dB louder, noise to the end; the length is not a
+    multiple of dec.  Taps: a firwin prototype for even seeds + case number, Gaussian otherwise."""
+    rng = np.random.default_rng(1000 * seed + 7 * N + 3 * P + ratio + (500 if with_hist else 0))
+    dec, L = N // ratio, P * N
+    rows = 2 * P * ratio + 12 + -(-(2 * N + 100 + 3000) // dec)
+    n = rows * dec + min(3, dec - 1)
+    x = fe_noise(rng, n)
+    at = (P * ratio + 3) * dec
+    x[at : at + L + 2 * dec] = 0
+    at += L + 2 * dec + 3 * dec
+    x[at : at + 2 * N + 100] *= np.float32(0.01)
+    at += 2 * N + 100 + 2 * dec
+    x[at : at + 3000] *= np.float32(1000.0)
+    if (seed + N + P) % 2 == 0 and L >= 8:
+        import scipy.signal as sps
+
+        taps = (sps.firwin(L, 1.0 / dec) * N).astype(np.float32)
+    else:
+        taps = rng.standard_normal(L).astype(np.float32)
+    hist = fe_noise(rng, L) if with_hist else None
+    return x, taps, hist
+
+
+def worst_ratio(got, ref, unit):
+    """max |got - ref| / unit; an element whose unit is zero must be matched exactly (ratio inf otherwise)."""
+    err = np.abs(np.asarray(got, np.complex128) - ref)
+    unit = np.broadcast_to(unit, err.shape)
+    z = unit == 0
+    if np.any(err[z] != 0):
+        return np.inf
+    return float(np.max(err[~z] / unit[~z])) if np.any(~z) else 0.0

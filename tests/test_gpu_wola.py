@@ -11,30 +11,11 @@ import pytest
 from pydsproutines_amd import CAFPlan, DeviceArray, asarray
 from pydsproutines_amd.cpuWola import cpu_threaded_wola
 from pydsproutines_amd.filterRoutines import Channeliser, wola
+from ref64 import wola64
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def wola64(taps, x, dec, N, hist=None):
-    """float64 restatement: rows floor(len(x) / dec) at x[r dec], history in front, odd rows rotated by N/2 (N == 2 dec)."""
-    taps = np.asarray(taps, np.float64)
-    L = taps.size
-    P = L // N
-    h = np.zeros(0, np.complex128) if hist is None else np.asarray(hist, np.complex128)
-    xe = np.concatenate((np.zeros(L, np.complex128), h, np.asarray(x, np.complex128)))
-    off = L + h.size
-    rows = len(x) // dec
-    n = off + np.arange(rows, dtype=np.int64) * dec
-    a = np.arange(N, dtype=np.int64)
-    v = np.zeros((rows, N), np.complex128)
-    for b in range(P):
-        idx = n[:, None] - b * N - a[None, :]
-        v += taps[b * N : (b + 1) * N][None, :] * np.where(idx >= 0, xe[np.maximum(idx, 0)], 0)
-    if N == 2 * dec:
-        v[1::2] = np.roll(v[1::2], -N // 2, axis=1)
-    return np.fft.ifft(v, axis=1) * N
 
 
 def cx(rng, n):

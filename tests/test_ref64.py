@@ -1,10 +1,32 @@
 """The float64 references of tests/ref64.py against the explicit-DFT rows, the c2_mini golden surface and the oracle's
-per-delay planes (no GPU): what the GPU paths are held to must itself be right."""
+per-delay planes (no GPU): what the GPU paths are held to must itself be right.
+
+The front end (second half of this module).  The FIR / upfirdn / WOLA restatements, their units and the float32 stand-ins:
+
+* fir64 / upfirdn64 against scipy.signal.lfilter / upfirdn at 1e-12 (both the np.convolve and the FFT branch), wola64 against
+  an independent loop-form restatement at 1e-12 and against the committed fixtures (those hold the reference's own complex64
+  arithmetic, out of reach of 1e-12: they are held to the WOLA bound, like the stand-in).
+* The float32 stand-ins of the two transform-based algorithms inside C * unit on every case the GPU tests use.  They are
+  what C_FIR_OS and C_WOLA come from: worst |stand-in - float64| / unit over seeds 0 .. 9 (CAF_F64_CALIBRATE=1
+  CAF_F64_SEED=s prints the ratios instead of asserting), each constant the smallest power of two at least 4x that:
+
+      overlap-save FIR  worst 6.32 (65536 firwin taps on B = 262144: the final rounding of an output inside the 60 dB
+                        stretch, 2^-24 |y|, against a unit that spreads the stretch's energy over the block;
+                        8193 firwin taps 3.02, every other case 1.15 .. 2.5)                  -> C_FIR_OS = 32
+      WOLA              worst 0.866 (N = 64, P = 1; P = 63 / 64: 0.07 .. 0.12)                 -> C_WOLA = 4
+
+* A sequential float32 direct form inside (K + 2) * 2^-24 * A.
+"""
+
+import glob
+import os
 
 import numpy as np
 import pytest
+import scipy.signal as sps
 
 import oracle as O
+import ref64 as R
 from conftest import cn, qpsk
 from ref64 import amp_bound, caf64, perdelay64
 from test_gpu_engine_fuzz import _oracle_rows
@@ -108,3 +130,161 @@ def test_amp_bound_widens_with_the_transform_span():
     sh2 = np.arange(0, 100000, 5000)
     bp = amp_bound(rx2, n2, sh2, 65536, part_len=32768)
     assert np.all(bp > 2.0 ** -24 * 16 * np.sqrt(3 * 65536 / n2 * 0.8))
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the front end: FIR, upfirdn, WOLA
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+CHECK = os.environ.get("CAF_F64_CALIBRATE") != "1"
+SEED = int(os.environ.get("CAF_F64_SEED", "0"))
+
+
+def _rel(a, b):
+    return float(np.max(np.abs(a - b))) / max(float(np.max(np.abs(b))), 1e-300)
+
+
+@pytest.mark.parametrize("ntaps, n", [(1, 50), (33, 5000), (300, 4000), (5000, 40000)])
+def test_fir64_is_lfilter(ntaps, n):
+    rng = np.random.default_rng(ntaps)
+    x = R.fe_noise(rng, n)
+    h = rng.standard_normal(ntaps).astype(np.float32)
+    h64 = h.astype(np.float64)
+    assert (x.size * ntaps > (1 << 27)) == (ntaps == 5000)  # the last case takes the FFT branch
+    assert _rel(R.fir64(x, h), sps.lfilter(h64, 1, x.astype(np.complex128))) <= 1e-12
+    for dlen in (0, 7, ntaps - 1, ntaps + 20):
+        d = R.fe_noise(rng, dlen)
+        full = sps.lfilter(h64, 1, np.concatenate((np.zeros(ntaps), d, x)).astype(np.complex128))[ntaps + dlen :]
+        for dsr, ph in ((1, 0), (3, 2), (16, 15)):
+            assert _rel(R.fir64(x, h, d, dsr, ph), full[ph::dsr]) <= 1e-12
+    # the moduli (real input) go through the same code
+    ax = np.abs(x.astype(np.complex128))
+    assert _rel(R.fir64(ax, np.abs(h64)), sps.lfilter(np.abs(h64), 1, ax)) <= 1e-12
+    np.testing.assert_array_equal(R.direct_unit(x, h), R.EPS32 * R.fir64(ax, np.abs(h64)))
+
+
+def test_fft_branch_keeps_exact_zeros():
+    rng = np.random.default_rng(3)
+    x = R.fe_noise(rng, 40000)
+    x[10000:16000] = 0
+    h = rng.standard_normal(5000).astype(np.float32)
+    y = R.fir64(x, h)
+    assert np.all(y[10000 + 4999 : 16000] == 0) and np.all(y[16000:16100] != 0) and np.all(y[9000:14999] != 0)
+
+
+@pytest.mark.parametrize("up, down, ntaps", [(1, 1, 40), (3, 5, 33), (16, 3, 301), (17, 8, 100), (2, 1, 20000)])
+def test_upfirdn64_is_upfirdn(up, down, ntaps):
+    rng = np.random.default_rng(up * 100 + down)
+    x = R.fe_noise(rng, 2 * 7001).reshape(2, 7001)
+    h = rng.standard_normal(ntaps).astype(np.float32)
+    ref = sps.upfirdn(h.astype(np.float64), x.astype(np.complex128), up, down)
+    got = R.upfirdn64(x, h, up, down)
+    assert got.shape == ref.shape and _rel(got, ref) <= 1e-12
+    assert _rel(R.upfirdn64(x[1], h, up, down), ref[1]) <= 1e-12
+
+
+def _wola_loops(taps, x, dec, N, hist=None):
+    """The channeliser branch by branch with explicit indices and numpy's ifft: a second, independent restatement."""
+    taps = np.asarray(taps, np.float64)
+    L = taps.size
+    P = L // N
+    h = np.zeros(0, np.complex128) if hist is None else np.asarray(hist, np.complex128)
+    xe = np.concatenate((np.zeros(L, np.complex128), h, np.asarray(x, np.complex128)))
+    off = L + h.size
+    rows = len(x) // dec
+    n = off + np.arange(rows, dtype=np.int64) * dec
+    a = np.arange(N, dtype=np.int64)
+    v = np.zeros((rows, N), np.complex128)
+    for b in range(P):
+        idx = n[:, None] - b * N - a[None, :]
+        v += taps[b * N : (b + 1) * N][None, :] * np.where(idx >= 0, xe[np.maximum(idx, 0)], 0)
+    if N == 2 * dec:
+        v[1::2] = np.roll(v[1::2], -N // 2, axis=1)
+    return np.fft.ifft(v, axis=1) * N
+
+
+@pytest.mark.parametrize("N, ratio, P, hist", [(64, 1, 4, False), (64, 2, 3, True), (10, 2, 4, True), (48, 1, 5, False), (1024, 2, 2, True)])
+def test_wola64_is_the_loop_form(N, ratio, P, hist):
+    x, taps, h = R.wola_case(SEED, N, ratio, P, with_hist=hist)
+    assert _rel(R.wola64(taps, x, N // ratio, N, h), _wola_loops(taps, x, N // ratio, N, h)) <= 1e-12
+
+
+@pytest.mark.parametrize("path", sorted(glob.glob(os.path.join(GOLDEN, "wola_d*.npz"))), ids=os.path.basename)
+def test_wola64_reproduces_the_fixtures(path):
+    z = np.load(path)
+    dec = int(z["dec"])
+    N = dec if int(z["N"]) < 0 else int(z["N"])
+    ref = R.wola64(z["taps"], z["x"], dec, N)
+    assert ref.shape == z["out"].shape
+    # the fixtures are the reference's own complex64 arithmetic (1e-12 is out of their reach): a float32 channeliser like the
+    # stand-in, held to the same bound
+    unit = R.wola_unit(z["taps"], z["x"], dec, N)
+    assert R.worst_ratio(z["out"], ref, unit[:, None]) <= R.C_WOLA
+
+
+RATIOS = {}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _report():
+    yield
+    if not CHECK:
+        print("\nF64_STANDIN_RATIOS seed=%d %s" % (SEED, " ".join("%s=%.4g" % kv for kv in sorted(RATIOS.items()))))
+
+
+def _record(name, r, c):
+    RATIOS[name] = max(RATIOS.get(name, 0.0), r)
+    if CHECK:
+        assert r <= c, "%s: %.3g units (c = %g)" % (name, r, c)
+
+
+@pytest.mark.parametrize("ntaps, B", R.FIR_OS_CASES)
+@pytest.mark.parametrize("kind", R.FE_KINDS)
+def test_overlap_save_stand_in_within_bound(ntaps, B, kind):
+    x, taps = R.fir_os_case(SEED, ntaps, B, kind)
+    rng = np.random.default_rng(ntaps)
+    for delay in (None, R.fe_noise(rng, ntaps - 1) * np.float32(30)):
+        ref = R.fir64(x, taps, delay)
+        unit = R.fir_os_unit(x, taps, B, delay)
+        _record("os_%d_%s" % (ntaps, kind), R.worst_ratio(R.fir_os32(x, taps, B, delay), ref, unit), R.C_FIR_OS)
+    # and the unit's index arithmetic under decimation: the kept elements of the full-rate unit
+    np.testing.assert_array_equal(R.fir_os_unit(x, taps, B, delay, 3, 2), unit[2::3])
+
+
+@pytest.mark.parametrize("ntaps, B", R.FIR_OS_CASES)
+@pytest.mark.parametrize("kind", R.FE_KINDS)
+def test_overlap_save_stand_in_on_impulses(ntaps, B, kind):
+    """The unit without the 1 / sqrt(B) spreading (ref64.fir_os_unit(spread=False)): what C_FIR_OS_IMPULSE comes from.  The
+    float64 reference is the tap set at the impulse, exactly, and zero elsewhere."""
+    n, taps, _, pos = R.fir_os_impulse_case(SEED, ntaps, B, kind)
+    for p in pos:
+        x = R.impulse(n, p, R.IMPULSE_AMP)
+        ref = R.impulse_fir64(n, p, R.IMPULSE_AMP, taps)
+        assert np.max(np.abs(R.fir64(x, taps) - ref)) <= 1e-12 * np.max(np.abs(ref))
+        unit = R.fir_os_unit(x, taps, B, spread=False)
+        assert np.all(unit[max(0, p - B + 1) : p + B] > 0) and not unit[: max(0, p - B + 1)].any() and not unit[p + B :].any()
+        _record("os_impulse_%d_%s" % (ntaps, kind), R.worst_ratio(R.fir_os32(x, taps, B), ref, unit), R.C_FIR_OS_IMPULSE)
+
+
+@pytest.mark.parametrize("N, ratio, P", R.WOLA_CASES)
+def test_wola_stand_in_within_bound(N, ratio, P):
+    for hist in (False, True):
+        x, taps, h = R.wola_case(SEED, N, ratio, P, with_hist=hist)
+        dec = N // ratio
+        ref = R.wola64(taps, x, dec, N, h)
+        unit = R.wola_unit(taps, x, dec, N, h)
+        assert np.any(unit == 0) and np.all(ref[unit == 0] == 0)  # the all-zero rows are there, and exact
+        _record("wola_%d_%d_%d" % (N, ratio, P), R.worst_ratio(R.wola32(taps, x, dec, N, h), ref, unit[:, None]), R.C_WOLA)
+
+
+@pytest.mark.parametrize("ntaps, kind", [(8, "ends"), (95, "firwin"), (300, "gauss"), (2048, "firwin")])
+def test_sequential_float32_direct_form_within_derived_bound(ntaps, kind):
+    rng = np.random.default_rng(ntaps + 1000 * SEED)
+    x = R.fe_record(rng, 3000 + 2 * 1024 + 100 + ntaps + 50 + 1500, 1024, ntaps)
+    taps = R.fe_taps(rng, kind, ntaps)
+    delay = R.fe_noise(rng, ntaps - 1)
+    idx = np.unique(np.concatenate((np.arange(0, 40), rng.integers(0, x.size, 300 if ntaps <= 300 else 60))))
+    got = R.fir_direct32(x, taps, delay, idx)
+    ref = R.fir64(x, taps, delay)[idx]
+    unit = (ntaps + 2) * R.direct_unit(x, taps, delay)[idx]
+    assert R.worst_ratio(got, ref, unit) <= 1.0
