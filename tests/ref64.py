@@ -456,3 +456,264 @@ def worst_ratio(got, ref, unit):
     if np.any(err[z] != 0):
         return np.inf
     return float(np.max(err[~z] / unit[~z])) if np.any(~z) else 0.0
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# The chirp-Z family: the direct sum in complex128 (no Bluestein), the zoom planes on top of it, the unit of their error
+# bound, a float32 stand-in of the three-multiply, two-FFT chain (which calibrates C_CZT), the bound of the
+# tone-dot kernel, and the cases that tests/test_ref64.py (CPU) and tests/test_gpu_f64_czt.py (GPU) share.
+
+C_CZT = 16.0  # chirp-Z chain: smallest power of two >= 4x the stand-in's worst ratio over seeds 0 .. 9 (3.75, test_ref64.py)
+
+
+def fast_len7(n):
+    """Smallest 2^a 3^b 5^c 7^d >= n (the transform length every chirp-Z object of the package picks)."""
+    n = int(n)
+    while True:
+        v = n
+        for p in (2, 3, 5, 7):
+            while v % p == 0:
+                v //= p
+        if v == 1:
+            return n
+        n += 1
+
+
+def factors(n):
+    return {p for p in (2, 3, 5, 7) if n % p == 0}
+
+
+def _cycles(f, n):
+    """frac(f[j] * n[i]) (len(f), len(n)) in float64, good to 2^-34 |f| of a cycle at any n < 2^31: n = 4096 n_hi + n_lo and
+    frac(4096 f) is exact, so no product ever carries more than 2^19 whole cycles into its rounding."""
+    f = np.atleast_1d(np.asarray(f, np.float64))
+    n = np.asarray(n, np.int64)
+    g = np.mod(f * 4096.0, 1.0)
+    cyc = g[:, None] * (n >> 12).astype(np.float64) + f[:, None] * (n & 4095).astype(np.float64)
+    return cyc - np.floor(cyc)
+
+
+def czt64(x, f_eval, fs=1.0):
+    """y[r, j] = sum_n x[r, n] exp(-2 pi i f_eval[j] n / fs), the direct sum in complex128; 1-D x gives 1-D y.  The phase is
+    reduced in cycles before exp; the exp matrix is built for at most 2^22 (bin, sample) pairs at a time."""
+    x = np.asarray(x)
+    one = x.ndim == 1
+    x2 = np.atleast_2d(x).astype(np.complex128)
+    nu = np.atleast_1d(np.asarray(f_eval, np.float64)) / float(fs)
+    m = x2.shape[1]
+    y = np.zeros((x2.shape[0], nu.size), np.complex128)
+    kc = max(1, min(nu.size, (1 << 22) // min(m, 1 << 16)))
+    for n0 in range(0, m, 1 << 16):
+        n = np.arange(n0, min(m, n0 + (1 << 16)))
+        for j0 in range(0, nu.size, kc):
+            e = np.exp(-2j * np.pi * _cycles(nu[j0 : j0 + kc], n))
+            y[:, j0 : j0 + kc] += x2[:, n0 : n0 + n.size] @ e.T
+    return y[0] if one else y
+
+
+CZT_CLASSES = {"CZTCachedGPU": ("gpu", "py"), "CZTCached": ("py", "py"), "czt": ("py", "py"), "pbIppCZT32fc": ("py", "cpp")}
+
+
+def czt_grid(cls, m, f1, f2, bw, fs):
+    """What a chirp-Z class of the package does with (f1, f2, binWidth, fs) on rows of m samples: dict of k, nfft, the
+    labels getFreq() reports (f1 + j bw), the frequencies it evaluates and the chirp step wexp in cycles per sample:
+    (f2 - f1 + bw) / k per bin under the "py" rule, bw under the "cpp" rule; equal whenever (f2 - f1) / bw is whole."""
+    nfft_rule, w_rule = CZT_CLASSES[cls]
+    k = int((f2 - f1) / bw + 1)
+    df = bw if w_rule == "cpp" else (f2 - f1 + bw) / k
+    nfft = fast_len7(m + k + 1) if nfft_rule == "gpu" else fast_len7(m + k - 1)
+    j = np.arange(k, dtype=np.float64)
+    return dict(k=k, nfft=nfft, labels=f1 + j * bw, f_eval=f1 + j * df, wexp=df / fs)
+
+
+def czt_unit(x, nfft, ref=None):
+    """2^-24 * (log2(nfft) * ||x_row||_2 + |ref|).  The first term is one number per row ((rows, 1) for 2-D x): Bluestein passes
+    the whole row through two nfft-point transforms, so the rounding of any sample reaches every bin alike.  The second is the
+    bin's own size (|y|, or the amplitude where amplitudes are compared): the last stages of the inverse transform, the
+    post-chirp and the 1 / nfft round at the size of the value they produce, which for a row that the transform compresses
+    into a peak (a tone, a matched product row: |y| up to sqrt(m) ||x||_2) is far above the row term -- the float32 stand-in
+    is 9.8 units of the row term alone off at such a peak, 1000 samples.  Without ref: the row term."""
+    x = np.asarray(x)
+    nrm = np.sqrt(np.sum(np.abs(x.astype(np.complex128)) ** 2, axis=-1, keepdims=x.ndim > 1))
+    u = EPS32 * np.log2(nfft) * nrm
+    return u if ref is None else u + EPS32 * np.abs(ref)
+
+
+def czt32(x, f1, fs, wexp, k, nfft):
+    """float32 stand-in of the chirp-Z chain: x * aa -> fft -> * fv -> ifft -> [m - 1 : m + k - 1] * ww in complex64 with
+    scipy.fft; the constants are computed in float64 and cast to complex64 (as _CZTBase and zoom_constants do)."""
+    x = np.atleast_2d(np.asarray(x)).astype(np.complex64)
+    m = x.shape[1]
+    assert nfft >= m + k - 1
+    kk = np.arange(-m + 1, max(k - 1, m - 1) + 1, dtype=np.float64)
+    cyc = wexp * (kk * kk / 2.0)
+    ww = np.exp(-2j * np.pi * (cyc - np.floor(cyc)))
+    fv = np.fft.fft(1.0 / ww[: k - 1 + m], nfft).astype(np.complex64)
+    nn = np.arange(m)
+    aa = (np.exp(-2j * np.pi * _cycles(f1 / fs, nn)[0]) * ww[m - 1 + nn]).astype(np.complex64)
+    buf = np.zeros((x.shape[0], nfft), np.complex64)
+    buf[:, :m] = x * aa
+    g = sfft.ifft(sfft.fft(buf, axis=1, workers=_WORKERS) * fv, axis=1, workers=_WORKERS)
+    y = g[:, m - 1 : m + k - 1] * ww[m - 1 : m + k - 1].astype(np.complex64)
+    assert g.dtype == np.complex64 and y.dtype == np.complex64
+    return y
+
+
+def zoom_rows64(template, rx, delays, auto_conj=True):
+    """The zoom's product rows in float64: p = rx[d : d + n] * conj(u) / (||rx[d : d + n]|| ||u||) per delay, u the template
+    (conjugated by the plan unless auto_conj is off); NaN rows where the window holds no energy."""
+    t = np.asarray(template).astype(np.complex128)
+    uc = np.conj(t) if auto_conj else t
+    n = t.size
+    d = np.asarray(delays, np.int64)
+    w = np.asarray(rx)[d[:, None] + np.arange(n)].astype(np.complex128)
+    e = np.sum(np.abs(w) ** 2, axis=1) * np.sum(np.abs(t) ** 2)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        p = w * uc / np.sqrt(e)[:, None]
+    p[e == 0] = np.nan
+    return p
+
+
+def zoom64(template, rx, delays, f0, span, step, nbins, auto_conj=True):
+    """(planes (len(delays), nbins) float64, product rows): |czt64(p_d, f0_d - span + j step)|^2 per delay, frequencies in
+    cycles per sample.  A window of zero energy gives a NaN plane (as caf64 does)."""
+    p = zoom_rows64(template, rx, delays, auto_conj)
+    f0 = np.broadcast_to(np.asarray(f0, np.float64), (p.shape[0],))
+    rel = -span + np.arange(nbins, dtype=np.float64) * step
+    pl = np.full((p.shape[0], nbins), np.nan)
+    n = np.arange(p.shape[1])
+    for i in range(p.shape[0]):
+        if not np.isnan(p[i, 0]):
+            # the coarse frequency is taken out of the row first (a rotation, exact to 2^-53), so that all rows share the grid
+            pl[i] = np.abs(czt64(p[i] * np.exp(-2j * np.pi * _cycles(f0[i], n)[0]), rel)) ** 2
+    return pl, p
+
+
+def zoom_nbins(span, step):
+    return int(np.floor(2.0 * span / step + 1.0 + 1e-9))
+
+
+def czt_rows(rng, m, rows=6):
+    """Unit noise rows with row 1 60 dB louder than its neighbours, row 2 40 dB quieter, row 3 all zeros and row 4 with a
+    60 dB step in the middle (rows beyond stay noise)."""
+    x = fe_noise(rng, rows * m).reshape(rows, m)
+    x[1] *= np.float32(1000.0)
+    x[2] *= np.float32(0.01)
+    x[3] = 0
+    x[4, m // 2 :] *= np.float32(1000.0)
+    return x
+
+
+# (m, k, whole): rows of m samples on k bins; whole=False puts half a bin more into f2 - f1 (labels != evaluated frequencies
+# under the "py" rule).  Every m of {1, 2, 10, 255, 256, 257, 1000, 4096} and every k of {1, 2, 65, 129, 1001}, k > m and
+# k < m; test_ref64.py checks that the transform lengths hold a factor 3, 5 and 7 at least once each.
+CZT_CASES = [(1, 1, True), (1, 65, True), (2, 2, True), (2, 1001, False), (10, 1, True), (10, 129, False), (255, 65, True),
+             (255, 1001, True), (256, 2, True), (256, 129, True), (257, 65, False), (257, 1001, True), (1000, 129, True),
+             (1000, 1001, False), (4096, 65, True), (4096, 1001, True)]
+CZT_LONG = (1 << 17, 257, True)
+CZT_CHUNK = (2048, 2049, True)   # nfft 4096 (py) / 4116 (gpu): 2^25 // nfft + 1 rows reach the second chunk of the row loop
+CZT_SPLIT = (8, 9, True)         # 65537 rows: the second launch of the 65535-row split
+CZT_ZOOM = [(1000, 129), (1000, 201), (500, 129), (500, 201)]  # (n, bins) of the zoom: nfft 1134, 1200, 630, 700
+CZT_FS = 1000.0
+
+
+def czt_params(m, k, whole):
+    """(f1, f2, binWidth, fs) of a case: binary fractions, so that int((f2 - f1) / bw + 1) is k without doubt."""
+    bw = 0.125
+    f1 = -17.375
+    return f1, f1 + (k - 1 + (0 if whole else 0.5)) * bw, bw, CZT_FS
+
+
+# The tone-dot kernel (caf_dot_tones): out[b][k] = sum over the 64 samples i of block b of src[i] e^{2 pi i (f0 + k fstep) i}.
+# Per sample the kernel forms src[i] * tone(f0 + k0 fstep) with k0 = 64 (k // 64) from a float64 phase, then takes r = k mod 64
+# steps src * tone *= alpha, alpha = e^{2 pi i fstep i} cast to complex64, and sums the 64 products of a block one after
+# another in float32.  With u = 2^-24, to first order and per sample of modulus a:
+#   the cast of a unit phasor to complex64 is off by <= u / sqrt(2) < u, a complex64 product by <= sqrt(5) u |ab| < 3 u |ab|
+#     (Brent, Percival, Zimmermann 2007; fewer roundings with FMA) -> the anchor product is within 4 u a;
+#   each recurrence step adds a rounded alpha (u a) and a product (3 u a)                  -> 4 r u a after r steps;
+#   a sequential float32 sum of 64 terms is within 63 u sum |term| of the exact sum        -> 63 u A, A = sum |src_i|;
+#   the float64 phases (f0 + k0 fstep) i and fstep i are each formed with two roundings (2^-52 relative) before their whole
+#     cycles are dropped                                                                   -> 2 pi 2^-52 (|f0 + k0 fstep| + r |fstep|) i a.
+# Hence |got - ref| <= (4 r + 68) u A_b + 2 pi 2^-52 (|f0 + k0 fstep| + r |fstep|) sum_i i |src_i|, c(r) = 4 r + 68 (one unit
+# spare for the second-order terms).  This is the DERIVED bound, not a calibrated one: it is some 20 times what the kernel
+# shows on noise (a random walk over 64 terms), and still 10^5 times below the effect of one misplaced sample or frequency.
+
+
+def dot_tones64(f0, fstep, num_freqs, src):
+    """(ceil(len / 64), num_freqs) complex128 block sums, phases exact to 2^-34 of a cycle at any index."""
+    src = np.asarray(src).astype(np.complex128)
+    nb = (src.size + 63) // 64
+    pad = np.zeros(nb * 64, np.complex128)
+    pad[: src.size] = src
+    f = f0 + np.arange(num_freqs, dtype=np.float64) * fstep
+    out = np.empty((nb, num_freqs), np.complex128)
+    bc = max(1, (1 << 22) // (64 * num_freqs))
+    for b0 in range(0, nb, bc):
+        i = np.arange(b0 * 64, min(nb, b0 + bc) * 64)
+        e = np.exp(2j * np.pi * _cycles(f, i))  # (K, i)
+        out[b0 : b0 + bc] = np.einsum("bc,kbc->bk", pad[i].reshape(-1, 64), e.reshape(num_freqs, -1, 64))
+    return out
+
+
+def dot_tones_bound(f0, fstep, num_freqs, src):
+    """The derived bound above per (block, frequency)."""
+    a = np.abs(np.asarray(src).astype(np.complex128))
+    nb = (a.size + 63) // 64
+    pad = np.zeros(nb * 64)
+    pad[: a.size] = a
+    A = pad.reshape(nb, 64).sum(axis=1)
+    Ai = (pad * np.arange(nb * 64, dtype=np.float64)).reshape(nb, 64).sum(axis=1)
+    k = np.arange(num_freqs)
+    r = (k % 64).astype(np.float64)
+    fa = np.abs(f0 + (k - k % 64) * fstep) + r * abs(fstep)
+    return (4 * r + 68)[None, :] * EPS32 * A[:, None] + 2 * np.pi * 2.0 ** -52 * fa[None, :] * Ai[:, None]
+
+
+def dot_tones32(f0, fstep, num_freqs, src):
+    """float32 stand-in of the tone-dot kernel: float64 anchors every 64 frequencies, complex64 recurrence, sequential float32
+    block sums (np.cumsum on float32 adds in order)."""
+    src = np.asarray(src, np.complex64)
+    nb = (src.size + 63) // 64
+    pad = np.zeros(nb * 64, np.complex64)
+    pad[: src.size] = src
+    i = np.arange(nb * 64)
+    alpha = np.exp(2j * np.pi * _cycles(fstep, i)[0]).astype(np.complex64)
+    out = np.empty((nb, num_freqs), np.complex64)
+    for k0 in range(0, num_freqs, 64):
+        cur = pad * np.exp(2j * np.pi * _cycles(f0 + k0 * fstep, i)[0]).astype(np.complex64)
+        for r in range(min(64, num_freqs - k0)):
+            w = cur.reshape(nb, 64)
+            out[:, k0 + r] = np.cumsum(w.real, axis=1, dtype=np.float32)[:, -1] + 1j * np.cumsum(w.imag, axis=1, dtype=np.float32)[:, -1]
+            cur = cur * alpha
+        assert cur.dtype == np.complex64
+    return out
+
+
+def synthetic_traces(S):
+    """Traces for the zoom's selection stage: name -> (trace float32 (S,), min_height, k).  tests/test_ref64.py checks (no GPU)
+    that each carries the condition it is named for."""
+    rng = np.random.default_rng(S)
+    out = {}
+    t = np.zeros(S, np.float32)
+    pos = 10 + 10 * np.arange(15)
+    t[pos] = np.float32([0.9, 0.5, 0.3, 0.5, 0.9, 0.5, 0.3, 0.9, 0.5, 0.3, 0.9, 0.5, 0.9, 0.5, 0.3])
+    out["ties_cut"] = (t, 0.0, 8)  # five at 0.9, six at 0.5: k = 8 takes the first three of the six
+    t = np.zeros(S, np.float32)
+    t[1::2] = rng.uniform(0.2, 0.9, t[1::2].size).astype(np.float32)
+    t[1001], t[3001], t[5] = t[1::2].max(), t[1::2].max(), t[1::2].max()  # ties among lanes of the strided scan
+    out["many"] = (t, 0.0, 8)
+    t = np.zeros(S, np.float32)
+    t[1::2] = 0.5
+    out["many_equal"] = (t, 0.0, 8)
+    t = np.zeros(S, np.float32)
+    t[[S // 2, 17, S - 40]] = np.float32([0.4, 0.4, 0.7])
+    out["few"] = (t, 0.0, 8)
+    out["none"] = (np.zeros(S, np.float32), 0.0, 8)
+    t = np.zeros(S, np.float32)
+    t[0], t[-1], t[99], t[151], t[300] = 0.7, 0.6, 0.8, 0.8, 0.4
+    t[100:151] = np.nan
+    out["ends_nan"] = (t, 0.0, 8)
+    t = np.zeros(S, np.float32)
+    t[[50, 150, 250]] = np.float32([0.5, 0.75, 0.25])
+    out["height_equal"] = (t, 0.5, 8)
+    return out

@@ -288,3 +288,165 @@ def test_sequential_float32_direct_form_within_derived_bound(ntaps, kind):
     ref = R.fir64(x, taps, delay)[idx]
     unit = (ntaps + 2) * R.direct_unit(x, taps, delay)[idx]
     assert R.worst_ratio(got, ref, unit) <= 1.0
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# The chirp-Z family (third part of this module): czt64 against np.fft.fft on a grid and zoom64 against caf64 at the same
+# (delay, frequency) pairs; the float32 stand-in czt32 over seeds 0 .. 9 on every case of tests/test_gpu_f64_czt.py, which is
+# where C_CZT comes from (worst ratio 1.41 among the rows of up to 10 samples, 1.18 up to 257, 1.15 up to 4096, 0.73 at
+# m = 2^17, 3.75 on the zoom's product rows with a matched burst: no growth with sqrt(m), the row term stays flat) -> C_CZT = 16; the tone-dot stand-in inside the derived
+# bound; and the conditions the GPU tests impose that need no GPU: NaN planes on zero windows, exact zeros on zero rows,
+# the oracle's tie order on the synthetic traces.
+
+CZT_CASE_RATIOS = {}  # (family, case) -> the stand-in's worst ratio on that case, filled by the stand-in tests below
+
+
+def _czt_family(name, r, case):
+    CZT_CASE_RATIOS[(name, case)] = max(CZT_CASE_RATIOS.get((name, case), 0.0), r)
+
+
+def test_czt64_is_the_fft_on_a_grid():
+    rng = np.random.default_rng(5)
+    for m in (1, 7, 360, 1000):
+        x = R.czt_rows(rng, m)
+        got = R.czt64(x, np.arange(m) * (8.0 / m), 8.0)
+        ref = np.fft.fft(x.astype(np.complex128), axis=1)
+        assert np.max(np.abs(got - ref)) <= 1e-12 * np.max(np.abs(ref), initial=1.0) * max(1, m) ** 0.5
+        assert not got[3].any()  # the all-zero row, exactly
+    # a long row, frequencies far off the principal interval: _cycles against exact rational arithmetic
+    from fractions import Fraction
+
+    f, n = np.array([370.37, -0.1234567, 5e-7]), np.array([0, 1, 4095, 4096, 2 ** 20 + 16, 2 ** 31 - 1])
+    exact = np.array([[float((Fraction(float(a)) * int(b)) % 1) for b in n] for a in f])
+    d = np.abs(R._cycles(f, n) - exact)
+    assert np.max(np.minimum(d, 1 - d)) <= 2.0 ** -34 * 371
+
+
+def test_czt_grids_of_the_classes():
+    for cls in R.CZT_CLASSES:
+        g = R.czt_grid(cls, 10, *R.czt_params(10, 129, True))
+        assert g["k"] == 129 and np.array_equal(g["labels"], g["f_eval"])
+        g = R.czt_grid(cls, 10, *R.czt_params(10, 129, False))
+        assert g["k"] == 129 and (np.array_equal(g["labels"], g["f_eval"]) == (cls == "pbIppCZT32fc"))
+        assert g["nfft"] == R.fast_len7(10 + 129 + (1 if cls == "CZTCachedGPU" else -1))
+    seen = set()
+    for m, k, whole in R.CZT_CASES + [R.CZT_LONG, R.CZT_CHUNK, R.CZT_SPLIT]:
+        assert R.czt_grid("CZTCached", m, *R.czt_params(m, k, whole))["k"] == k
+        for cls in R.CZT_CLASSES:
+            seen |= R.factors(R.czt_grid(cls, m, *R.czt_params(m, k, whole))["nfft"])
+    assert seen == {2, 3, 5, 7}
+    assert {m for m, _, _ in R.CZT_CASES} == {1, 2, 10, 255, 256, 257, 1000, 4096} and {k for _, k, _ in R.CZT_CASES} == {1, 2, 65, 129, 1001}
+    for n, nb in R.CZT_ZOOM:
+        assert {5, 7} & R.factors(R.fast_len7(n + nb - 1))
+
+
+@pytest.mark.parametrize("m, k, whole", R.CZT_CASES + [R.CZT_LONG, R.CZT_CHUNK, R.CZT_SPLIT])
+def test_czt_stand_in_within_bound(m, k, whole):
+    """All ten seeds at once (the rows of one call share the exp matrix of czt64)."""
+    rows = 1 if m >= (1 << 17) else 6
+    x = np.concatenate([R.czt_rows(np.random.default_rng(1000 * s + m + k), m, max(rows, 5))[: max(rows, 5)] for s in range(10)])
+    f1, f2, bw, fs = R.czt_params(m, k, whole)
+    for cls in ("CZTCachedGPU", "CZTCached", "pbIppCZT32fc"):
+        g = R.czt_grid(cls, m, f1, f2, bw, fs)
+        ref = R.czt64(x, g["f_eval"], fs)
+        unit = R.czt_unit(x, g["nfft"], ref)
+        got = R.czt32(x, f1, fs, g["wexp"], k, g["nfft"])
+        r = R.worst_ratio(got, ref, unit)
+        _czt_family("m<=10" if m <= 10 else "m<=257" if m <= 257 else "m<=4096" if m <= 4096 else "m=2^17", r, (m, k, whole))
+        assert r <= R.C_CZT, "%s m=%d k=%d nfft=%d: %.3g units" % (cls, m, k, g["nfft"], r)
+        z = ~np.any(x, axis=1)
+        assert z.any() and not got[z].any() and not ref[z].any()  # all-zero rows: exact zeros from both
+
+
+@pytest.mark.parametrize("n, nb", R.CZT_ZOOM)
+def test_zoom_stand_in_within_bound_and_zoom64_is_caf64(n, nb):
+    worst = 0.0
+    for seed in range(10):
+        rng = np.random.default_rng(100 * seed + n + nb)
+        t = qpsk(rng, n)
+        rx = cn(rng, 3 * n + 50)
+        rx[n + 20 : 2 * n + 40] = 0                      # delay n + 20: a window of exact zeros
+        rx[n // 2 :n] *= np.float32(1000.0)              # delay 0: a 60 dB step in the middle of the window
+        delays = np.array([0, 7, n + 20, 2 * n + 50])    # (the last window ends on rx's last sample)
+        step = 1.0 / (64 * n)
+        span = (nb // 2) * step
+        f0 = rng.uniform(-0.2, 0.2, delays.size)
+        # delay 7: a burst of the template 0.3 fine bins off the coarse frequency -- a row the transform compresses into a peak
+        rx[7 : 7 + n] += (2 * t * np.exp(2j * np.pi * (f0[1] + 0.3 * step) * np.arange(n))).astype(np.complex64) * np.where(np.arange(7, 7 + n) >= n // 2, np.float32(1000.0), np.float32(1.0))
+        pl, p = R.zoom64(t, rx, delays, f0, span, step, nb)
+        assert R.zoom_nbins(span, step) == nb
+        assert np.isnan(pl[2]).all() and np.isnan(p[2]).all() and not np.isnan(pl[[0, 1, 3]]).any()
+        if seed == 0:
+            # against caf64 at the same (delay, frequency) pairs, on the record before its 60 dB stretches (caf64 is ONE FFT
+            # correlation over the whole record: its own float64 rounding scales with the loudest stretch)
+            plain = np.where(np.abs(rx) > 50, 0, rx).astype(np.complex64)
+            pl0, _ = R.zoom64(t, plain, delays, f0, span, step, nb)
+            for i in (0, 1, 3):
+                ref = caf64(t, plain, f0[i] - span + np.arange(nb) * step, delays[i : i + 1])[0, 0]
+                np.testing.assert_allclose(np.sqrt(pl0[i]), np.sqrt(ref), rtol=0, atol=1e-13)
+            assert np.isnan(caf64(t, rx, np.array([0.0]), delays[2:3])).all()
+        nfft = R.fast_len7(n + nb - 1)
+        ok = [0, 1, 3]
+        rot = p[ok] * np.exp(-2j * np.pi * R._cycles(f0[ok], np.arange(n)))
+        got = R.czt32(rot, -span, 1.0, step, nb, nfft)
+        worst = max(worst, float(np.max(np.abs(np.abs(got.astype(np.complex128)) - np.sqrt(pl[ok])) / (R.C_CZT * R.czt_unit(p[ok], nfft, np.sqrt(pl[ok]))))))
+    _czt_family("zoom", worst * R.C_CZT, (n, nb))
+    assert worst <= 1.0, "zoom n=%d bins=%d: %.3g of the bound" % (n, nb, worst)
+
+
+def test_c_czt_follows_the_calibration_rule():
+    """C_CZT is the smallest power of two >= 4x the stand-in's worst ratio over ALL cases: whichever of them this run has not
+    computed yet (a selection with -k, another worker) is computed here, so the answer does not depend on what ran before."""
+    for case in R.CZT_CASES + [R.CZT_LONG, R.CZT_CHUNK, R.CZT_SPLIT]:
+        if not any(c == case for _, c in CZT_CASE_RATIOS):
+            test_czt_stand_in_within_bound(*case)
+    for case in R.CZT_ZOOM:
+        if ("zoom", case) not in CZT_CASE_RATIOS:
+            test_zoom_stand_in_within_bound_and_zoom64_is_caf64(*case)
+    fam = {}
+    for (name, _), r in CZT_CASE_RATIOS.items():
+        fam[name] = max(fam.get(name, 0.0), r)
+    w = max(fam.values())
+    print("\nCZT_STANDIN_RATIOS %s -> C_CZT = %g" % (" ".join("%s=%.4g" % kv for kv in sorted(fam.items())), 2.0 ** np.ceil(np.log2(4 * w))))
+    assert len(CZT_CASE_RATIOS) == len(R.CZT_CASES) + 3 + len(R.CZT_ZOOM) and R.C_CZT == 2.0 ** np.ceil(np.log2(4 * w))
+
+
+@pytest.mark.parametrize("n, K", [(1, 1), (63, 63), (64, 64), (65, 65), (1000, 129), (5000, 1000), (2 ** 20 + 17, 65)])
+def test_dot_tones_stand_in_within_derived_bound(n, K):
+    rng = np.random.default_rng(n + K)
+    src = R.fe_noise(rng, n)
+    src[n // 3 : n // 2] *= np.float32(1000.0)
+    worst = 0.0
+    for f0, fstep in ((-0.3125, 1.0 / 4096), (-7.3, 0.37)):
+        ref = R.dot_tones64(f0, fstep, K, src)
+        np.testing.assert_allclose(ref[:64], O.kernels.dotTonesScaling(f0, fstep, K, src)[:64], rtol=0, atol=1e-9 * 1000 * 64)
+        bound = R.dot_tones_bound(f0, fstep, K, src)
+        worst = max(worst, R.worst_ratio(R.dot_tones32(f0, fstep, K, src), ref, bound))
+        tot = R.czt64(src, -(f0 + np.arange(K) * fstep))
+        assert np.max(np.abs(ref.sum(axis=0) - tot)) <= 1e-9 * np.sum(np.abs(src))
+    print("\nDOT_TONES_STANDIN n=%d K=%d: %.3g of the derived bound" % (n, K, worst))
+    assert worst <= 1.0
+
+
+def test_synthetic_traces_carry_the_conditions_they_are_for():
+    for name, (trace, min_height, k) in R.synthetic_traces(4000).items():
+        idx = O.kernels.findLocalMaxima(trace, min_height)
+        sel = O.kernels.topk_peaks(trace, min_height, k)
+        v = trace[sel]
+        assert np.all(np.diff(v) <= 0) and np.all((np.diff(v) < 0) | (np.diff(sel) > 0)), name  # value descending, delay ascending
+        if name == "ties_cut":
+            assert idx.size > k and v[-1] == trace[idx][np.argsort(-trace[idx], kind="stable")][k]  # k cuts through a tie
+        if name == "many_equal":
+            assert idx.size > 16 * 64 and np.unique(trace[idx]).size == 1
+        if name == "many":
+            assert idx.size > 1024 and idx.size > k
+        if name == "few":
+            assert 0 < idx.size < k
+        if name == "none":
+            assert idx.size == 0
+        if name == "ends_nan":
+            assert idx[0] == 0 and idx[-1] == trace.size - 1 and np.isnan(trace).any()
+            nan = np.nonzero(np.isnan(trace))[0]
+            assert not np.isin(np.concatenate((nan - 1, nan + 1)), idx).any()  # x > NaN is false: no maximum beside a NaN
+        if name == "height_equal":
+            assert np.any(trace == np.float32(min_height)) and not np.any(trace[idx] == np.float32(min_height))
