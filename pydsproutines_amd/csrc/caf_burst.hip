@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "caf_internal.h"
+#include "caf_wave.h"
 
 namespace caf {
 
@@ -184,12 +185,7 @@ __global__ __launch_bounds__(1024) void k_scan_i64(int64_t* __restrict__ a, int6
     for (int64_t c0 = 0; c0 < n; c0 += 1024) {
         const int64_t t = c0 + threadIdx.x;
         const int64_t v = t < n ? a[t] : 0;
-        int64_t incl = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int64_t u = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += u;
-        }
+        const int64_t incl = wave_scan_inclusive(v, lane);
         if (lane == 63) s_wave[wave] = incl;
         __syncthreads();
         int64_t off = s_base;
@@ -414,8 +410,7 @@ __global__ __launch_bounds__(GE_TILE) void k_ge_count(const int32_t* __restrict_
         const int32_t k = ge_stored(counts, r, emax);
         for (int32_t j = 0; j < k; ++j) c += edges[r * emax + j] != 0;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    c = wave_sum(c);
     if (lane == 0) s_w[wave] = c;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -437,12 +432,7 @@ __global__ __launch_bounds__(GE_TILE) void k_ge_compact(const int32_t* __restric
         k = ge_stored(counts, r, emax);
         for (int32_t j = 0; j < k; ++j) c += edges[r * emax + j] != 0;
     }
-    int64_t incl = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int64_t u = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += u;
-    }
+    const int64_t incl = wave_scan_inclusive(c, lane);
     if (lane == 63) s_w[wave] = incl;
     __syncthreads();
     int64_t off = tile_off[blockIdx.x] + incl - c;
@@ -473,12 +463,7 @@ __global__ __launch_bounds__(1024) void k_ge_pair(const int32_t* __restrict__ fl
     for (int64_t c0 = 0; c0 < T; c0 += 1024) {
         const int64_t j = c0 + me;
         const int32_t e = j < T ? flat[j] : 0;
-        int32_t seg = e > 0 ? me + 1 : 0;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int32_t u = __shfl_up(seg, o, 64);
-            if (lane >= o) seg = max(seg, u);
-        }
+        int32_t seg = wave_scan_inclusive(e > 0 ? me + 1 : 0, lane, [](int32_t a, int32_t b) { return max(a, b); });
         if (lane == 63) s_wave[wave] = seg;
         s_lval[me + 1] = e > 0 ? e : 0;
         s_first[me + 1] = 0x7fffffff;

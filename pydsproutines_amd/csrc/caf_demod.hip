@@ -10,14 +10,15 @@
 // Rows that do not fit the LDS image (more than DEMOD_LDS_SAMPLES samples) take the same steps from global memory.
 //
 // Summation order (fixed, a function of the row alone, never of the launch): thread t of 256 adds the elements
-// t, t + 256, t + 512, ... of a phase in increasing order in float32; the 64 lanes of a wave are combined by an xor
-// butterfly (offsets 32, 16, ..., 1), the four waves as ((w0 + w1) + w2) + w3.  The stand-alone kernels and the fused
+// t, t + 256, t + 512, ... of a phase in increasing order in float32; the 64 lanes of a wave are combined by wave_sum
+// (caf_wave.h: the fixed xor butterfly), the four waves as ((w0 + w1) + w2) + w3.  The stand-alone kernels and the fused
 // one call the same device functions, so a chain of stand-alone calls gives the fused call's bits.
 // Floating-point contraction is off in this file: every product and sum below is rounded where it is written.
 #include <algorithm>
 #include <cstdint>
 
 #include "caf_internal.h"
+#include "caf_wave.h"
 
 #pragma clang fp contract(off)
 
@@ -33,11 +34,6 @@ struct Red {
     float f[3][4];
     uint32_t u[2][4];
 };
-
-__device__ __forceinline__ float wave_sum(float v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 __device__ __forceinline__ void block_sum3(float& a, float& b, float& c, Red& red) {
     a = wave_sum(a);
@@ -66,15 +62,9 @@ __device__ __forceinline__ float block_sum(float a, Red& red) {
     return a;
 }
 
-// the largest count wins, the lowest flat index among equals (NumPy's / argmax.cu's first maximum)
+// the largest count wins, the lowest flat index among equals (the tie rule of caf_wave.h)
 __device__ __forceinline__ void block_argmax(uint32_t& cnt, uint32_t& idx, Red& red) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t c2 = __shfl_xor(cnt, o), i2 = __shfl_xor(idx, o);
-        if (c2 > cnt || (c2 == cnt && i2 < idx)) {
-            cnt = c2;
-            idx = i2;
-        }
-    }
+    wave_argmax(cnt, idx);
     const int w = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) {
         red.u[0][w] = cnt;

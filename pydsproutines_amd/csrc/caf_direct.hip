@@ -11,6 +11,7 @@
 // hypotheses each per pass (they share each sample load); multipliers from LDS; the window energy is the float64 sum over
 // the K samples themselves (no prefix differences), so a window of zeros has energy exactly 0.
 #include "caf_internal.h"
+#include "caf_wave.h"
 
 namespace caf {
 
@@ -126,7 +127,8 @@ __global__ __launch_bounds__(256) void k_direct_caf(const float2* __restrict__ r
                 }
             }
         }
-        // the four sub-chunks of a delay sit in adjacent lanes: highest value, lowest hypothesis on ties
+        // the four sub-chunks of a delay sit in adjacent lanes: highest value, lowest hypothesis on ties (the tie rule of
+        // caf_wave.h, spelled out: the two delays' exchanges are interleaved, two wave_argmax calls compile differently)
 #pragma unroll
         for (int o = 1; o <= 2; o <<= 1) {
             float ov = __shfl_xor(bv0, o, 64);
@@ -153,14 +155,7 @@ __global__ __launch_bounds__(256) void k_direct_caf(const float2* __restrict__ r
                 b.delay = (int32_t)(shift_start + i1);
                 b.f = bi1;
             }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                PeakRec r;
-                r.v = __shfl_xor(b.v, o, 64);
-                r.delay = __shfl_xor(b.delay, o, 64);
-                r.f = __shfl_xor(b.f, o, 64);
-                if (r.v > b.v || (r.v == b.v && r.delay < b.delay)) b = r;
-            }
+            wave_argmax(b.v, b.delay, b.f);
             __syncthreads();  // (s_w of the previous template has been read)
             if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = b;
             __syncthreads();

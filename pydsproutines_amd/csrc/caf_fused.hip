@@ -30,6 +30,7 @@
 
 #include "caf_internal.h"
 #include "caf_fft_dev.h"
+#include "caf_wave.h"
 
 namespace caf {
 
@@ -591,11 +592,7 @@ __device__ __forceinline__ void fused_item(float2* __restrict__ s_d, const float
             }
             const uint32_t dloc = pk_d0 + (16u * bii + 64u * bq) * 64u;
             unsigned long long key = bvv < 0.f ? 0ull : (((unsigned long long)__float_as_uint(bvv) << 32) | (uint32_t)~dloc);
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const unsigned long long ok = __shfl_xor(key, o, 64);
-                key = ok > key ? ok : key;
-            }
+            key = wave_max(key);
             if ((tid & 63) == 0) {
                 PeakRec r;
                 r.v = key ? __uint_as_float((uint32_t)(key >> 32)) : -1.f;
@@ -1227,7 +1224,8 @@ __global__ __launch_bounds__(256) void k_transpose_norm_argmax(
         }
         __syncthreads();
     }
-    // one cross-lane reduction per row: highest value, lowest frequency index on ties
+    // one cross-lane reduction per row: highest value, lowest frequency index on ties (the tie rule of caf_wave.h, spelled
+    // out: through wave_argmax on the array elements this kernel's register moves change)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
 #pragma unroll
@@ -1259,15 +1257,7 @@ __global__ __launch_bounds__(256) void k_transpose_norm_argmax(
         if (partial) {
             float b = v;
             int32_t bidx = lane;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float ov = __shfl_xor(b, o, 64);
-                const int32_t oi = __shfl_xor(bidx, o, 64);
-                if (ov > b || (ov == b && oi < bidx)) {
-                    b = ov;
-                    bidx = oi;
-                }
-            }
+            wave_argmax(b, bidx);
             if (lane == 0) {
                 PeakRec r;
                 r.v = b;
@@ -1465,17 +1455,7 @@ __device__ __forceinline__ void transpose_wave(float* __restrict__ lds, const Pe
         }
         // lanes l, l^16, l^32, l^48 hold the same four delays: highest value, lowest hypothesis on ties
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-#pragma unroll
-            for (int o = 16; o <= 32; o <<= 1) {
-                const float ov = __shfl_xor(bv[k], o, 64);
-                const int32_t oi = __shfl_xor(bi[k], o, 64);
-                if (ov > bv[k] || (ov == bv[k] && oi < bi[k])) {
-                    bv[k] = ov;
-                    bi[k] = oi;
-                }
-            }
-        }
+        for (int k = 0; k < 4; ++k) wave_argmax<32, 16>(bv[k], bi[k]);
         // lanes 0..15 (fq == 0) now hold delays 4*lane .. 4*lane+3
         float* row_max = P->row_max;
         int32_t* row_arg = P->row_arg;
@@ -1497,17 +1477,7 @@ __device__ __forceinline__ void transpose_wave(float* __restrict__ lds, const Pe
             }
         }
         if (partial) {
-#pragma unroll
-            for (int o = 8; o > 0; o >>= 1) {
-                const float ov = __shfl_xor(best, o, 64);
-                const int32_t od = __shfl_xor(bdel, o, 64);
-                const int32_t of = __shfl_xor(bfrq, o, 64);
-                if (ov > best || (ov == best && od < bdel)) {
-                    best = ov;
-                    bdel = od;
-                    bfrq = of;
-                }
-            }
+            wave_argmax<8>(best, bdel, bfrq);
             if (lane == 0) {
                 PeakRec r;
                 r.v = best;
@@ -1601,15 +1571,7 @@ __device__ __attribute__((noinline)) void transpose_wave_f1(const PersistParams*
                         best = x[k];
                         bdel = s4 + k;
                     }
-#pragma unroll
-                for (int o = 8; o > 0; o >>= 1) {
-                    const float ov = __shfl_xor(best, o, 64);
-                    const int32_t od = __shfl_xor(bdel, o, 64);
-                    if (ov > best || (ov == best && od < bdel)) {
-                        best = ov;
-                        bdel = od;
-                    }
-                }
+                wave_argmax<8>(best, bdel);
                 if (hv && (lane & 15) == 0) {
                     PeakRec r;
                     r.v = best;
@@ -1694,6 +1656,8 @@ __device__ __attribute__((noinline)) void reduce_wave_nosurf(const PersistParams
             }
         }
         if (partial) {
+            // (the tie rule of caf_wave.h, spelled out: through wave_argmax the compiler turns this role's updates into
+            // other instructions)
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) {
                 const float ov = __shfl_xor(best, o, 64);

@@ -9,6 +9,7 @@
 // These kernels are HBM-bound elementwise / transpose / reduction work: no MFMA.
 #include "caf_internal.h"
 #include "caf_energy.h"
+#include "caf_wave.h"
 
 namespace caf {
 
@@ -21,12 +22,6 @@ namespace caf {
 constexpr int PFX_THREADS = 256;
 constexpr int PFX_PER_THREAD = 4;
 constexpr int PFX_TILE = PFX_THREADS * PFX_PER_THREAD;
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // Exclusive scan of the tile sums in place, one workgroup: a thread owns up to 16 consecutive entries, so up to 16384
 // tiles take one trip through the wave scan and the two barriers (one entry per thread and a trip per 1024 tiles took
@@ -47,12 +42,7 @@ __global__ __launch_bounds__(1024) void k_scan_tile_sums(double* __restrict__ ti
             v[j] = (j < per && i0 + j < ntiles) ? tile_sums[i0 + j] : 0.0;
             tot += v[j];
         }
-        double incl = tot;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const double u = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += u;
-        }
+        const double incl = wave_scan_inclusive(tot, lane);
         __syncthreads();  // (s_carry of the previous chunk is in place; s_wave is free)
         if (lane == 63) s_wave[wave] = incl;
         __syncthreads();
@@ -115,7 +105,7 @@ __global__ __launch_bounds__(PF_NT) void k_prefix_tiles(const float2* __restrict
         } else {
             double c = 0.0;
             for (int t = threadIdx.x; t < (int)blockIdx.x; t += PF_NT) c += tile_sums[t];
-            c = wave_sum_f64(c);
+            c = wave_sum(c);
             if (lane == 0) s_part[wave] = c;
         }
     }
@@ -126,7 +116,7 @@ __global__ __launch_bounds__(PF_NT) void k_prefix_tiles(const float2* __restrict
 #pragma unroll
         for (int j = 0; j < PF_PER; ++j) t += (double)v[k][j].x * (double)v[k][j].x + (double)v[k][j].y * (double)v[k][j].y;
         tot[k] = t;
-        double in = t;
+        double in = t;  // (wave_scan_inclusive of caf_wave.h, spelled out: through the helper this kernel takes one more VGPR)
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
             const double u = __shfl_up(in, o, 64);
@@ -158,7 +148,7 @@ __global__ __launch_bounds__(PF_NT) void k_prefix_tiles(const float2* __restrict
         const int64_t nchunks = (m + 63) / 64;
 #pragma unroll
         for (int k = 0; k < SUB; ++k) {
-            double c = tot[k];
+            double c = tot[k];  // (offsets ASCENDING over 8 lanes: wave_sum<8> of caf_wave.h would change the float64 bits)
             c += __shfl_xor(c, 1, 64);
             c += __shfl_xor(c, 2, 64);
             c += __shfl_xor(c, 4, 64);
@@ -306,6 +296,8 @@ __global__ __launch_bounds__(MUL_THREADS) void k_spectral_mul(const float2* __re
 // chunks of MAG_F through an LDS tile: reads are MAG_S*8 B contiguous per hypothesis row,
 // writes are MAG_F*4 B contiguous per delay row.
 // ----------------------------------------------------------------------------------------
+// (k_magsq_norm_argmax keeps its own spelling of the tie rule of caf_wave.h: at 256 VGPRs its register allocation
+// changes with every other form of this loop, wave_argmax included)
 struct Best {
     float v;
     int32_t i;
@@ -481,14 +473,7 @@ __global__ __launch_bounds__(1024) void k_peak_reduce(const PeakRec* __restrict_
         const PeakRec r = p[i];
         if (r.v > b.v || (r.v == b.v && r.delay < b.delay)) b = r;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        PeakRec r;
-        r.v = __shfl_xor(b.v, o, 64);
-        r.delay = __shfl_xor(b.delay, o, 64);
-        r.f = __shfl_xor(b.f, o, 64);
-        if (r.v > b.v || (r.v == b.v && r.delay < b.delay)) b = r;
-    }
+    wave_argmax(b.v, b.delay, b.f);
     if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = b;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -539,15 +524,7 @@ __global__ __launch_bounds__(256) void k_rows_peak(const float* __restrict__ row
             b.delay = (int32_t)(shift_start + i);
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(b.v, o, 64);
-        const int32_t od = __shfl_xor(b.delay, o, 64);
-        if (ov > b.v || (ov == b.v && od < b.delay)) {
-            b.v = ov;
-            b.delay = od;
-        }
-    }
+    wave_argmax(b.v, b.delay);
     if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = b;
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -22,6 +22,7 @@
 #include "caf_internal.h"
 #include "caf_energy.h"
 #include "caf_ldsfft.h"
+#include "caf_wave.h"
 
 namespace caf {
 
@@ -73,14 +74,15 @@ __global__ __launch_bounds__((1 << LOGN) / 16 > 256 ? (1 << LOGN) / 16 : 256, 4)
         xr[t] = a;
         xs += (double)a.x * a.x + (double)a.y * a.y;
     }
-    // sum over the lanes of the row slot that share this wave
-    auto wave_sum = [&](double e) {
+    // sum over the lanes of the row slot that share this wave (offsets ASCENDING, unlike wave_sum of caf_wave.h: the
+    // float64 bits of ||x||^2 depend on the order)
+    auto slot_sum = [&](double e) {
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1)
             if (o < NTR) e += __shfl_xor(e, o, 64);
         return e;
     };
-    double xnorm2 = wave_sum(xs);
+    double xnorm2 = slot_sum(xs);
     if (WPR > 1) {
         if (lane == 0) s_e[0][wave] = xnorm2;
         __syncthreads();
@@ -126,7 +128,7 @@ __global__ __launch_bounds__((1 << LOGN) / 16 > 256 ? (1 << LOGN) / 16 : 256, 4)
         }
         // window energy: lanes of the wave by shuffles; across the waves of a wide row through LDS, published by the
         // barrier that ends the first pass
-        double e = wave_sum(es);
+        double e = slot_sum(es);
         if (WPR > 1 && lane == 0) s_e[it & 1][wave] = e;
         pd_fft<LOGN>(buf, tw, lo, v);
         if (WPR > 1) {
@@ -182,13 +184,7 @@ __global__ __launch_bounds__((1 << LOGN) / 16 > 256 ? (1 << LOGN) / 16 : 256, 4)
             // zero-energy window -- reports (NaN, 0): the reference's pmax / ||cutout||^2 / 0, xcorrRoutines.py:527-528,
             // IppXcorrFFT.cpp:174; a zero ROW of the out-of-range rule has inv = 0, all values +0, key != 0: (0, 0))
             unsigned long long key = bv < 0.f ? 0ull : (((unsigned long long)__float_as_uint(bv) << 32) | (uint32_t)~bi);
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                if (o < NTR) {
-                    const unsigned long long ok = __shfl_xor(key, o, 64);
-                    key = ok > key ? ok : key;
-                }
-            }
+            key = wave_max<(NTR < 64 ? NTR : 64)>(key);
             if (WPR > 1) {
                 if (lane == 0) s_key[it & 1][wave] = key;
                 __syncthreads();
@@ -301,17 +297,12 @@ __global__ __launch_bounds__(1024) void k_block_spectra(const float2* __restrict
             for (int j = 0; j < 16; ++j) tot += s_p[17 * lo + j];
             const int lane = lo & 63, wave = lo >> 6;
             {   // energies of the block's 64-sample chunks (4 lanes x 16 samples), plain sums: for windows the prefix cannot resolve
-                double c4 = tot;
+                double c4 = tot;  // (offsets ASCENDING over 4 lanes: wave_sum<4> of caf_wave.h would change the float64 bits)
                 c4 += __shfl_xor(c4, 1, 64);
                 c4 += __shfl_xor(c4, 2, 64);
                 if ((lane & 3) == 0) s_chunk[lo >> 2] = c4;
             }
-            double incl = tot;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const double u = __shfl_up(incl, o, 64);
-                if (lane >= o) incl += u;
-            }
+            const double incl = wave_scan_inclusive(tot, lane);
             if (lane == 63) s_wtot[wave] = incl;
             double base = __shfl_up(incl, 1, 64);  // exclusive value from the neighbour (no inclusive-minus-own)
             if (lane == 0) base = 0.0;

@@ -13,6 +13,7 @@
 // All are HBM-bound (or, for long FIRs, VALU-bound) elementwise / sliding-window work.
 #include "caf_internal.h"
 #include "caf_energy.h"
+#include "caf_wave.h"
 
 namespace caf {
 
@@ -45,8 +46,7 @@ __global__ __launch_bounds__(256) void k_cutout_sumsq(const float2* __restrict__
         const float2 a = x[i];
         e += (double)a.x * a.x + (double)a.y * a.y;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o, 64);
+    e = wave_sum(e);
     if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = e;
     __syncthreads();
     if (threadIdx.x == 0) parts[blockIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);
@@ -165,15 +165,7 @@ __global__ __launch_bounds__(256) void k_rows_argmax(const float2* __restrict__ 
             bi = (uint32_t)t;
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const uint32_t oi = __shfl_xor(bi, o, 64);
-        if (ov > bv || (ov == bv && oi < bi)) {
-            bv = ov;
-            bi = oi;
-        }
-    }
+    wave_argmax(bv, bi);
     if ((threadIdx.x & 63) == 0) {
         s_v[threadIdx.x >> 6] = bv;
         s_i[threadIdx.x >> 6] = bi;
@@ -228,15 +220,7 @@ __global__ __launch_bounds__(256) void k_rows_argmax_wave(const float2* __restri
         offer(make_float2(q.z, q.w), head + 2 * p + 1);
     }
     if (len > head && ((len - head) & 1) && lane == 0) offer(zr[len - 1], len - 1);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const uint32_t oi = __shfl_xor(bi, o, 64);
-        if (ov > bv || (ov == bv && oi < bi)) {
-            bv = ov;
-            bi = oi;
-        }
-    }
+    wave_argmax(bv, bi);
     if (lane == 0) {
         if (bv < 0.f) {  // empty or all-NaN row: see k_rows_argmax
             bv = (nan_empty && len > 0) ? __builtin_nanf("") : 0.f;
@@ -269,11 +253,7 @@ __global__ __launch_bounds__(256) void k_rows_argmax_part(const float2* __restri
         }
     }
     unsigned long long key = bv < 0.f ? 0ull : (((unsigned long long)__float_as_uint(bv)) << 32) | (0xFFFFFFFFu - bi);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long ok = __shfl_xor(key, o, 64);
-        key = ok > key ? ok : key;
-    }
+    key = wave_max(key);
     if ((threadIdx.x & 63) == 0) s_k[threadIdx.x >> 6] = key;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -313,15 +293,7 @@ __global__ __launch_bounds__(256) void k_argmax3d_u32(const uint32_t* __restrict
             bi = (uint32_t)t;
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t ov = __shfl_xor(bv, o, 64);
-        const uint32_t oi = __shfl_xor(bi, o, 64);
-        if (ov > bv || (ov == bv && oi < bi)) {
-            bv = ov;
-            bi = oi;
-        }
-    }
+    wave_argmax(bv, bi);
     if ((threadIdx.x & 63) == 0) {
         s_v[threadIdx.x >> 6] = bv;
         s_i[threadIdx.x >> 6] = bi;
@@ -369,8 +341,7 @@ __global__ __launch_bounds__(MA_THREADS) void k_moving_sum_prefix(const float* _
 #pragma unroll
     for (int j = 0; j < MA_PER_THREAD; ++j)
         if (base + j < n) acc += (double)x[base + j];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    acc = wave_sum(acc);
     if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -394,12 +365,7 @@ __global__ __launch_bounds__(MA_THREADS) void k_moving_prefix_write(const float*
         p[j] = tot;
         if (base + j < n) tot += (double)x[base + j];
     }
-    double incl = tot;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const double u = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += u;
-    }
+    const double incl = wave_scan_inclusive(tot, lane);
     if (lane == 63) s_wave[wave] = incl;
     __syncthreads();
     double off = tile_off[blockIdx.x] + (incl - tot);
@@ -457,12 +423,7 @@ __global__ __launch_bounds__(MAT_NT) void k_moving_tile(const float* __restrict_
     double tot = 0.0;
 #pragma unroll
     for (int k = 0; k < MAT_PER; ++k) pl[k] = (tot += (double)v[k]);
-    double incl = tot;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const double u = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += u;
-    }
+    const double incl = wave_scan_inclusive(tot, lane);
     if (lane == 63) s_wave[wave] = incl;
     if (threadIdx.x == 0) s_p[0] = 0.0;
     __syncthreads();
@@ -552,11 +513,8 @@ __global__ __launch_bounds__(256) void k_multi_template_dot(const float2* __rest
                 ar += a.x * b.x - a.y * b.y;
                 ai += a.x * b.y + a.y * b.x;
             }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                ar += __shfl_xor(ar, o, 64);
-                ai += __shfl_xor(ai, o, 64);
-            }
+            ar = wave_sum(ar);
+            ai = wave_sum(ai);
             const int64_t s = start + k0 + k;
             int64_t e1 = s + L;
             if (e1 > xlen) e1 = xlen;
@@ -749,9 +707,7 @@ __global__ __launch_bounds__(LM_NT) void k_local_max_flags(const float* __restri
         if (base + j < n && v[j] > min_height && v[j] > l && v[j] > r) mask |= 1u << j;
     }
     masks[(int64_t)blockIdx.x * LM_NT + threadIdx.x] = (uint16_t)mask;
-    int c = __popc(mask);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    const int c = wave_sum(__popc(mask));
     if (lane == 0) s_w[wave] = c;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -772,12 +728,7 @@ __global__ __launch_bounds__(1024) void k_local_max_scan(int32_t* __restrict__ t
     for (int64_t c0 = 0; c0 < ntiles; c0 += 1024) {
         const int64_t t = c0 + threadIdx.x;
         const int v = t < ntiles ? tile_count[t] : 0;
-        int incl = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int u = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += u;
-        }
+        const int incl = wave_scan_inclusive(v, lane);
         if (lane == 63) s_wave[wave] = incl;
         __syncthreads();
         int off = s_base;
@@ -808,8 +759,7 @@ __global__ __launch_bounds__(LM_NT) void k_local_max_write(const uint16_t* __res
         if (mine == 0 && !last) return;  // (uniform)
         int c = 0;
         for (int t = threadIdx.x; t < (int)blockIdx.x; t += LM_NT) c += tile_count[t];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+        c = wave_sum(c);
         if (lane == 0) s_w[wave] = c;
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -826,12 +776,7 @@ __global__ __launch_bounds__(LM_NT) void k_local_max_write(const uint16_t* __res
     }
     uint32_t mask = masks[(int64_t)blockIdx.x * LM_NT + threadIdx.x];
     const int c = __popc(mask);
-    int incl = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int u = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += u;
-    }
+    const int incl = wave_scan_inclusive(c, lane);
     if (lane == 63) s_w[wave] = incl;
     __syncthreads();
     int off = before + (incl - c);
@@ -1564,11 +1509,8 @@ __global__ __launch_bounds__(256) void k_steer_dot(const float2* __restrict__ ve
         re += (double)v.x * s.x + (double)v.y * s.y;  // v * conj(s)
         im += (double)v.y * s.x - (double)v.x * s.y;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        re += __shfl_xor(re, o, 64);
-        im += __shfl_xor(im, o, 64);
-    }
+    re = wave_sum(re);
+    im = wave_sum(im);
     if ((threadIdx.x & 63) == 0) {
         s_re[threadIdx.x >> 6] = re;
         s_im[threadIdx.x >> 6] = im;

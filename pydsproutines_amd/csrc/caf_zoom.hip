@@ -8,6 +8,7 @@
 //   k_zoom_finish  assembles the result table
 // Nothing but the final k-row table ever needs to leave the device, and the host never waits in between.
 #include "caf_internal.h"
+#include "caf_wave.h"
 
 namespace caf {
 
@@ -36,15 +37,7 @@ __global__ __launch_bounds__(1024) void k_zoom_topk(const float* __restrict__ tr
                 bi = i;
             }
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(bv, o, 64);
-            const int32_t oi = __shfl_xor(bi, o, 64);
-            if (ov > bv || (ov == bv && oi < bi)) {
-                bv = ov;
-                bi = oi;
-            }
-        }
+        wave_argmax(bv, bi);
         if ((tid & 63) == 0) {
             s_v[tid >> 6] = bv;
             s_i[tid >> 6] = bi;
@@ -91,8 +84,7 @@ __global__ __launch_bounds__(256) void k_zoom_rows(const float2* __restrict__ rx
         const float2 a = w[t];
         e += (double)a.x * a.x + (double)a.y * a.y;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o, 64);
+    e = wave_sum(e);
     if ((threadIdx.x & 63) == 0) s_e[threadIdx.x >> 6] = e;
     __syncthreads();
     e = s_e[0] + s_e[1] + s_e[2] + s_e[3];
