@@ -325,36 +325,24 @@ __global__ __launch_bounds__(256) void k_magnsq(const TIn* __restrict__ x, int64
 
 // ---------------------------------------------------------------------------------------
 // Causal moving sum / mean of float32 (zeros in front), double accumulation (filter.cu:324-339).
-// Each workgroup produces MA_TILE outputs from an LDS-staged window; a thread sums its first
-// window directly and then slides, re-anchoring every MA_PER_THREAD outputs.
+// Two forms: float64 prefixes per MA_TILE-sample tile in global memory (any window), and k_moving_tile below
+// (windows up to MAT_MAXL, one launch).
 // ---------------------------------------------------------------------------------------
 constexpr int MA_THREADS = 256;
 constexpr int MA_PER_THREAD = 16;
 constexpr int MA_TILE = MA_THREADS * MA_PER_THREAD;
 
-__global__ __launch_bounds__(MA_THREADS) void k_moving_sum_prefix(const float* __restrict__ x, int64_t n,
-                                                                  double* __restrict__ tile_sums) {
-    // per-tile sums of x (float64) for the two-level prefix used by the moving sum
-    __shared__ double s_part[MA_THREADS / 64];
-    const int64_t base = (int64_t)blockIdx.x * MA_TILE + (int64_t)threadIdx.x * MA_PER_THREAD;
-    double acc = 0.0;
-#pragma unroll
-    for (int j = 0; j < MA_PER_THREAD; ++j)
-        if (base + j < n) acc += (double)x[base + j];
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int w = 0; w < MA_THREADS / 64; ++w) t += s_part[w];
-        tile_sums[blockIdx.x] = t;
-    }
-}
-
-// prefix[i] = sum_{j<i} x[j] (float64), i in [0, n]
+// The long-window form (L > MAT_MAXL, or more rows than one launch of k_moving_tile takes) keeps no prefix of the whole
+// record: a difference of two entries of such a prefix is off by 2^-53 of everything in front of the window, which is
+// the whole window where the record is far louder somewhere before it.  local[i] = the sum of x over [tile start, i) of
+// the MA_TILE-sample tile that holds index i (i in [0, n]) and tile_sums[t] = the total of tile t; a window is then
+//   the tail of its first tile (total - local: a difference within ONE tile) + the whole tiles between + the head of its last,
+// so that nothing is subtracted across more than MA_TILE samples -- what the upstream kernel's per-thread re-anchoring
+// achieves (filter.cu:324-339).  The tile form's reach was not raised instead: its LDS prefix holds span = window + outputs
+// doubles, so the outputs per workgroup shrink as the window grows and no span serves every window length.
 __global__ __launch_bounds__(MA_THREADS) void k_moving_prefix_write(const float* __restrict__ x, int64_t n,
-                                                                    const double* __restrict__ tile_off,
-                                                                    double* __restrict__ prefix) {
+                                                                    double* __restrict__ tile_sums,
+                                                                    double* __restrict__ local) {
     __shared__ double s_wave[MA_THREADS / 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t base = (int64_t)blockIdx.x * MA_TILE + (int64_t)threadIdx.x * MA_PER_THREAD;
@@ -368,20 +356,29 @@ __global__ __launch_bounds__(MA_THREADS) void k_moving_prefix_write(const float*
     const double incl = wave_scan_inclusive(tot, lane);
     if (lane == 63) s_wave[wave] = incl;
     __syncthreads();
-    double off = tile_off[blockIdx.x] + (incl - tot);
+    double off = incl - tot;
     for (int w = 0; w < wave; ++w) off += s_wave[w];
 #pragma unroll
     for (int j = 0; j < MA_PER_THREAD; ++j)
-        if (base + j <= n) prefix[base + j] = off + p[j];
+        if (base + j <= n) local[base + j] = off + p[j];
+    if (threadIdx.x == MA_THREADS - 1) tile_sums[blockIdx.x] = off + tot;  // (the same additions as an entry one past the tile)
 }
 
-// out[i] = (prefix[i+1] - prefix[max(0, i+1-L)]) [/ L]
-__global__ __launch_bounds__(256) void k_moving_from_prefix(const double* __restrict__ prefix, int64_t n, int32_t L,
-                                                            int32_t sum_instead, float* __restrict__ out) {
+// out[i] = sum x[max(0, i+1-L) .. i] [/ L] from the tile-local prefixes and the tile totals
+__global__ __launch_bounds__(256) void k_moving_from_prefix(const double* __restrict__ local, const double* __restrict__ tile_sums,
+                                                            int64_t n, int32_t L, int32_t sum_instead, float* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const int64_t lo = i + 1 - L;
-    const double s = prefix[i + 1] - prefix[lo < 0 ? 0 : lo];
+    const int64_t hi = i + 1, lo = hi > L ? hi - L : 0;
+    const int64_t ta = lo / MA_TILE, tb = hi / MA_TILE;
+    double s;
+    if (ta == tb) {
+        s = local[hi] - local[lo];
+    } else {
+        s = tile_sums[ta] - local[lo];
+        for (int64_t t = ta + 1; t < tb; ++t) s += tile_sums[t];
+        s += local[hi];
+    }
     out[i] = sum_instead ? (float)s : (float)(s / (double)L);
 }
 
@@ -477,6 +474,18 @@ __global__ __launch_bounds__(256) void k_complex_moving_sum(const float2* __rest
 // ---------------------------------------------------------------------------------------
 constexpr int MT_SLIDES = 64;
 
+// 1 / ||x[s : s+L]||^2 of a slide: the energy from window_energy (caf_energy.h: the prefix difference where it is resolved,
+// the direct sum where it is not -- a window behind a louder stretch of the record), float64 up to and including the one
+// division.  A window without energy gives 0, so that every template scores 0 and the slide reports (0, 0.0): the
+// reference's all-zero column.
+__device__ __forceinline__ float mt_inv_energy(const double* __restrict__ prefix, const float2* __restrict__ x, int64_t xlen,
+                                               int64_t s, int32_t L) {
+    int64_t e1 = s + L;
+    if (e1 > xlen) e1 = xlen;
+    const double e = window_energy(prefix, x, xlen, s, e1);
+    return e > 0.0 ? (float)(1.0 / e) : 0.f;
+}
+
 __global__ __launch_bounds__(256) void k_multi_template_dot(const float2* __restrict__ tm, const float* __restrict__ te,
                                                             int32_t ntm, int32_t L, const float2* __restrict__ x,
                                                             int64_t xlen, const double* __restrict__ prefix,
@@ -491,10 +500,12 @@ __global__ __launch_bounds__(256) void k_multi_template_dot(const float2* __rest
                      [&](int t, float2 v) { s_xs[t] = v; });
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     constexpr int PER_WAVE = MT_SLIDES / 4;
-    float bv[PER_WAVE];
+    float bv[PER_WAVE], ie[PER_WAVE];  // ie: 1 / ||x[k:k+L]||^2 per slide (mt_inv_energy)
     int32_t bi[PER_WAVE];
 #pragma unroll
     for (int r = 0; r < PER_WAVE; ++r) {
+        const int64_t k = k0 + wave * PER_WAVE + r;
+        ie[r] = k < nslides ? mt_inv_energy(prefix, x, xlen, start + k, L) : 0.f;
         bv[r] = 0.f;
         bi[r] = 0;
     }
@@ -515,11 +526,7 @@ __global__ __launch_bounds__(256) void k_multi_template_dot(const float2* __rest
             }
             ar = wave_sum(ar);
             ai = wave_sum(ai);
-            const int64_t s = start + k0 + k;
-            int64_t e1 = s + L;
-            if (e1 > xlen) e1 = xlen;
-            const float e = (float)(prefix[e1] - prefix[s]);
-            const float v = (ar * ar + ai * ai) * inv_te / e;
+            const float v = (ar * ar + ai * ai) * inv_te * ie[r];
             if (v > bv[r]) {
                 bv[r] = v;
                 bi[r] = i;
@@ -563,18 +570,11 @@ __global__ __launch_bounds__(256) void k_multi_template_dot_rt(const float2* __r
     stage_batched<8>(span, [&](int t) { const int64_t j = start + k0 + t; return (j < xlen) ? x[j] : make_float2(0.f, 0.f); },
                      [&](int t, float2 v) { s_xs[(t % MTR_R) * pitch + t / MTR_R] = v; });
     const int l0 = threadIdx.x * MTR_R;
-    float ewin[MTR_R], bv[MTR_R];  // ewin: ||x[k:k+L]||^2 per slide (1 for slides past the end)
+    float ie[MTR_R], bv[MTR_R];  // ie: 1 / ||x[k:k+L]||^2 per slide (mt_inv_energy; 0 for slides past the end)
     int32_t bi[MTR_R];
 #pragma unroll
     for (int r = 0; r < MTR_R; ++r) {
-        const int64_t s = start + k0 + l0 + r;
-        float e = 1.f;
-        if (k0 + l0 + r < nslides) {
-            int64_t e1 = s + L;
-            if (e1 > xlen) e1 = xlen;
-            e = (float)(prefix[e1] - prefix[s]);
-        }
-        ewin[r] = e;
+        ie[r] = k0 + l0 + r < nslides ? mt_inv_energy(prefix, x, xlen, start + k0 + l0 + r, L) : 0.f;
         bv[r] = 0.f;
         bi[r] = 0;
     }
@@ -606,7 +606,7 @@ __global__ __launch_bounds__(256) void k_multi_template_dot_rt(const float2* __r
         const float inv_te = 1.0f / te[i];
 #pragma unroll
         for (int r = 0; r < MTR_R; ++r) {
-            const float v = (acc[r].x * acc[r].x + acc[r].y * acc[r].y) * inv_te / ewin[r];
+            const float v = (acc[r].x * acc[r].x + acc[r].y * acc[r].y) * inv_te * ie[r];
             if (v > bv[r]) {
                 bv[r] = v;
                 bi[r] = i;
@@ -1582,15 +1582,11 @@ void launch_dot_tones(double f0, double fstep, int32_t num_freqs, int64_t len, c
 
 int64_t moving_num_tiles(int64_t n) { return (n + 1 + MA_TILE - 1) / MA_TILE; }
 
-void scan_tiles(double* tile_sums, int64_t ntiles, hipStream_t st);  // caf_kernels.hip
-
 void launch_moving_average(const float* x, int64_t n, int32_t L, int32_t sum_instead, double* tile_sums,
                            double* prefix, float* out, hipStream_t st) {
     const int64_t nt = moving_num_tiles(n);
-    hipLaunchKernelGGL(k_moving_sum_prefix, dim3((unsigned)nt), dim3(MA_THREADS), 0, st, x, n, tile_sums);
-    scan_tiles(tile_sums, nt, st);
     hipLaunchKernelGGL(k_moving_prefix_write, dim3((unsigned)nt), dim3(MA_THREADS), 0, st, x, n, tile_sums, prefix);
-    hipLaunchKernelGGL(k_moving_from_prefix, dim3(cdiv(n, 256)), dim3(256), 0, st, prefix, n, L, sum_instead, out);
+    hipLaunchKernelGGL(k_moving_from_prefix, dim3(cdiv(n, 256)), dim3(256), 0, st, prefix, tile_sums, n, L, sum_instead, out);
 }
 
 void launch_complex_moving_sum(const float2* x, int64_t n, int32_t L, float* out, hipStream_t st) {

@@ -717,3 +717,365 @@ def synthetic_traces(S):
     t[[50, 150, 250]] = np.float32([0.5, 0.75, 0.25])
     out["height_equal"] = (t, 0.5, 8)
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# The rows toolbox (csrc/caf_rows.hip): sliding normalised product, multi-template dot, moving sums, row and column maxima
+# and the elementwise kernels.  Every reference below is a DIRECT float64 / complex128 sum -- no difference of running sums
+# anywhere, which is what oracle.kernels.movingAverage / movingComplexSum are and why they are not the reference here -- and
+# every bound is derived from the arithmetic the kernel does ("The rows toolbox"); none is calibrated on a GPU.
+
+EPS64 = 2.0 ** -53
+
+# Lengths D of the longest chain of float64 additions behind one prefix entry, read off the kernels:
+#   k_prefix_tiles (the |x|^2 prefix of window_energy): 8 samples per thread + 6 steps of the wave scan + 4 wave totals of the
+#   tile + the totals of the tiles in front, added by the tile itself (1 per thread up to 256 tiles, 6 steps of wave_sum, 4 partials)
+D_ENERGY = 8 + 6 + 4 + (1 + 6 + 4)
+#   k_moving_tile: 8 samples per thread + 6 (wave scan) + 3 (wave totals in front) + 1 (offset + own run)
+D_MOVING_TILE = 8 + 6 + 3 + 1
+#   k_moving_prefix_write: 16 samples per thread + 6 + 3 + 1; there is no scan across tiles (the prefixes are per tile)
+D_MOVING_PREFIX = 16 + 6 + 3 + 1
+MOVING_SPAN = 4096  # the largest span any form may cancel over: MA_TILE, and twice MAT_SPAN
+
+
+def d_moving(L):
+    """D of the moving sum: two prefix entries (or a tile total and an entry) of at most D_MOVING_PREFIX additions each, their
+    difference, and one addition per whole tile between the window's ends plus the last tile's head."""
+    return 2 * max(D_MOVING_TILE, D_MOVING_PREFIX) + 1 + -(-int(L) // MOVING_SPAN) + 1
+
+
+def d_complex_moving(L):
+    """k_complex_moving_sum: L samples added one after another, then at most 7 slides of (new - old) + sum: 2 each."""
+    return int(L) + 2 * 8
+
+
+def rows_record(rng, n, loud=None, quiet=None, zeros=None, base=None):
+    """complex64 unit noise (or `base`) of n samples with the stretch loud = (a, b) scaled by 2^10, quiet = (a, b) by 2^-20 (both
+    exact) and zeros = (a, b) set to exact zeros; None leaves a stretch out."""
+    x = fe_noise(rng, n) if base is None else np.asarray(base, np.complex64).copy()
+    assert x.size == n
+    if loud is not None:
+        x[loud[0] : loud[1]] *= np.float32(2.0 ** 10)
+    if quiet is not None:
+        x[quiet[0] : quiet[1]] *= np.float32(2.0 ** -20)
+    if zeros is not None:
+        x[zeros[0] : zeros[1]] = 0
+    return x
+
+
+def _windows(a, L, lo, hi):
+    """rows lo .. hi - 1 of sliding_window_view(a, L) (a view)."""
+    return np.lib.stride_tricks.sliding_window_view(a, L)[lo:hi]
+
+
+def window_sums64(a, L, chunk_elems=1 << 22):
+    """sum a[k : k + L] for every k, float64 / complex128, each window added up on its own (NumPy's pairwise sum)."""
+    a = _as64(a)
+    out = np.empty(a.size - L + 1, a.dtype)
+    step = max(1, chunk_elems // L)
+    for k in range(0, out.size, step):
+        out[k : k + step] = _windows(a, L, k, min(out.size, k + step)).sum(axis=1)
+    return out
+
+
+def _energy_share(y, a, b, E):
+    """eps_E per window [a_i, b_i): the share of the window energy's error in units of 2^-24 of the result.  window_energy
+    (caf_energy.h) takes prefix[b] - prefix[a] only where it exceeds 2^-30 prefix[b]; each entry carries at most D_ENERGY
+    roundings of at most 2^-53 prefix[b], and 1 / sqrt(E) moves by half the relative error of E:
+        eps_E = 2^24 * D_ENERGY * 2^-53 * prefix[b] / (2 E)     (at most D_ENERGY: 29)
+    Where E <= 2^-31 prefix[b] the difference is never taken (a factor 2 of margin for the kernel's own rounding of the
+    comparison) and the direct sum's error, L 2^-53, is nothing: eps_E = 0."""
+    p = _prefix(y)
+    pb = p[np.asarray(b, np.int64)]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        eps = np.where(E > 2.0 ** -31 * pb, 2.0 ** 24 * D_ENERGY * EPS64 * pb / (2 * E), 0.0)
+    return np.where(E > 0, eps, 0.0)
+
+
+def sliding_multiply64(x, y, start, rows, coef=None, step=1, zero_oor=False):
+    """(ref, bound), both (rows, xlen): z[i][t] = x[t] y[s_i + t] / (sqrt(E_i) coef), s_i = start + i step, E_i the energy of
+    y[s_i : s_i + xlen] clipped to y (samples outside read as zero), coef = ||x|| by default; complex128, E_i a direct sum.
+    A window without energy gives NaN where it reads y and 0 where it reads past the end; with zero_oor a window that leaves y
+    gives a row of exact zeros.
+
+    Bound per element: (8 + eps_E) 2^-24 |x_t| |y_j| / (sqrt(E) coef).  On the complex modulus: the float32 product x_t y_j is
+    two products and an add per component, with or without FMA (sqrt(5) < 3 units, Brent et al. 2007), the float32 `inv` is one
+    rounding of a float64 value, the two multiplies by it one unit each of the modulus: under 6, 8 with the second-order terms
+    and the float64 sqrt and division.  eps_E: _energy_share."""
+    x64, y64 = np.asarray(x).astype(np.complex128), np.asarray(y).astype(np.complex128)
+    n, m = x64.size, y64.size
+    if coef is None:
+        coef = float(np.sqrt(np.sum(np.abs(x64) ** 2)))
+    s = start + step * np.arange(rows, dtype=np.int64)
+    j = s[:, None] + np.arange(n)[None, :]
+    inside = (j >= 0) & (j < m)
+    w = np.where(inside, y64[np.clip(j, 0, m - 1)], 0)
+    E = np.sum(np.abs(w) ** 2, axis=1)
+    eps = _energy_share(y, np.clip(s, 0, m), np.clip(s + n, 0, m), E)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        g = 1.0 / (np.sqrt(E) * coef)
+        ref = x64[None, :] * w * g[:, None]
+        bound = (8 + eps)[:, None] * EPS32 * np.abs(x64)[None, :] * np.abs(w) * g[:, None]
+    dead = E == 0
+    ref[dead] = np.where(inside[dead], np.nan, 0)
+    bound[dead] = 0
+    if zero_oor:
+        oor = (s < 0) | (s + n > m)
+        ref[oor] = 0
+        bound[oor] = 0
+    return ref, bound
+
+
+def sliding_multiply32(x, y, start, rows, coef=None):
+    """float32 stand-in of the kernel: complex64 products, inv = float32(1 / (sqrt(E) coef)) from a float64 direct energy."""
+    x, y = np.asarray(x, np.complex64), np.asarray(y, np.complex64)
+    n = x.size
+    ye = np.concatenate((y, np.zeros(n, np.complex64)))
+    if coef is None:
+        coef = float(np.sqrt(np.sum(np.abs(x.astype(np.complex128)) ** 2)))
+    w = _windows(ye, n, start, start + rows)
+    E = np.sum(np.abs(w.astype(np.complex128)) ** 2, axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        inv = (1.0 / (np.sqrt(E) * coef)).astype(np.float32)
+        out = (x[None, :] * w) * inv[:, None]
+    assert out.dtype == np.complex64
+    return out
+
+
+def multi_template64(x, templates, te, start, nslides):
+    """(qf2, bound), both (nslides, T) float64: |d|^2 / (te_i E_k), d = sum_t T_i[t] x[k + t] in complex128 (no conjugation), E_k
+    the direct float64 energy of x[k : k + L], te the float32 energies the wrapper hands to the kernel.  E_k = 0 gives qf2 = 0 for
+    every template: the reference's all-zero column, reported as (0, 0.0).
+
+    With A = sum_t |T_i[t]| |x[k + t]|:  delta = sqrt(2) (L + 2) 2^-24 A bounds the float32 sum of L products in any order, with or
+    without FMA (direct_unit's argument, sqrt(2) from the two components), so |d_got|^2 is within 2 |d| delta + delta^2 of |d|^2; the
+    normalisation rounds six times -- ar^2, ai^2 and their sum count 2 on the sum, 1 / te, the product by it, the float32 of
+    1 / E and the product by it -- and 1 / E moves by the whole relative error of E (2 eps_E in the units of _energy_share):
+        |qf2_got - qf2_ref| <= (2 |d| delta + delta^2) / (te E) + (6 + 2 eps_E) 2^-24 qf2_ref."""
+    x = np.asarray(x)
+    tm = np.atleast_2d(np.asarray(templates))
+    T, L = tm.shape
+    te = np.asarray(te, np.float64)
+    x64, ax = x.astype(np.complex128), np.abs(x.astype(np.complex128))
+    t64, at = tm.astype(np.complex128).T.copy(), np.abs(tm.astype(np.complex128)).T.copy()
+    d = np.empty((nslides, T), np.complex128)
+    A = np.empty((nslides, T))
+    E = np.empty(nslides)
+    step = max(1, (1 << 22) // L)
+    for k in range(0, nslides, step):
+        k1 = min(nslides, k + step)
+        d[k:k1] = _windows(x64, L, start + k, start + k1) @ t64
+        wa = _windows(ax, L, start + k, start + k1)
+        A[k:k1] = wa @ at
+        E[k:k1] = np.sum(wa * wa, axis=1)
+    s = start + np.arange(nslides, dtype=np.int64)
+    eps = _energy_share(x, s, s + L, E)
+    delta = np.sqrt(2.0) * (L + 2) * EPS32 * A
+    with np.errstate(divide="ignore", invalid="ignore"):
+        den = te[None, :] * E[:, None]
+        q = np.abs(d) ** 2 / den
+        b = (2 * np.abs(d) * delta + delta ** 2) / den + (6 + 2 * eps)[:, None] * EPS32 * q
+    q[E == 0] = 0
+    b[E == 0] = 0
+    return q, b
+
+
+def multi_template_decided(q, b):
+    """(winner, decided): the reference's template per slide (lowest index on ties, 0 for an all-zero column) and whether the
+    top-two gap across templates exceeds the sum of the two templates' bounds (always, for one template)."""
+    win = np.argmax(q, axis=1)
+    if q.shape[1] == 1:
+        return win, np.ones(q.shape[0], bool)
+    r = np.arange(q.shape[0])
+    q2 = q.copy()
+    q2[r, win] = -np.inf
+    sec = np.argmax(q2, axis=1)
+    return win, (q[r, win] - q[r, sec]) > (b[r, win] + b[r, sec])
+
+
+def multi_template32(x, templates, te, start, nslides):
+    """float32 stand-in: complex64 dot products (BLAS order), float32 normalisation as the kernel's; (idx, qf2)."""
+    x, tm = np.asarray(x, np.complex64), np.atleast_2d(np.asarray(templates, np.complex64))
+    T, L = tm.shape
+    q = np.empty((nslides, T), np.float32)
+    step = max(1, (1 << 22) // L)
+    inv_te = np.float32(1) / np.asarray(te, np.float32)
+    for k in range(0, nslides, step):
+        k1 = min(nslides, k + step)
+        w = _windows(x, L, start + k, start + k1)
+        d = w @ tm.T.copy()
+        assert d.dtype == np.complex64
+        E = np.sum(np.abs(w.astype(np.complex128)) ** 2, axis=1)
+        with np.errstate(divide="ignore"):
+            ie = np.where(E > 0, 1.0 / E, 0.0).astype(np.float32)
+        q[k:k1] = (d.real * d.real + d.imag * d.imag) * inv_te[None, :] * ie[:, None]
+    idx = np.argmax(q, axis=1)
+    return idx.astype(np.int32), q[np.arange(nslides), idx]
+
+
+def moving_sum64(x, L, mean=False):
+    """out[i] = sum x[max(0, i + 1 - L) .. i] (/ L with mean), float64, every window added up on its own."""
+    x = np.asarray(x, np.float64)
+    s = window_sums64(np.concatenate((np.zeros(L - 1), x)), L)
+    return s / L if mean else s
+
+
+def moving_bound(x, L, ref, mean=False):
+    """|got - ref| <= 2^-24 |ref| + D 2^-53 S_i / (L or 1), S_i = sum |x_j| over j in (i - L - 4096, i], D = d_moving(L): the float32
+    cast of the result, and D float64 roundings each of at most 2^-53 of the moduli a kernel may touch for output i when it
+    re-anchors its sums at least every MOVING_SPAN samples, as upstream's does (filter.cu:324-339).  The bound is NOT stated on a
+    prefix of the whole record.  Where every sample in that range is zero it is zero: the output is exactly zero."""
+    S = moving_sum64(np.abs(np.asarray(x, np.float64)), L + MOVING_SPAN)
+    return EPS32 * np.abs(ref) + d_moving(L) * EPS64 * S / (L if mean else 1)
+
+
+def moving_local(x, L, mean=False, tile=MOVING_SPAN):
+    """Stand-in of a locally anchored kernel: float64 cumulative sums per `tile` samples, a window = tail + whole tiles + head,
+    result cast to float32."""
+    x = np.asarray(x, np.float64)
+    n = x.size
+    nt = n // tile + 1
+    pad = np.zeros(nt * tile)
+    pad[:n] = x
+    c = np.cumsum(pad.reshape(nt, tile), axis=1)
+    tot = c[:, -1].copy()
+    local = np.concatenate((np.zeros((nt, 1)), c[:, :-1]), axis=1).reshape(-1)  # sum over [tile start, i)
+    out = np.empty(n)
+    for i in range(n):
+        hi, lo = i + 1, max(0, i + 1 - L)
+        ta, tb = lo // tile, hi // tile
+        out[i] = local[hi] - local[lo] if ta == tb else (tot[ta] - local[lo]) + tot[ta + 1 : tb].sum() + local[hi]
+    return (out / L if mean else out).astype(np.float32)
+
+
+def complex_moving_sum64(x, L):
+    """(|s|^2, bound), valid outputs only: s_o = sum x[o : o + L] in complex128, each on its own.
+
+    The kernel adds L samples one after another in float64 per component and slides at most 7 times from an anchor at o & ~7:
+    delta_s = sqrt(2) d_complex_moving(L) 2^-53 sum |x_j| over j in [o - 7, o + L)  (span L + 7 <= L + 8), and with the float64
+    squares and the float32 cast  |got - |s|^2| <= 3 2^-24 |s|^2 + 2 |s| delta_s + delta_s^2."""
+    x = np.asarray(x)
+    s = window_sums64(x.astype(np.complex128), L)
+    ax = np.abs(x.astype(np.complex128))
+    S = window_sums64(np.concatenate((np.zeros(7), ax)), L + 7)
+    ds = np.sqrt(2.0) * d_complex_moving(L) * EPS64 * S
+    p = np.abs(s) ** 2
+    return p, 3 * EPS32 * p + 2 * np.abs(s) * ds + ds ** 2
+
+
+def rows_absq64(z, scale=1.0):
+    """|z|^2 * scale in float64 (any shape)."""
+    z = np.asarray(z)
+    return (z.real.astype(np.float64) ** 2 + z.imag.astype(np.float64) ** 2) * float(scale)
+
+
+def check_rowmax(got_arg, got_max, v, root=False, units=3, axis=1, empty=(0.0, 0)):
+    """Row (axis 1) or column (axis 0) maxima against v = the float64 values the kernel compares (rows_absq64, or their roots).
+    The value is within `units` 2^-24 of the reference's maximum -- |z|^2 scale in float32: two squares and an add are 2 units on a
+    sum of positives, the scale 1 -- plus one for sqrtf with root (v then holds the squares); the argument is the reference's
+    wherever the top-two gap exceeds twice that, and the lowest index on exact ties; a row of NaN reports `empty`.
+    Returns the worst value error in units of the bound."""
+    v = np.moveaxis(np.asarray(v, np.float64), axis, -1)
+    got_arg, got_max = np.asarray(got_arg).astype(np.int64), np.asarray(got_max, np.float64)
+    worst = 0.0
+    for r in range(v.shape[0]):
+        row = v[r]
+        if row.size == 0 or np.all(np.isnan(row)):
+            assert got_arg[r] == empty[1] and (np.isnan(got_max[r]) if np.isnan(empty[0]) else got_max[r] == empty[0]), (r, got_arg[r], got_max[r])
+            continue
+        top = np.nanmax(row)
+        first = int(np.nonzero(row == top)[0][0])
+        tol = units * EPS32 * top
+        order = np.sort(row[~np.isnan(row)])
+        ties = int(np.sum(row == top))
+        gap = top - (order[-1 - ties] if order.size > ties else -np.inf)
+        assert 0 <= got_arg[r] < row.size, (r, got_arg[r])
+        if gap > 2 * tol:
+            assert row[got_arg[r]] == top, "row %d: argument %d (%.9g) against %d (%.9g)" % (r, got_arg[r], row[got_arg[r]], first, top)
+            if ties > 1:
+                assert got_arg[r] == first, "row %d: tie taken at %d, first is %d" % (r, got_arg[r], first)
+        else:
+            assert row[got_arg[r]] >= top - 2 * tol, (r, got_arg[r])
+        want = np.sqrt(top) if root else top
+        bnd = (units / 2 + 1) * EPS32 * want if root else tol
+        err = abs(got_max[r] - want)
+        assert err <= bnd, "row %d: value %.9g against %.9g (bound %.3g)" % (r, got_max[r], want, bnd)
+        worst = max(worst, err / bnd if bnd > 0 else 0.0)
+    return worst
+
+
+def steer_dot64(vec, steer, scale):
+    """(ref, bound): out[r] = scale * sum_k vec[k] conj(steer[r][k]) in complex128 (np.sum's pairwise order), and
+    (ceil(n / 256) + 10) 2^-53 |scale| sum |v| |s|: per thread ceil(n / 256) fused or unfused multiply-adds, 6 steps of wave_sum,
+    3 additions of the wave totals and the product by scale."""
+    v = np.asarray(vec).astype(np.complex128)
+    s = np.atleast_2d(np.asarray(steer, np.complex128))
+    ref = scale * np.sum(v[None, :] * np.conj(s), axis=1)
+    bound = (-(-v.size // 256) + 10) * EPS64 * abs(scale) * np.sum(np.abs(v)[None, :] * np.abs(s), axis=1)
+    return ref, bound
+
+
+# Cases that tests/test_ref64.py (CPU) and tests/test_gpu_f64_rows.py (GPU, seed 0) share.
+# multi-template dot: (L, T, tones).  L: either side of the register tile of 8, 100, the limit of the register-tiled kernel (2048),
+# the fallback kernel (2049) and the ABI's maximum (8192); T in {1, 3, 20}, one template only at L = 1 (one-sample templates all score exactly
+# 1: no slide is decided between two of them).  Noise templates up to 100 samples; from 2048 on the
+# templates are unit tones at (i + 1) / 16 cycles per sample with 10 % of noise and the record carries their conjugates for a
+# third of its length each: between random templates the top-two gap is exponentially distributed with mean 1 / L while the
+# bound grows like sqrt(L), and at 2048 samples and more fewer than 95 % of the slides would be decided.
+MT_CASES = [(1, 1), (7, 3), (8, 20), (9, 3), (100, 1), (100, 20), (2048, 3), (2049, 1), (2049, 3), (8192, 1), (8192, 3)]
+
+
+def mt_case(seed, L, T):
+    """dict(x, tm, te, n, loud, quiet, zeros): the record, the templates (complex64, to be used as they are: the kernel does not
+    conjugate) and their float32 energies.  Before the stretches are scaled, conj(T_i) is added to the noise at twice its level
+    once in the unit region, once inside the quiet stretch and once across the loud -> unit edge, as far as T copies fit (later
+    copies overwrite none: they add); with tone templates the whole record carries them instead.  The run of zeros is longer
+    than the window up to 2049 samples; at 8192 the record of 20000 samples has no room for one, and the quiet stretch is as
+    long as the window + 300."""
+    rng = np.random.default_rng(1000 * seed + 13 * L + T)
+    if L <= 100:
+        n, loud, quiet, zeros = 12288, (3000, 5048), (7000, 9048), (10000, 10000 + L + 150)
+    elif L <= 2049:
+        n, loud, quiet, zeros = 20000, (2500, 4548), (7000, 7000 + L + 600), (12000, 12000 + L + 50)
+    else:
+        n, loud, quiet, zeros = 20000, (1000, 3048), (4000, 4000 + L + 300), (13000, 15000)
+    base = fe_noise(rng, n)
+    if L <= 100:
+        tm = fe_noise(rng, T * L).reshape(T, L)
+        for i in range(T):
+            for p in (200 + i * (L + 3), quiet[0] + 40 + i * (L + 3), loud[1] - (L * (i + 1)) // (T + 1)):
+                if p + L <= n:
+                    base[p : p + L] += 2 * np.conj(tm[i])
+    else:
+        t = np.arange(L)
+        tm = (np.exp(2j * np.pi * np.outer(np.arange(1, T + 1) / 16.0, t)) + 0.1 * fe_noise(rng, T * L).reshape(T, L)).astype(np.complex64)
+        k = np.arange(n)
+        for i in range(T):
+            a, b = i * n // T, (i + 1) * n // T
+            base[a:b] += (2 * np.exp(-2j * np.pi * (i + 1) / 16.0 * k[a:b])).astype(np.complex64)
+    x = rows_record(rng, n, loud, quiet, zeros, base=base)
+    te = np.sum(np.abs(tm.astype(np.complex128)) ** 2, axis=1).astype(np.float32)
+    return dict(x=x, tm=tm, te=te, n=n, loud=loud, quiet=quiet, zeros=zeros)
+
+
+def mt_runs(L, n, quiet):
+    """(start, nslides) runs of a case: the whole record from start 3 to the slide that ends on the last sample, and runs that
+    begin 100 slides in front of the quiet stretch with one slide below, at and above the slides of one workgroup (2048 of the
+    register-tiled kernel up to L = 2048, 64 of the fallback beyond)."""
+    per = 2048 if (L + 7) // 8 * 8 <= 2048 else 64
+    return [(3, n - L + 1 - 3)] + [(quiet[0] - 100, c) for c in (per - 1, per, per + 1)]
+
+
+# moving average / sum: (n, L) -- one sample; a window longer than the record; either side of the tile form's reach (1024) and
+# of its outputs per workgroup; the prefix form within one tile, across two and across several, with the record's stretches
+# in front of, inside and behind the windows
+MOVING_CASES = [(1, 1), (100, 1024), (4097, 1024), (4097, 1025), (12289, 1023), (9000, 3000), (5000, 4096), (12288, 1500), (12288, 6000)]
+
+
+def moving_record(seed, n, signed):
+    """float32 record of a moving-sum case: |rows_record| (or its real part when signed) with the loud stretch over n/16 .. n/16 +
+    n/6, the quiet one over 0.7 n .. 0.9 n -- at 12288 samples more than 1500 + 4096 behind the loud one, so that the bound of
+    the windows inside it holds nothing loud -- and zeros over the last twentieth."""
+    rng = np.random.default_rng(1000 * seed + n + (1 if signed else 0))
+    z = rows_record(rng, n, (n // 16, n // 16 + n // 6), (7 * n // 10, 9 * n // 10), (n - n // 20, n))
+    return np.ascontiguousarray(z.real if signed else np.abs(z)).astype(np.float32)

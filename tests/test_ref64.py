@@ -450,3 +450,124 @@ def test_synthetic_traces_carry_the_conditions_they_are_for():
             assert not np.isin(np.concatenate((nan - 1, nan + 1)), idx).any()  # x > NaN is false: no maximum beside a NaN
         if name == "height_equal":
             assert np.any(trace == np.float32(min_height)) and not np.any(trace[idx] == np.float32(min_height))
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# The rows toolbox: the direct-sum references against the oracle's kernel restatements on plain noise, the oracle's cumsum
+# forms OUTSIDE the moving-sum bound on rows_record (why they are not the reference there), float32 / locally anchored NumPy
+# stand-ins inside every bound over seeds 0 .. 9 of the cases the GPU tests use, and the "decided >= 95 %" condition of the
+# multi-template cases.
+from oracle import kernels as K  # noqa: E402
+
+
+def _close_to_oracle(ref, got, casts):
+    """The oracle returns float32 / complex64: `casts` roundings of 2^-24 |ref| on top of 1e-12 of the largest value."""
+    ref = np.asarray(ref)
+    assert np.all(np.abs(got - ref) <= casts * R.EPS32 * np.abs(ref) + 1e-12 * np.max(np.abs(ref)))
+
+
+def test_rows_references_equal_the_oracle_on_plain_noise():
+    rng = np.random.default_rng(41)
+    x, y = cn(rng, 75), cn(rng, 3000)
+    ref, _ = R.sliding_multiply64(x, y, 17, 200)
+    _close_to_oracle(ref, K.slidingMultiplyNormalised(x, y, 17, 200), 6)  # (its complex64 product, float32 divisor, division and cast)
+    ref, _ = R.sliding_multiply64(x, y, 2900, 100, coef=1.5)  # windows that run past the end read zeros
+    _close_to_oracle(ref, K.slidingMultiplyNormalised(x, y, 2900, 100, 1.5), 6)
+    tm = cn(rng, 5 * 33).reshape(5, 33)
+    te = np.sum(np.abs(tm.astype(np.complex128)) ** 2, axis=1).astype(np.float32)
+    q, b = R.multi_template64(y, tm, te, 5, 2000)
+    win, dec = R.multi_template_decided(q, b)
+    oti, oq = K.multiTemplateSlidingDotProduct(y, tm, 5, 2000, te)
+    _close_to_oracle(q.max(axis=1), oq, 1)
+    assert np.array_equal(win[dec], oti[dec]) and dec.mean() > 0.95
+    v = rng.standard_normal(5000).astype(np.float32)
+    for L in (1, 100, 1500):
+        _close_to_oracle(R.moving_sum64(v, L, mean=True), K.movingAverage(v, L), 1)
+        _close_to_oracle(R.moving_sum64(v, L), K.movingAverage(v, L, True), 1)
+        p, _ = R.complex_moving_sum64(y, L)
+        _close_to_oracle(p, K.movingComplexSum(y, L), 1)
+    z = cn(rng, 7 * 129).reshape(7, 129)
+    _close_to_oracle(R.rows_absq64(z), K.complexMagnSq(z, np.float32), 2)
+    am, mx = K.argmaxAbsRows(z, True)
+    assert R.check_rowmax(am, mx, R.rows_absq64(z)) <= 1
+    am, mx = K.argmaxAbsRows(z)
+    assert R.check_rowmax(am, mx, R.rows_absq64(z), root=True) <= 1
+    st = np.exp(2j * np.pi * rng.uniform(size=(4, 75)))
+    ref, bound = R.steer_dot64(x, st, 0.25)
+    assert np.all(np.abs(ref - 0.25 * (st.conj() @ x.astype(np.complex128))) <= bound)
+
+
+def test_rows_record_and_the_oracle_cumsum_forms():
+    """The record's scalings are exact, and on it the oracle's difference of cumulative sums leaves the moving-sum bound by
+    a wide margin in the quiet stretch more than a window + 4096 samples behind the loud one -- while a locally anchored stand-in stays inside."""
+    rng = np.random.default_rng(3)
+    n = 12288
+    base = R.fe_noise(rng, n)
+    x = R.rows_record(rng, n, (200, 2248), (8000, 10048), (11000, 11200), base=base)
+    assert np.array_equal(x[200:2248], base[200:2248] * np.float32(1024)) and np.array_equal(x[8000:10048] * np.float32(2.0 ** 20), base[8000:10048])
+    assert not x[11000:11200].any() and np.array_equal(x[:200], base[:200])
+    a = np.abs(x).astype(np.float32)
+    for L, mean in ((1500, True), (1500, False), (64, False)):
+        ref = R.moving_sum64(a, L, mean)
+        bound = R.moving_bound(a, L, ref, mean)
+        assert R.worst_ratio(K.movingAverage(a, L, not mean), ref, bound) > 1
+        assert R.worst_ratio(R.moving_local(a, L, mean), ref, bound) <= 1
+    p, bound = R.complex_moving_sum64(x, 100)
+    assert R.worst_ratio(K.movingComplexSum(x, 100), p, bound) > 1
+
+
+@pytest.mark.parametrize("seed", range(10))
+def test_rows_moving_stand_in_inside_the_bound(seed):
+    for n, L in R.MOVING_CASES:
+        for signed in (False, True):
+            x = R.moving_record(seed, n, signed)
+            for mean in (True, False):
+                ref = R.moving_sum64(x, L, mean)
+                bound = R.moving_bound(x, L, ref, mean)
+                assert R.worst_ratio(R.moving_local(x, L, mean), ref, bound) <= 1, (n, L, signed, mean)
+                assert np.all(bound[np.arange(n) >= n - n // 20 + L + R.MOVING_SPAN] == 0)  # an all-zero range must come back exact
+
+
+@pytest.mark.parametrize("seed", range(10))
+def test_rows_sliding_multiply_stand_in_inside_the_bound(seed):
+    rng = np.random.default_rng(50 + seed)
+    y = R.rows_record(rng, 9000, (1500, 3548), (4500, 6548), (7000, 8500))
+    for xlen in (1, 3, 75, 1000, 1430):
+        x = R.fe_noise(rng, xlen)
+        for start, rows in ((4400, 65), (6500, 64), (7000 - xlen, 3), (8990, 10)):
+            rows = min(rows, 9000 - start)
+            ref, bound = R.sliding_multiply64(x, y, start, rows)
+            got = R.sliding_multiply32(x, y, start, rows)
+            assert np.array_equal(np.isnan(got), np.isnan(ref)), (xlen, start)
+            ok = ~np.isnan(ref)
+            assert R.worst_ratio(got[ok], ref[ok], bound[ok]) <= 1, (xlen, start)
+
+
+@pytest.mark.parametrize("case", R.MT_CASES, ids=lambda c: "L%d-T%d" % c)
+def test_rows_multi_template_cases_decided_and_stand_in(case):
+    """Every run of every multi-template case: at least 95 % of the slides have a decided template (from the reference and the
+    bound alone), and the float32 stand-in is inside the bound and agrees on every decided slide; seeds 0 .. 9 for templates up
+    to 100 samples, seed 0 (the GPU's) beyond."""
+    L, T = case
+    for seed in range(10 if L <= 100 else 1):
+        c = R.mt_case(seed, L, T)
+        for start, ns in R.mt_runs(L, c["n"], c["quiet"]):
+            assert start >= 0 and start + ns - 1 + L <= c["n"]
+            q, b = R.multi_template64(c["x"], c["tm"], c["te"], start, ns)
+            win, dec = R.multi_template_decided(q, b)
+            assert dec.mean() >= 0.95, (seed, start, ns, dec.mean())
+            gi, gq = R.multi_template32(c["x"], c["tm"], c["te"], start, ns)
+            r = np.arange(ns)
+            assert R.worst_ratio(gq, q[r, gi], b[r, gi]) <= 1 and np.array_equal(gi[dec], win[dec])
+        assert (3, c["n"] - L - 2) == R.mt_runs(L, c["n"], c["quiet"])[0]  # the whole-record run ends on the last sample
+
+
+def test_rows_complex_moving_sum_stand_in():
+    for seed in range(10):
+        rng = np.random.default_rng(70 + seed)
+        x = R.rows_record(rng, 9000, (1500, 3548), (4500, 6548), (7000, 8500))
+        for L in (1, 8, 100, 513, 4096):
+            p, bound = R.complex_moving_sum64(x, L)
+            s = np.lib.stride_tricks.sliding_window_view(x.astype(np.complex128), L).sum(axis=1) if L <= 513 else R.window_sums64(x.astype(np.complex128), L)
+            got = (s.real ** 2 + s.imag ** 2).astype(np.float32)
+            assert R.worst_ratio(got, p, bound) <= 1
