@@ -14,7 +14,6 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
-#include <vector>
 
 #include "caf_internal.h"
 #include "caf_wave.h"
@@ -22,26 +21,6 @@
 namespace caf {
 
 namespace {
-
-// ---- scratch from the library's pool; the caller's own stream is synchronised before the blocks go back --------------
-struct BurstScratch {
-    std::vector<void*> ptrs;
-    hipStream_t st;
-    explicit BurstScratch(hipStream_t s) : st(s) {}
-    template <typename T>
-    int get(T** p, int64_t count) {
-        void* q = nullptr;
-        const int rc = pool_alloc(&q, std::max<int64_t>(count * (int64_t)sizeof(T), 16));
-        if (rc) return rc;
-        ptrs.push_back(q);
-        *p = (T*)q;
-        return CAF_OK;
-    }
-    ~BurstScratch() {
-        if (!ptrs.empty() && st != nullptr) (void)hipStreamSynchronize(st);
-        for (void* q : ptrs) (void)pool_free(q);
-    }
-};
 
 unsigned grid_for(int64_t items, int64_t per_block, int64_t cap = 1 << 20) {
     const int64_t g = (items + per_block - 1) / per_block;
@@ -338,7 +317,7 @@ int medfilt_wavelet(const T* x, int64_t n, int64_t W, T* out, hipStream_t st) {
     constexpr int BITS = KeyOf<T>::BITS;
     const int64_t ntiles = n / WM_TILE + 1;  // rank queries reach position n
     const int64_t nwl = ntiles * (WM_TILE / 64);
-    BurstScratch sc(st);
+    Scratch sc(st);
     K *a = nullptr, *b = nullptr;
     WmWord* words = nullptr;
     int64_t *tiles = nullptr, *Zs = nullptr;
@@ -357,8 +336,7 @@ int medfilt_wavelet(const T* x, int64_t n, int64_t W, T* out, hipStream_t st) {
         std::swap(a, b);
     }
     hipLaunchKernelGGL(k_wm_median<T>, dim3(grid_for(n, 256)), dim3(256), 0, st, words, nwl, Zs, n, W, out);
-    CAF_HIP_TRY(hipGetLastError());
-    return CAF_OK;
+    return sc.finish();
 }
 
 // ---- threshold edges: one wave per row ----------------------------------------------------------------------------------
@@ -616,22 +594,21 @@ int column_means(const T* x, int64_t rows, int64_t cols, int32_t absolute, doubl
     const int64_t rows_per = (rows + nchunks - 1) / nchunks;
     const int64_t gx = (cols + 255) / 256;
     CAF_REQUIRE(gx <= 0x7fffffff, "caf_column_means: too many columns");
-    BurstScratch sc(st);
+    Scratch sc(st);
     double* part = nullptr;
     const int rc = sc.get(&part, nchunks * cols);
     if (rc) return rc;
     hipLaunchKernelGGL(k_colsum_part<T>, dim3((unsigned)gx, (unsigned)nchunks), dim3(256), 0, st, x, rows, cols, absolute,
                        rows_per, part);
     hipLaunchKernelGGL(k_colsum_final, dim3(grid_for(cols, 256)), dim3(256), 0, st, part, (int32_t)nchunks, rows, cols, out);
-    CAF_HIP_TRY(hipGetLastError());
-    return CAF_OK;
+    return sc.finish();
 }
 
 template <typename T>
 int above_threshold(const T* x, int64_t n, T thr, int64_t* idx, int64_t idx_cap, int64_t* starts, int64_t starts_cap,
                     int64_t* h_counts, hipStream_t st) {
     const int64_t ntiles = (n + WM_TILE - 1) / WM_TILE;
-    BurstScratch sc(st);
+    Scratch sc(st);
     int64_t *ta = nullptr, *ts = nullptr;
     int rc;
     if ((rc = sc.get(&ta, ntiles + 1)) || (rc = sc.get(&ts, ntiles + 1))) return rc;
@@ -648,8 +625,7 @@ int above_threshold(const T* x, int64_t n, T thr, int64_t* idx, int64_t idx_cap,
         CAF_REQUIRE(idx_cap >= tot[0] && starts != nullptr && starts_cap >= tot[1], "caf_threshold_indices: outputs too small");
         hipLaunchKernelGGL((k_above<T, true>), dim3(g), dim3(256), 0, st, x, n, thr, ntiles, ta, ts, idx, starts);
     }
-    CAF_HIP_TRY(hipGetLastError());
-    return CAF_OK;
+    return sc.finish();
 }
 
 template <typename T>
@@ -745,7 +721,7 @@ int32_t caf_gather_edges(const int32_t* d_edges, int64_t rows, int32_t edges_max
     hipStream_t st = (hipStream_t)stream;
     const int64_t ntiles = (rows + GE_TILE - 1) / GE_TILE;
     CAF_REQUIRE(ntiles <= 0x7fffffff, "caf_gather_edges: too many rows");
-    BurstScratch sc(st);
+    Scratch sc(st);
     int64_t *tiles = nullptr, *np = nullptr;
     int32_t* flat = nullptr;
     int rc;
@@ -755,7 +731,7 @@ int32_t caf_gather_edges(const int32_t* d_edges, int64_t rows, int32_t edges_max
     int64_t T = 0;
     CAF_HIP_TRY(hipMemcpyAsync(&T, tiles + ntiles, 8, hipMemcpyDeviceToHost, st));
     CAF_HIP_TRY(hipStreamSynchronize(st));
-    if (T == 0) return CAF_OK;
+    if (T == 0) return sc.finish();
     if ((rc = sc.get(&flat, T))) return rc;
     hipLaunchKernelGGL(k_ge_compact, dim3((unsigned)ntiles), dim3(GE_TILE), 0, st, d_edges, d_counts, rows, edges_max, tiles, flat);
     hipLaunchKernelGGL(k_ge_pair, dim3(1), dim3(1024), 0, st, flat, tiles + ntiles, min_len, max_len, d_pairs, capacity, np);
@@ -764,7 +740,7 @@ int32_t caf_gather_edges(const int32_t* d_edges, int64_t rows, int32_t edges_max
     CAF_HIP_TRY(hipMemcpyAsync(&K, np, 8, hipMemcpyDeviceToHost, st));
     CAF_HIP_TRY(hipStreamSynchronize(st));
     *h_num_pairs = K;
-    return CAF_OK;
+    return sc.finish();
 }
 
 int32_t caf_threshold_indices(const void* d_x, int64_t n, int32_t is_f64, double threshold, int64_t* d_idx, int64_t idx_cap,

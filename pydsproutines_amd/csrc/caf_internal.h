@@ -10,6 +10,7 @@
 #include <mutex>
 #include <string>
 #include <utility>
+#include <vector>
 
 namespace caf {
 
@@ -80,6 +81,63 @@ int pool_alloc(void** out, int64_t bytes);
 int pool_free(void* p);
 void pool_trim();
 void pool_stats(int64_t* cached, int64_t* in_use, int64_t* hits, int64_t* misses);
+
+// The one owner of pooled scratch.  A block may go back to the pool only once nothing on a stream other than the null stream
+// can still touch it (caf_pool.hip): on the null stream the block's next user is ordered behind the work that uses it now,
+// on a caller's own stream the next user may sit anywhere, so that stream is synchronised first.  An entry point ends with
+// `return sc.finish();`; the destructor covers every earlier return, where it blocks (on whatever stream) rather than free
+// blocks that are still in use.  blocking: the call also blocks on the null stream (kept per entry point: DESIGN.md).
+class Scratch {
+public:
+    explicit Scratch(hipStream_t st, bool blocking = false) : st_(st), blocking_(blocking) {}
+    Scratch(const Scratch&) = delete;
+    Scratch& operator=(const Scratch&) = delete;
+    template <class T>
+    int get(T** p, int64_t count) {
+        void* q = nullptr;
+        const int64_t bytes = count * (int64_t)sizeof(T);
+        const int rc = pool_alloc(&q, bytes < 16 ? 16 : bytes);
+        if (rc) return rc;
+        ptrs_.push_back(q);
+        *p = (T*)q;
+        return CAF_OK;
+    }
+    int finish() {
+        finished_ = true;
+        if (!ptrs_.empty() && (st_ != nullptr || blocking_)) CAF_HIP_TRY(hipStreamSynchronize(st_));
+        CAF_HIP_TRY(hipGetLastError());
+        return CAF_OK;
+    }
+    ~Scratch() {
+        if (!ptrs_.empty() && !finished_) (void)hipStreamSynchronize(st_);
+        for (void* q : ptrs_) (void)pool_free(q);
+    }
+
+private:
+    std::vector<void*> ptrs_;
+    hipStream_t st_;
+    bool blocking_, finished_ = false;
+};
+
+// a host table for a long-lived owner: allocated (from the pool, or with hipMalloc for tables kept for the life of the
+// process), uploaded on the null stream (complete on return), and freed again when the upload fails
+inline int upload_table(const void* host, int64_t bytes, bool pooled, void** out) {
+    void* d = nullptr;
+    if (pooled) {
+        const int rc = pool_alloc(&d, bytes);
+        if (rc) return rc;
+    } else {
+        CAF_HIP_TRY(hipMalloc(&d, (size_t)bytes));
+    }
+    const int rc = host_h2d(d, host, bytes, nullptr);
+    if (rc) {
+        if (pooled) (void)pool_free(d);
+        else (void)hipFree(d);
+        return rc;
+    }
+    *out = d;
+    return CAF_OK;
+}
 
 int64_t prefix_num_tiles(int64_t m);
 // prefix: energy_prefix_doubles(m) entries (the prefix itself, then the 64-sample chunk energies: caf_energy.h)
@@ -320,17 +378,26 @@ struct FftPlan {
     void* info = nullptr;  // rocfft_execution_info
     void* work = nullptr;
     size_t work_bytes = 0;
-    int create(bool inverse, size_t len, size_t batch, size_t dist, bool inplace = true);
     int exec(void* in, void* out, hipStream_t st);
+    void* slot = nullptr;  // its place in the checkout cache (set by fft_plan_acquire)
+    // recorded by fft_plan_release on a caller's own stream: the work buffer's last use.  The next owner's first exec
+    // makes its stream wait for it (no host synchronisation on either side).
+    hipEvent_t last_use = nullptr;
+    bool last_use_pending = false;
+
+private:
+    friend int fft_plan_acquire(FftPlan*, bool, size_t, size_t, size_t, bool);
+    friend void fft_plan_release(FftPlan*, hipStream_t);
+    int create(bool inverse, size_t len, size_t batch, size_t dist, bool inplace);
     void destroy();
-    // identity for the checkout cache (set by fft_plan_acquire; key_len == 0: not cacheable)
-    int key_dev = 0;
-    bool key_inverse = false, key_inplace = true;
-    size_t key_len = 0, key_batch = 0, key_dist = 0;
 };
-// checkout cache: acquire hands out a parked plan of the same shape or creates one; release parks it again
+// The one cache of rocFFT plans, a checkout cache: acquire hands out a parked plan of the same shape or creates one, and
+// release parks it again, so a plan, its work buffer and its execution info have exactly one owner at a time.
+// st: the stream the plan last ran on.  A plan may be released with work still queued: like pooled scratch, its next owner
+// either runs on the null stream or behind the releasing call's Scratch synchronisation -- and where a call on a caller's
+// stream takes no scratch (caf_fft_rows), behind the event recorded here.
 int fft_plan_acquire(FftPlan* out, bool inverse, size_t len, size_t batch, size_t dist, bool inplace = true);
-void fft_plan_release(FftPlan* p);
+void fft_plan_release(FftPlan* p, hipStream_t st = nullptr);
 
 #define CAF_REQUIRE(cond, msg)      \
     do {                            \

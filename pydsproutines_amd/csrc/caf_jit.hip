@@ -802,15 +802,10 @@ int pdj_bluestein_tables(const PdjPlan& pl, float2** chirp_out, float2** bhat_ou
     rec(b.data(), out.data(), m, 1, 0);
     for (int k = 0; k < m; ++k) bhat[k] = std::complex<float>((float)(out[k].real() / m), (float)(out[k].imag() / m));
     float2 *dc = nullptr, *db = nullptr;
-    int rc = pool_alloc((void**)&dc, (int64_t)nx * 8);
+    int rc = upload_table(chirp.data(), (int64_t)nx * 8, true, (void**)&dc);
     if (rc) return rc;
-    if ((rc = pool_alloc((void**)&db, (int64_t)m * 8))) {
+    if ((rc = upload_table(bhat.data(), (int64_t)m * 8, true, (void**)&db))) {
         (void)pool_free(dc);
-        return rc;
-    }
-    if ((rc = host_h2d(dc, chirp.data(), (int64_t)nx * 8, nullptr)) || (rc = host_h2d(db, bhat.data(), (int64_t)m * 8, nullptr))) {
-        (void)pool_free(dc);
-        (void)pool_free(db);
         return rc;
     }
     *chirp_out = dc, *bhat_out = db;
@@ -824,16 +819,7 @@ int pdj_twiddles(int32_t n, float2** out) {
         const double ph = 2.0 * M_PI * (double)q / (double)n;
         t[q] = std::complex<float>((float)std::cos(ph), (float)std::sin(ph));
     }
-    float2* d = nullptr;
-    int rc = pool_alloc((void**)&d, (int64_t)n * 8);
-    if (rc) return rc;
-    rc = host_h2d(d, t.data(), (int64_t)n * 8, nullptr);
-    if (rc) {
-        (void)pool_free(d);
-        return rc;
-    }
-    *out = d;
-    return CAF_OK;
+    return upload_table(t.data(), (int64_t)n * 8, true, (void**)out);
 }
 
 std::string brace_list(const int* v, int n) {

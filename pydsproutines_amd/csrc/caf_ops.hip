@@ -18,76 +18,23 @@ using namespace caf;
 
 namespace {
 
-// Small cache of row-FFT plans keyed by (device, len, batch, inverse, inplace); plans are reused
-// across calls (create -> use many), destroyed at process exit by the OS.
-struct PlanKey {
-    int dev;
-    int64_t len, batch;
-    int inv, inplace;
-    bool operator<(const PlanKey& o) const {
-        return std::tie(dev, len, batch, inv, inplace) < std::tie(o.dev, o.len, o.batch, o.inv, o.inplace);
-    }
-};
-std::mutex g_plan_mu;
-std::map<PlanKey, FftPlan> g_plans;
-
-int get_row_plan(int64_t len, int64_t batch, bool inverse, bool inplace, FftPlan** out) {
-    int dev = 0;
-    CAF_HIP_TRY(hipGetDevice(&dev));
-    PlanKey k{dev, len, batch, inverse ? 1 : 0, inplace ? 1 : 0};
-    std::lock_guard<std::mutex> lk(g_plan_mu);
-    auto it = g_plans.find(k);
-    if (it == g_plans.end()) {
-        if (g_plans.size() > 64) {  // bound the cache
-            for (auto& kv : g_plans) kv.second.destroy();
-            g_plans.clear();
-        }
-        FftPlan p;
-        int rc = p.create(inverse, (size_t)len, (size_t)batch, (size_t)len, inplace);
-        if (rc) {
-            p.destroy();
-            return rc;
-        }
-        it = g_plans.emplace(k, p).first;
-    }
-    *out = &it->second;
-    return CAF_OK;
-}
-
-// rows FFT of a (rows, len) matrix, chunked so that the plan batch is bounded
+// rows FFT of a (rows, len) matrix, chunked so that the plan batch is bounded; a plan is checked out per chunk (caf_fft.hip)
 int fft_rows(const float2* in, float2* out, int64_t rows, int64_t len, bool inverse, hipStream_t st) {
-    if (rows <= 0) return CAF_OK;
     const bool inplace = (out == in);
-    int64_t done = 0;
-    while (done < rows) {
+    for (int64_t done = 0; done < rows;) {
         // largest power-of-two chunk <= remaining keeps the number of distinct plans small
         int64_t chunk = 1;
         while (chunk * 2 <= rows - done && chunk * 2 * len <= ((int64_t)1 << 27)) chunk *= 2;
-        FftPlan* p = nullptr;
-        int rc = get_row_plan(len, chunk, inverse, inplace, &p);
+        FftPlan p;
+        int rc = fft_plan_acquire(&p, inverse, (size_t)len, (size_t)chunk, (size_t)len, inplace);
         if (rc) return rc;
-        rc = p->exec((void*)(in + done * len), inplace ? nullptr : (void*)(out + done * len), st);
+        rc = p.exec((void*)(in + done * len), inplace ? nullptr : (void*)(out + done * len), st);
+        fft_plan_release(&p, st);
         if (rc) return rc;
         done += chunk;
     }
     return CAF_OK;
 }
-
-struct Scratch {
-    std::vector<void*> ptrs;
-    template <typename T>
-    int get(T** p, int64_t count) {
-        void* q = nullptr;
-        const int rc = pool_alloc(&q, std::max<int64_t>(count * (int64_t)sizeof(T), 16));
-        if (rc) return rc;
-        ptrs.push_back(q);
-        *p = (T*)q;
-        return CAF_OK;
-    }
-    ~Scratch() {
-        for (void* q : ptrs) (void)pool_free(q);
-    }
-};
 
 int energy_prefix(const float2* x, int64_t n, Scratch& sc, double** prefix, hipStream_t st) {
     double* tiles = nullptr;
@@ -139,7 +86,7 @@ int fir_overlap_save(const void* x, int64_t n, bool is_iq16, float scale, const 
         if (fir_debug()) fir_report(call, is_iq16, "none", 0, ntaps, 1, dsr, phase, 1, n, nout);
         return CAF_OK;
     }
-    Scratch sc;
+    Scratch sc(st);
     int rc;
     if (const int fb = fir_os_fused_block(ntaps)) {
         if (fir_debug()) fir_report(call, is_iq16, "os_fused", fb, ntaps, 1, dsr, phase, 1, n, nout);
@@ -176,12 +123,7 @@ int fir_overlap_save(const void* x, int64_t n, bool is_iq16, float scale, const 
             launch_fos_scatter(rows, b0, nb, L, B, ntaps, dsr, phase, out, nout, st);
         }
     }
-    // The scratch goes back to the pool on return.  Reuse is stream-ordered (caf_pool.hip): on the default stream a
-    // later user is ordered behind the kernels above, so the call stays asynchronous like the direct form; a caller's
-    // own stream is synchronised, because the next user of the block may sit on another stream.
-    if (st != nullptr) CAF_HIP_TRY(hipStreamSynchronize(st));
-    CAF_HIP_TRY(hipGetLastError());
-    return CAF_OK;
+    return sc.finish();
 }
 
 // ---- chirp-Z constants of the zoom, computed like CZTCached / IppCZT32fc (spectralRoutines.py:239-267,
@@ -265,12 +207,14 @@ int zoom_constants(int dev, int m, double span, double step, ZoomCzt* out) {
     }
     for (int i = 0; i < nfft; ++i) fvf[i] = std::complex<float>((float)fv[i].real(), (float)fv[i].imag());
     for (int i = 0; i < k; ++i) wws[i] = std::complex<float>((float)ww[m - 1 + i].real(), (float)ww[m - 1 + i].imag());
-    CAF_HIP_TRY(hipMalloc((void**)&z.aa, (size_t)m * 8));
-    CAF_HIP_TRY(hipMalloc((void**)&z.fv, (size_t)nfft * 8));
-    CAF_HIP_TRY(hipMalloc((void**)&z.wws, (size_t)k * 8));
-    CAF_H2D(z.aa, aa.data(), (size_t)m * 8);
-    CAF_H2D(z.fv, fvf.data(), (size_t)nfft * 8);
-    CAF_H2D(z.wws, wws.data(), (size_t)k * 8);
+    int rc;
+    if ((rc = upload_table(aa.data(), (int64_t)m * 8, false, (void**)&z.aa)) ||
+        (rc = upload_table(fvf.data(), (int64_t)nfft * 8, false, (void**)&z.fv)) ||
+        (rc = upload_table(wws.data(), (int64_t)k * 8, false, (void**)&z.wws))) {
+        (void)hipFree(z.aa);  // (the tables that did get uploaded; hipFree(nullptr) does nothing)
+        (void)hipFree(z.fv);
+        return rc;
+    }
     if (g_zoom_czt.size() > 64) g_zoom_czt.clear();  // (leaks a few hundred KB at worst; bounded)
     g_zoom_czt[key] = z;
     *out = z;
@@ -326,20 +270,18 @@ int32_t caf_xcorr_perdelay(const float* d_cutout, int32_t n, const float* d_rx, 
     // Power-of-two cutouts up to 16384 samples: one fused kernel (product -> LDS FFT -> |.|^2 -> argmax; window energies
     // and the cutout norm summed in the kernel): no product matrix, no prefix pass, no scratch, no synchronisation.
     // CAF_PERDELAY_UNFUSED=1 keeps the three-kernel form below (A/B switch; it also serves every other length).
-    {
-        static const bool unfused = [] {
-            const char* e = getenv("CAF_PERDELAY_UNFUSED");
-            return e && atoi(e) != 0;
-        }();
-        if (!unfused && perdelay_fused_ok(n) && !(jit_all && perdelay_jit_ok(n))) {
-            const int rc1 = launch_perdelay_fused((const float2*)d_cutout, n, (const float2*)d_rx, rx_len, start, step, num,
-                                                  zero_oor ? 1 : 0, d_qf2, (uint32_t*)d_fidx, d_caf, (float2*)d_ccaf, st);
-            if (rc1) return rc1;
-            CAF_HIP_TRY(hipGetLastError());
-            return CAF_OK;
-        }
+    static const bool unfused = [] {
+        const char* e = getenv("CAF_PERDELAY_UNFUSED");
+        return e && atoi(e) != 0;
+    }();
+    if (!unfused && perdelay_fused_ok(n) && !(jit_all && perdelay_jit_ok(n))) {
+        const int rc1 = launch_perdelay_fused((const float2*)d_cutout, n, (const float2*)d_rx, rx_len, start, step, num,
+                                              zero_oor ? 1 : 0, d_qf2, (uint32_t*)d_fidx, d_caf, (float2*)d_ccaf, st);
+        if (rc1) return rc1;
+        CAF_HIP_TRY(hipGetLastError());
+        return CAF_OK;
     }
-    Scratch sc;
+    Scratch sc(st, true);
     // energy prefix over the span of rx the delays touch (not the whole array: 128 delays of a 10^7-sample rx used
     // to cost a full pass), indices shifted accordingly; only when every window lies inside rx (otherwise the
     // out-of-range rules are stated against the whole array and the whole array is scanned)
@@ -360,21 +302,13 @@ int32_t caf_xcorr_perdelay(const float* d_cutout, int32_t n, const float* d_rx, 
     const double* d_norm = launch_cutout_norm((const float2*)d_cutout, n, d_cnorm, st);
     // cutouts of 100 / 1000 / 10000 samples: one fused kernel with radix-10 passes in LDS (CAF_PERDELAY_UNFUSED=1: the chain below)
     {
-        static const bool unfused10 = [] {
-            const char* e = getenv("CAF_PERDELAY_UNFUSED");
-            return e && atoi(e) != 0;
-        }();
         // lengths with prime factors up to 23 that are neither a power of two nor of ten: a kernel compiled for the length at run
         // time (caf_jit.hip); a length / box without one, or a compilation that fails (reported once), keeps the plan-driven
         // kernel (7-smooth lengths) or the three-kernel form below
-        if (!unfused10 && (jit_all || !(perdelay_fused_ok(n) || perdelay_decimal_ok(n))) && perdelay_jit_ok(n)) {
+        if (!unfused && (jit_all || !(perdelay_fused_ok(n) || perdelay_decimal_ok(n))) && perdelay_jit_ok(n)) {
             rc = launch_perdelay_jit((const float2*)d_cutout, n, yv, ylen_v, prefix, d_norm, start_v, step, num, zero_oor ? 1 : 0, d_qf2,
                                      (uint32_t*)d_fidx, d_caf, (float2*)d_ccaf, st);
-            if (rc == CAF_OK) {
-                CAF_HIP_TRY(hipStreamSynchronize(st));  // scratch (prefix, norm) is freed on return
-                CAF_HIP_TRY(hipGetLastError());
-                return CAF_OK;
-            }
+            if (rc == CAF_OK) return sc.finish();
             perdelay_jit_failed(n);
             static bool said = false;
             if (!said) {
@@ -384,7 +318,7 @@ int32_t caf_xcorr_perdelay(const float* d_cutout, int32_t n, const float* d_rx, 
                 std::fprintf(stderr, "[caf] run-time compilation unavailable, using the prebuilt per-delay kernels: %s\n", msg);
             }
         }
-        if (!unfused10 && (perdelay_decimal_ok(n) || perdelay_mixed_ok(n))) {
+        if (!unfused && (perdelay_decimal_ok(n) || perdelay_mixed_ok(n))) {
             // (the radix-10 kernel of caf_perdelay.hip / the plan-driven mixed-radix kernel of caf_perdelay_mr.hip)
             rc = perdelay_decimal_ok(n)
                      ? launch_perdelay_decimal((const float2*)d_cutout, n, yv, ylen_v, prefix, d_norm, start_v, step, num,
@@ -392,9 +326,7 @@ int32_t caf_xcorr_perdelay(const float* d_cutout, int32_t n, const float* d_rx, 
                      : launch_perdelay_mixed((const float2*)d_cutout, n, yv, ylen_v, prefix, d_norm, start_v, step, num,
                                              zero_oor ? 1 : 0, d_qf2, (uint32_t*)d_fidx, d_caf, (float2*)d_ccaf, st);
             if (rc) return rc;
-            CAF_HIP_TRY(hipStreamSynchronize(st));  // scratch (prefix, norm) is freed on return
-            CAF_HIP_TRY(hipGetLastError());
-            return CAF_OK;
+            return sc.finish();
         }
     }
     // rows per batch: up to 2^28 product elements (2 GiB of the 288) in flight, so that even 1e7-sample cutouts go
@@ -417,9 +349,7 @@ int32_t caf_xcorr_perdelay(const float* d_cutout, int32_t n, const float* d_rx, 
             launch_rows_argmax(buf, nr, n, 1, 1.0f, (uint32_t*)(d_fidx ? d_fidx + r0 : nullptr), d_qf2 ? d_qf2 + r0 : nullptr,
                                d_caf ? d_caf + r0 * n : nullptr, st, part, 1);
     }
-    CAF_HIP_TRY(hipStreamSynchronize(st));  // scratch is freed on return
-    CAF_HIP_TRY(hipGetLastError());
-    return CAF_OK;
+    return sc.finish();
 }
 
 int32_t caf_sliding_multiply_normalised(const float* d_x, int32_t xlen, const float* d_y, int64_t ylen,
@@ -430,15 +360,13 @@ int32_t caf_sliding_multiply_normalised(const float* d_x, int32_t xlen, const fl
                 "startIdx and idxlen should be within the bounds of d_y.");
     if (idxlen == 0) return CAF_OK;
     hipStream_t st = (hipStream_t)stream;
-    Scratch sc;
+    Scratch sc(st, true);
     double* prefix = nullptr;
     int rc = energy_prefix((const float2*)d_y, ylen, sc, &prefix, st);
     if (rc) return rc;
     launch_sliding_multiply((const float2*)d_x, xlen, (const float2*)d_y, ylen, prefix, start_idx, 1, idxlen, coefficient,
                             0, (float2*)d_z, st);
-    CAF_HIP_TRY(hipStreamSynchronize(st));
-    CAF_HIP_TRY(hipGetLastError());
-    return CAF_OK;
+    return sc.finish();
 }
 
 int32_t caf_multi_template_sliding_dot(const float* d_templates, const float* d_energies, int32_t num_templates,
@@ -451,15 +379,13 @@ int32_t caf_multi_template_sliding_dot(const float* d_templates, const float* d_
                 "final slide index should be within the bounds of d_x");
     if (idxlen == 0) return CAF_OK;
     hipStream_t st = (hipStream_t)stream;
-    Scratch sc;
+    Scratch sc(st, true);
     double* prefix = nullptr;
     int rc = energy_prefix((const float2*)d_x, xlen, sc, &prefix, st);
     if (rc) return rc;
     launch_multi_template_dot((const float2*)d_templates, d_energies, num_templates, template_len, (const float2*)d_x,
                               xlen, prefix, start_idx, idxlen, d_template_idx, d_qf2, st);
-    CAF_HIP_TRY(hipStreamSynchronize(st));
-    CAF_HIP_TRY(hipGetLastError());
-    return CAF_OK;
+    return sc.finish();
 }
 
 int32_t caf_multiply_slices_indexed_rows(const float* d_x, int64_t xlen, const float* d_rows, int32_t num_rows,
@@ -486,7 +412,7 @@ int32_t caf_argmax_abs_rows(const float* d_x, int64_t rows, int64_t len, uint32_
                             int32_t use_normsq, void* stream) {
     CAF_REQUIRE(d_x && d_argmax && rows >= 0 && len >= 1, "caf_argmax_abs_rows: bad arguments");
     hipStream_t st = (hipStream_t)stream;
-    Scratch sc;
+    Scratch sc(st);
     unsigned long long* part = nullptr;
     const int ch = rows > 0 ? rows_argmax_chunks(rows, len) : 0;
     if (ch) {
@@ -496,9 +422,7 @@ int32_t caf_argmax_abs_rows(const float* d_x, int64_t rows, int64_t len, uint32_
     for (int64_t r0 = 0; r0 < rows; r0 += ((int64_t)1 << 30))
         launch_rows_argmax((const float2*)d_x + r0 * len, std::min<int64_t>(rows - r0, (int64_t)1 << 30), len, use_normsq,
                            1.0f, d_argmax + r0, d_max ? d_max + r0 : nullptr, nullptr, st, part ? part + r0 * ch : nullptr);
-    if (ch && st != nullptr) CAF_HIP_TRY(hipStreamSynchronize(st));  // (scratch: stream-ordered on the default stream)
-    CAF_HIP_TRY(hipGetLastError());
-    return CAF_OK;
+    return sc.finish();
 }
 
 int32_t caf_moving_average(const float* d_x, int64_t rows, int64_t n, int32_t avg_length, int32_t sum_instead,
@@ -510,16 +434,14 @@ int32_t caf_moving_average(const float* d_x, int64_t rows, int64_t n, int32_t av
         CAF_HIP_TRY(hipGetLastError());
         return CAF_OK;
     }
-    Scratch sc;
+    Scratch sc(st, true);
     double *tiles = nullptr, *prefix = nullptr;
     int rc = sc.get(&tiles, moving_num_tiles(n) + 1024);
     if (rc) return rc;
     if ((rc = sc.get(&prefix, n + 1))) return rc;
     for (int64_t r = 0; r < rows; ++r)
         launch_moving_average(d_x + r * n, n, avg_length, sum_instead, tiles, prefix, d_out + r * n, st);
-    CAF_HIP_TRY(hipStreamSynchronize(st));
-    CAF_HIP_TRY(hipGetLastError());
-    return CAF_OK;
+    return sc.finish();
 }
 
 int32_t caf_complex_moving_sum(const float* d_x, int64_t n, int32_t sum_length, float* d_out, void* stream) {
@@ -555,14 +477,12 @@ int32_t caf_find_local_maxima(const float* d_x, int64_t n, float min_height, int
                               int32_t* d_count, void* stream) {
     CAF_REQUIRE(d_x && d_peak_index && d_count && n >= 1 && max_peaks >= 1, "caf_find_local_maxima: bad arguments");
     hipStream_t st = (hipStream_t)stream;
-    Scratch sc;
+    Scratch sc(st, true);
     int32_t* tiles = nullptr;
     int rc = sc.get(&tiles, local_maxima_scratch_ints(n));
     if (rc) return rc;
     launch_find_local_maxima(d_x, n, min_height, tiles, max_peaks, d_peak_index, d_count, st);
-    CAF_HIP_TRY(hipStreamSynchronize(st));
-    CAF_HIP_TRY(hipGetLastError());
-    return CAF_OK;
+    return sc.finish();
 }
 
 int32_t caf_gather_b32(const void* d_x, int64_t xlen, const int32_t* d_index, int64_t n, void* d_out, void* stream) {
@@ -621,18 +541,14 @@ int32_t caf_wola(const float* d_x, int64_t n, const float* d_hist, int64_t hist_
                          (int)dec, (long long)P, (long long)rows, (int)layout);
     if (fused) return launch_wola_fused(x, h, hist_len, d_taps, (int32_t)P, N, dec, layout, out, rows, st);
     // general path: polyphase sums (rotation folded in) -> batched backward rocFFT in place -> (layout 1) transpose
-    Scratch sc;
+    Scratch sc(st);
     float2* V = out;
     int rc;
     if (layout == 1 && (rc = sc.get(&V, rows * (int64_t)N))) return rc;
     if ((rc = launch_wola_poly(x, h, hist_len, d_taps, (int32_t)P, N, dec, V, rows, st))) return rc;
     if ((rc = fft_rows(V, V, rows, N, true, st))) return rc;
-    if (layout == 1) {
-        if ((rc = launch_wola_transpose(V, rows, N, out, st))) return rc;
-        if (st != nullptr) CAF_HIP_TRY(hipStreamSynchronize(st));  // scratch: see fir_overlap_save
-    }
-    CAF_HIP_TRY(hipGetLastError());
-    return CAF_OK;
+    if (layout == 1 && (rc = launch_wola_transpose(V, rows, N, out, st))) return rc;
+    return sc.finish();
 }
 
 int32_t caf_iq16_fir_decimate(const int16_t* d_iq, int64_t num_samples, float scale, const float* d_taps, int32_t num_taps,
@@ -668,16 +584,14 @@ int32_t caf_upfirdn(const float* d_x, int64_t rows, int64_t n, const float* d_ta
         hipStream_t st = (hipStream_t)stream;
         const int fb = fir_os_fused_block(num_taps);  // (launch_fir_os_fused picks its kernel by the same function)
         if (fir_debug()) fir_report("upfirdn", false, "os_fused", fb, num_taps, 1, down, 0, rows, n, out_len);
-        Scratch sc;
+        Scratch sc(st);
         float2* ht = nullptr;
         int rc = sc.get(&ht, fb);
         if (rc) return rc;
         rc = launch_fir_os_fused((const float2*)d_x, n, d_taps, num_taps, nullptr, 0, down, 0, (float2*)d_out, out_len, ht, st, rows, n,
                                  out_len);
         if (rc) return rc;
-        if (st != nullptr) CAF_HIP_TRY(hipStreamSynchronize(st));  // (scratch: stream-ordered on the default stream, see fir_overlap_save)
-        CAF_HIP_TRY(hipGetLastError());
-        return CAF_OK;
+        return sc.finish();
     }
     const char* kernel = launch_upfirdn((const float2*)d_x, rows, n, d_taps, num_taps, up, down, out_len, (float2*)d_out, d_out_abs,
                                         (hipStream_t)stream);
@@ -692,7 +606,7 @@ int32_t caf_czt_run_many(const float* d_x, int64_t rows, int32_t m, int32_t k, i
     CAF_REQUIRE(rows >= 0 && m >= 1 && k >= 1 && nfft >= m + k - 1, "caf_czt_run_many: need nfft >= m + k - 1");
     if (rows == 0) return CAF_OK;
     hipStream_t st = (hipStream_t)stream;
-    Scratch sc;
+    Scratch sc(st, true);
     const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(rows, ((int64_t)1 << 25) / nfft));
     float2* buf = nullptr;
     int rc = sc.get(&buf, chunk * nfft);
@@ -708,9 +622,7 @@ int32_t caf_czt_run_many(const float* d_x, int64_t rows, int32_t m, int32_t k, i
         launch_rows_mul_vec(buf, nfft, m - 1, (const float2*)d_ww, k, (float2*)d_out + r0 * k, k, k, nr,
                             1.0f / (float)nfft, st);
     }
-    CAF_HIP_TRY(hipStreamSynchronize(st));
-    CAF_HIP_TRY(hipGetLastError());
-    return CAF_OK;
+    return sc.finish();
 }
 
 int32_t caf_argmax3d_u32(const uint32_t* d_x, int64_t num_items, int32_t dim1, int32_t dim2, int32_t dim3,
@@ -822,7 +734,7 @@ int32_t caf_zoom_czt(caf_plan plan, int32_t template_index, const float* d_rx, i
     hipStream_t st = (hipStream_t)stream;
     ZoomCzt z;
     if ((rc = zoom_constants(v.device, v.N, span, step, &z))) return rc;
-    Scratch sc;
+    Scratch sc(st);
     const int32_t max_cand = (int32_t)std::min<int64_t>(num_shifts, (int64_t)1 << 20);
     int32_t *tiles = nullptr, *cand = nullptr, *cnt = nullptr, *sel = nullptr, *selcnt = nullptr;
     float *vals = nullptr, *fmax = nullptr;
@@ -850,9 +762,7 @@ int32_t caf_zoom_czt(caf_plan plan, int32_t template_index, const float* d_rx, i
     launch_zoom_finish(d_row_max, d_row_arg, v.d_nu, sel, selcnt, k, shift_start, span, step, farg, fmax, max_cand, cnt,
                        out->d_count, out->d_delay, out->d_coarse_freq_index, out->d_coarse_qf2, out->d_fine_index,
                        out->d_fine_freq, out->d_fine_qf2, st);
-    if (st != nullptr) CAF_HIP_TRY(hipStreamSynchronize(st));  // scratch: see fir_overlap_save
-    CAF_HIP_TRY(hipGetLastError());
-    return CAF_OK;
+    return sc.finish();
 }
 
 }  // extern "C"

@@ -217,14 +217,8 @@ int lds_fft_twiddles(int device, const float2** out) {
             const double ph = 2.0 * M_PI * (double)q / (double)PD_TWN;
             t[q] = std::complex<float>((float)std::cos(ph), (float)std::sin(ph));
         }
-        float2* d = nullptr;
-        CAF_HIP_TRY(hipMalloc((void**)&d, (size_t)PD_TWN * 8));
-        const hipError_t e = hipMemcpy(d, t.data(), (size_t)PD_TWN * 8, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(d);
-            CAF_HIP_TRY(e);
-        }
-        per_dev[device] = d;
+        const int rc = upload_table(t.data(), (int64_t)PD_TWN * 8, false, (void**)&per_dev[device]);
+        if (rc) return rc;
     }
     *out = per_dev[device];
     return CAF_OK;
@@ -859,12 +853,8 @@ static int r10_twiddles(int device, int32_t n, const float2** out) {
         t[q] = std::complex<float>((float)std::cos(ph), (float)std::sin(ph));
     }
     float2* d = nullptr;
-    CAF_HIP_TRY(hipMalloc((void**)&d, (size_t)n * 8));
-    const hipError_t e = hipMemcpy(d, t.data(), (size_t)n * 8, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        CAF_HIP_TRY(e);
-    }
+    const int rc = upload_table(t.data(), (int64_t)n * 8, false, (void**)&d);
+    if (rc) return rc;
     tabs.push_back({{device, n}, d});
     *out = d;
     return CAF_OK;

@@ -432,12 +432,8 @@ int mr_twiddles(int device, int32_t n, const float2** out) {
         t[q] = std::complex<float>((float)std::cos(ph), (float)std::sin(ph));
     }
     float2* d = nullptr;
-    CAF_HIP_TRY(hipMalloc((void**)&d, (size_t)n * 8));
-    const hipError_t e = hipMemcpy(d, t.data(), (size_t)n * 8, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        CAF_HIP_TRY(e);
-    }
+    const int rc = upload_table(t.data(), (int64_t)n * 8, false, (void**)&d);
+    if (rc) return rc;
     tabs.push_back({{device, n}, d});
     *out = d;
     return CAF_OK;

@@ -205,14 +205,11 @@ static int fused_twiddles(int device, float2** tw1_out, float2** tw23_out) {
         for (int n3 = 0; n3 < 16; ++n3)
             for (int dd = 0; dd < 4; ++dd) tw23[1088 + 1024 + n3 * 4 + dd] = cis((double)n3 * (2 * dd + 1), 128.0);
         float2 *a = nullptr, *b = nullptr;
-        CAF_HIP_TRY(hipMalloc((void**)&a, tw1.size() * 8));
-        hipError_t e = hipMalloc((void**)&b, tw23.size() * 8);
-        if (e == hipSuccess) e = hipMemcpy(a, tw1.data(), tw1.size() * 8, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(b, tw23.data(), tw23.size() * 8, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
+        int rc = upload_table(tw1.data(), (int64_t)tw1.size() * 8, false, (void**)&a);
+        if (rc) return rc;
+        if ((rc = upload_table(tw23.data(), (int64_t)tw23.size() * 8, false, (void**)&b))) {
             (void)hipFree(a);
-            (void)hipFree(b);
-            CAF_HIP_TRY(e);
+            return rc;
         }
         per_dev[device] = {a, b};
     }
@@ -667,98 +664,77 @@ static int32_t plan_build(caf_plan p, const caf_plan_desc* d) {
         for (int n = 0; n < N; ++n) e += std::norm(std::complex<double>(tm[(size_t)t * N + n]));
         tscale[t] = (float)(1.0 / e);
     }
-    void *tmp_tm = nullptr, *tmp_nu = nullptr;  // inputs of the device-side table build, freed after the sync below
-    auto free_tmp = [&]() {
-        (void)pool_free(tmp_tm);
-        (void)pool_free(tmp_nu);
-        tmp_tm = tmp_nu = nullptr;
-    };
-    if (p->mul_mode == 2 && T <= 65535) {
-        // explicit frequencies: the T*F modulated templates are generated on the device (k_build_hyp_time)
-        if ((rc = pool_alloc(&tmp_tm, (int64_t)T * N * 8)) || (rc = pool_alloc(&tmp_nu, (int64_t)F * 8))) {
-            free_tmp();
-            return rc;
-        }
-        if ((rc = host_h2d(tmp_tm, tm, (int64_t)T * N * 8, nullptr)) || (rc = host_h2d(tmp_nu, d->h_freqs_norm, (int64_t)F * 8, nullptr))) {
-            free_tmp();
-            return rc;
-        }
-        launch_build_hyp_time((const float2*)tmp_tm, (const double*)tmp_nu, N, B, F, T, d->auto_conj ? 0 : 1, p->d_hc,
-                              nullptr, NP, PLEN);
-    } else {
-        std::vector<std::complex<float>> host((size_t)nspec * B, std::complex<float>(0.f, 0.f));
-        for (int t = 0; t < T; ++t) {
-            // (row of partition q of a spectrum: the samples q * PLEN .. of the template at the row's start; the on-grid shifts
-            //  need no phase per partition: an even shift at 65536 points makes nu * 32768 q a whole number of cycles)
-            if (p->mul_mode != 2) {
-                for (int n = 0; n < N; ++n) {
-                    std::complex<float> u = tm[(size_t)t * N + n];
-                    host[((size_t)t * NP + n / PLEN) * B + n % PLEN] = d->auto_conj ? u : std::conj(u);
-                }
-            } else {
-                for (int f = 0; f < F; ++f) {
-                    const double nu = d->h_freqs_norm[f];
-                    std::complex<float>* dst0 = &host[((size_t)t * F + f) * NP * B];
+    {  // template spectra on the device; the inputs of the table build go back to the pool at the end of this block
+        Scratch build_in(nullptr);  // inputs of the device-side table build, in use until the synchronisation below
+        if (p->mul_mode == 2 && T <= 65535) {
+            // explicit frequencies: the T*F modulated templates are generated on the device (k_build_hyp_time)
+            float2* tmp_tm = nullptr;
+            double* tmp_nu = nullptr;
+            if ((rc = build_in.get(&tmp_tm, (int64_t)T * N)) || (rc = build_in.get(&tmp_nu, F))) return rc;
+            if ((rc = host_h2d(tmp_tm, tm, (int64_t)T * N * 8, nullptr)) || (rc = host_h2d(tmp_nu, d->h_freqs_norm, (int64_t)F * 8, nullptr)))
+                return rc;
+            launch_build_hyp_time(tmp_tm, tmp_nu, N, B, F, T, d->auto_conj ? 0 : 1, p->d_hc, nullptr, NP, PLEN);
+        } else {
+            std::vector<std::complex<float>> host((size_t)nspec * B, std::complex<float>(0.f, 0.f));
+            for (int t = 0; t < T; ++t) {
+                // (row of partition q of a spectrum: the samples q * PLEN .. of the template at the row's start; the on-grid shifts
+                //  need no phase per partition: an even shift at 65536 points makes nu * 32768 q a whole number of cycles)
+                if (p->mul_mode != 2) {
                     for (int n = 0; n < N; ++n) {
-                        std::complex<float>* dst = dst0 + (size_t)(n / PLEN) * B - (size_t)(n / PLEN) * PLEN;
-                        std::complex<double> u(tm[(size_t)t * N + n]);
-                        if (!d->auto_conj) u = std::conj(u);
-                        // reduce the phase in cycles before the trig call to keep full f64 accuracy
-                        double cyc = nu * (double)n;
-                        cyc -= std::floor(cyc);
-                        const double ph = 2.0 * M_PI * cyc;
-                        u *= std::complex<double>(std::cos(ph), std::sin(ph));
-                        dst[n] = std::complex<float>((float)u.real(), (float)u.imag());
+                        std::complex<float> u = tm[(size_t)t * N + n];
+                        host[((size_t)t * NP + n / PLEN) * B + n % PLEN] = d->auto_conj ? u : std::conj(u);
+                    }
+                } else {
+                    for (int f = 0; f < F; ++f) {
+                        const double nu = d->h_freqs_norm[f];
+                        std::complex<float>* dst0 = &host[((size_t)t * F + f) * NP * B];
+                        for (int n = 0; n < N; ++n) {
+                            std::complex<float>* dst = dst0 + (size_t)(n / PLEN) * B - (size_t)(n / PLEN) * PLEN;
+                            std::complex<double> u(tm[(size_t)t * N + n]);
+                            if (!d->auto_conj) u = std::conj(u);
+                            // reduce the phase in cycles before the trig call to keep full f64 accuracy
+                            double cyc = nu * (double)n;
+                            cyc -= std::floor(cyc);
+                            const double ph = 2.0 * M_PI * cyc;
+                            u *= std::complex<double>(std::cos(ph), std::sin(ph));
+                            dst[n] = std::complex<float>((float)u.real(), (float)u.imag());
+                        }
                     }
                 }
             }
+            CAF_H2D(p->d_hc, host.data(), host.size() * sizeof(std::complex<float>));
         }
-        CAF_H2D(p->d_hc, host.data(), host.size() * sizeof(std::complex<float>));
-    }
-    {
-        FftPlan tmp;
-        rc = fft_plan_acquire(&tmp, false, (size_t)B, (size_t)nspec, (size_t)B);
-        if (rc == CAF_OK) rc = tmp.exec(p->d_hc, nullptr, nullptr);
-        if (rc == CAF_OK) launch_conj_scale(p->d_hc, nspec * B, 1.0f / (float)B, nullptr);
-        if (rc == CAF_OK && p->fused && B == 65536) {
-            // the 65536-point engine reads its template-spectrum rows as pairs of the two halves of each parity, every
-            // 1024-chunk in butterfly order, which this one pass produces as well (the permutation below is skipped)
-            float2* tmp = nullptr;
-            rc = pool_alloc((void**)&tmp, nspec * (int64_t)B * 8);
-            if (rc == CAF_OK) {
-                launch_parity_pairs(p->d_hc, tmp, nspec, B / 4, nullptr);
-                if (hipMemcpyAsync(p->d_hc, tmp, (size_t)nspec * B * 8, hipMemcpyDeviceToDevice, nullptr) != hipSuccess) rc = CAF_ERR_HIP;
-                (void)hipStreamSynchronize(nullptr);
-                (void)pool_free(tmp);
-            }
+        {
+            FftPlan tmp;
+            rc = fft_plan_acquire(&tmp, false, (size_t)B, (size_t)nspec, (size_t)B);
+            if (rc == CAF_OK) rc = tmp.exec(p->d_hc, nullptr, nullptr);
+            if (rc == CAF_OK) launch_conj_scale(p->d_hc, nspec * B, 1.0f / (float)B, nullptr);
+            // the in-LDS engines read their template-spectrum rows permuted: d_hc -> a temporary of the same size -> d_hc, on the
+            // null stream, which is synchronised (a blocking Scratch) before the temporary goes back to the pool
+            auto permute_hc = [&](auto&& launch) -> int {
+                Scratch sc(nullptr, true);
+                float2* t = nullptr;
+                const int prc = sc.get(&t, nspec * (int64_t)B);
+                if (prc) return prc;
+                launch(t);
+                CAF_HIP_TRY(hipMemcpyAsync(p->d_hc, t, (size_t)nspec * B * 8, hipMemcpyDeviceToDevice, nullptr));
+                return sc.finish();
+            };
+            // 65536 points: pairs of the two halves of each parity, every 1024-chunk in butterfly order, in one pass
+            if (rc == CAF_OK && p->fused && B == 65536)
+                rc = permute_hc([&](float2* t) { launch_parity_pairs(p->d_hc, t, nspec, B / 4, nullptr); });
+            // 32768 points: parity-major (even samples, then odd samples) ...
+            if (rc == CAF_OK && p->fused && B == 32768)
+                rc = permute_hc([&](float2* t) { launch_parity_major(p->d_hc, t, nspec, B / 2, nullptr); });
+            // ... and, like 16384 points, every 1024-chunk in butterfly order (caf_fused.hip, fp_tid_of)
+            if (rc == CAF_OK && p->fused && B != 65536)
+                rc = permute_hc([&](float2* t) { launch_butterfly_order(p->d_hc, t, nspec * (int64_t)B / 1024, nullptr); });
+            hipError_t e = hipStreamSynchronize(nullptr);
+            fft_plan_release(&tmp);
+            if (rc) return rc;
+            CAF_HIP_TRY(e);
+            if ((rc = build_in.finish())) return rc;
         }
-        if (rc == CAF_OK && p->fused && B == 32768) {
-            // the 32768-point engine reads its template-spectrum rows parity-major (even samples, then odd samples)
-            float2* tmp = nullptr;
-            rc = pool_alloc((void**)&tmp, nspec * (int64_t)B * 8);
-            if (rc == CAF_OK) {
-                launch_parity_major(p->d_hc, tmp, nspec, B / 2, nullptr);
-                if (hipMemcpyAsync(p->d_hc, tmp, (size_t)nspec * B * 8, hipMemcpyDeviceToDevice, nullptr) != hipSuccess) rc = CAF_ERR_HIP;
-                (void)hipStreamSynchronize(nullptr);
-                (void)pool_free(tmp);
-            }
-        }
-        if (rc == CAF_OK && p->fused && B != 65536) {
-            // the in-LDS engines read their rows in butterfly order (caf_fused.hip, fp_tid_of): permuted once, here
-            float2* tmpb = nullptr;
-            rc = pool_alloc((void**)&tmpb, nspec * (int64_t)B * 8);
-            if (rc == CAF_OK) {
-                launch_butterfly_order(p->d_hc, tmpb, nspec * (int64_t)B / 1024, nullptr);
-                if (hipMemcpyAsync(p->d_hc, tmpb, (size_t)nspec * B * 8, hipMemcpyDeviceToDevice, nullptr) != hipSuccess) rc = CAF_ERR_HIP;
-                (void)hipStreamSynchronize(nullptr);
-                (void)pool_free(tmpb);
-            }
-        }
-        hipError_t e = hipStreamSynchronize(nullptr);
-        fft_plan_release(&tmp);
-        free_tmp();
-        if (rc) return rc;
-        CAF_HIP_TRY(e);
     }
     if (!shifts.empty())
         CAF_H2D(p->d_shifts, shifts.data(), shifts.size() * 4);
@@ -1267,35 +1243,18 @@ int32_t caf_plan_execute_host(caf_plan p, const float* h_rx, int64_t rx_len, int
         return e && atoi(e);
     }();
     const bool surf_t = h_surface && p->persistent && p->B == 16384 && F > 1 && F <= 65536 && !host_delay_major;
-    std::vector<void*> owned;
-    auto dalloc = [&](void** ptr, int64_t bytes) -> int {
-        const int prc = pool_alloc(ptr, std::max<int64_t>(bytes, 16));  // cached across calls (caf_pool.hip)
-        if (prc) return prc;
-        owned.push_back(*ptr);
-        return CAF_OK;
-    };
-    int rc = dalloc((void**)&d_rx, rx_len * 8);
-    if (!rc && h_surface) rc = dalloc((void**)(surf_t ? &o2.d_surface_t : &o.d_surface), (int64_t)T * num_shifts * F * 4);
-    if (!rc && h_row_max) rc = dalloc((void**)&o.d_row_max, (int64_t)T * num_shifts * 4);
-    if (!rc && h_row_arg) rc = dalloc((void**)&o.d_row_arg, (int64_t)T * num_shifts * 4);
-    if (!rc && h_peak_val) rc = dalloc((void**)&o.d_peak_val, T * 4);
-    if (!rc && h_peak_delay) rc = dalloc((void**)&o.d_peak_delay, T * 4);
-    if (!rc && h_peak_freq) rc = dalloc((void**)&o.d_peak_freq, T * 4);
-    auto cleanup = [&]() {
-        for (void* q : owned) (void)pool_free(q);
-    };
-    if (rc) {
-        cleanup();
-        return rc;
-    }
+    Scratch sc(nullptr);  // device copies of rx and of the outputs, cached across calls (caf_pool.hip)
+    int rc = sc.get(&d_rx, rx_len);
+    if (!rc && h_surface) rc = sc.get(surf_t ? &o2.d_surface_t : &o.d_surface, (int64_t)T * num_shifts * F);
+    if (!rc && h_row_max) rc = sc.get(&o.d_row_max, (int64_t)T * num_shifts);
+    if (!rc && h_row_arg) rc = sc.get(&o.d_row_arg, (int64_t)T * num_shifts);
+    if (!rc && h_peak_val) rc = sc.get(&o.d_peak_val, T);
+    if (!rc && h_peak_delay) rc = sc.get(&o.d_peak_delay, T);
+    if (!rc && h_peak_freq) rc = sc.get(&o.d_peak_freq, T);
     // (host arrays travel through the library's pinned staging lanes, never as pinned user pages: caf_host.cpp)
-    rc = host_h2d(d_rx, h_rx, rx_len * 8, nullptr);
+    if (!rc) rc = host_h2d(d_rx, h_rx, rx_len * 8, nullptr);
     if (!rc) rc = caf_plan_execute2(p, reinterpret_cast<const float*>(d_rx), rx_len, shift_start, num_shifts, &o2, nullptr);
-    if (rc) {
-        cleanup();
-        return rc;
-    }
-    hipError_t e = hipSuccess;
+    if (rc) return rc;
     auto back = [&](void* h, const void* dptr, int64_t bytes) {
         if (!rc && h) rc = host_d2h(h, dptr, bytes, nullptr);
     };
@@ -1311,9 +1270,7 @@ int32_t caf_plan_execute_host(caf_plan p, const float* h_rx, int64_t rx_len, int
     back(h_peak_val, o.d_peak_val, T * 4);
     back(h_peak_delay, o.d_peak_delay, T * 4);
     back(h_peak_freq, o.d_peak_freq, T * 4);
-    cleanup();
-    CAF_HIP_TRY(e);
-    return rc;
+    return rc ? rc : sc.finish();  // (the downloads are complete on return: nothing is left to wait for)
 }
 
 }  // extern "C"
