@@ -20,6 +20,33 @@ void set_error(const std::string& msg) { g_last_error = msg; }
 
 using namespace caf;
 
+// A/B and diagnostic switches read in this file (environment; integers).  "process": once, the first time the code that asks
+// is reached; "plan": in caf_plan_create; "call": in every caf_plan_execute* (the tests flip those inside one process).
+//   CAF_DIRECT                    1      process  AUTO plans take the direct engine for composite templates under 64 samples
+//   CAF_FUSED_LB15                0      process  32768-point blocks for templates of <= 8192 samples too
+//   CAF_FUSED_LB16                1      process  65536-point blocks (templates beyond 16384 samples) in the in-LDS engines
+//   CAF_FUSED_PARTS               8      process  most template partitions of 32768 samples taken (1 .. 16)
+//   CAF_FWD_ROCFFT                0      process  gather + rocFFT forward transforms instead of the in-LDS ones
+//   CAF_ENERGY_PREFIX             0      process  the separate float64-prefix pass for the window energies
+//   CAF_PERSIST_F1DIRECT          1      process  F == 1: the FFT items write the finished rows
+//   CAF_F1_ITEM_PEAKS             1      process  F == 1: ... and the peak records
+//   CAF_HOST_SURFACE_DELAY_MAJOR  0      process  caf_plan_execute_host: never the hypothesis-major launch
+//   CAF_PERSISTENT                unset  plan     AUTO plans, templates of <= 8192 samples: 0 = the two-launch engine
+//   CAF_PERSIST_WGS               CUs    plan     workgroups of the persistent launch
+//   CAF_PERSIST_TR_SLOTS          12     plan     tile-first workgroup slots per XCD (<= 31)
+//   CAF_AUX_STREAM                1      plan     window energies on an auxiliary stream
+//   CAF_HYP_PER_WG                unset  plan     hypotheses per FFT work item (1 .. 256); set at all: no sizing heuristics,
+//                                        + call   ... and none for the no-surface groups of a call
+//   CAF_PERSIST_NOSURF            1      call     (value, hypothesis) pairs instead of |y|^2 tiles when no surface is asked for
+//   CAF_PERSIST_POISON            0      call     fill the tile buffer with POISON_VT before every launch with tile items
+//   CAF_PERSIST_DEBUG             unset  call     per launch: 1 = role report of every launch, 2 = of every 10th
+//   CAF_PERSIST_TILE_ONLY         unset  call     per report: "16,64,256" = re-run the tile role alone on k workgroups
+static int env_int(const char* name, int dflt, bool* is_set = nullptr) {
+    const char* e = getenv(name);
+    if (is_set) *is_set = e != nullptr;
+    return e ? atoi(e) : dflt;
+}
+
 // CAF_PERSIST_POISON: the fill of the tile / pair buffer (~1e30 as a float; as an int32 hypothesis number far past any plan's)
 constexpr uint32_t POISON_VT = 0x7149F2CAu;
 
@@ -345,137 +372,125 @@ int32_t caf_plan_destroy(caf_plan plan) {
     return CAF_OK;
 }
 
-// Direct engine (caf_direct.hip): everything the plan needs is the list of non-zero template positions, one complex
-// multiplier per (template, hypothesis, position), the template scales, the peak records -- and what caf_zoom_czt reads.
-static int32_t plan_build_direct(caf_plan p, const caf_plan_desc* d, const std::vector<int32_t>& gs,
-                                 const std::vector<int32_t>& gl, const std::vector<int32_t>& nz) {
-    const int T = p->T, N = p->N, F = p->F, K = (int)nz.size();
-    const std::complex<float>* tm = reinterpret_cast<const std::complex<float>*>(d->h_templates);
-    p->direct = true;
-    p->dir_k = K;
-    p->B = p->step = p->nb = 0;
-    p->partial_per_tmpl = (d->max_rx_len - N + 1 + 127) / 128;  // one record per workgroup of 128 delays (caf_direct.hip)
-    std::vector<double> nu(F);
-    for (int f = 0; f < F; ++f) {
-        if (d->freq_mode == CAF_FREQ_BINS) {
-            CAF_REQUIRE(d->h_bins && d->grid >= 1, "CAF_FREQ_BINS needs bins and grid");
-            nu[f] = (double)d->h_bins[f] / (double)d->grid;
-        } else {
-            CAF_REQUIRE(d->h_freqs_norm, "CAF_FREQ_NORM needs freqs_norm");
-            nu[f] = d->h_freqs_norm[f];
-        }
+// ---- plan build: one function per step, handing each other what is not kept in the plan ----
+struct Build {
+    const caf_plan_desc* d = nullptr;
+    std::vector<int32_t> gs, gl;  // groups (support of the template for the energy normalisation)
+    std::vector<int32_t> nz;      // direct engine taken: union over the templates of their non-zero positions
+    std::vector<int32_t> shifts;  // on-grid hypotheses as circular shifts of the block spectrum
+    int fused_lb = 14;            // log2 of the in-LDS engines' block for this template length
+    int cus = 256;                // compute units (in-LDS engines; 256 only when the query fails)
+    int64_t total_blocks = 0, nspec = 0;  // blocks of max_rx_len; template spectra held (one row per partition)
+};
+
+static int32_t hyp_freqs(const caf_plan_desc* d, std::vector<double>* nu) {  // hypothesis f in cycles per sample
+    nu->resize((size_t)d->num_freqs);
+    if (d->freq_mode == CAF_FREQ_BINS) {
+        CAF_REQUIRE(d->h_bins && d->grid >= 1, "CAF_FREQ_BINS needs bins and grid");
+        for (size_t f = 0; f < nu->size(); ++f) (*nu)[f] = (double)d->h_bins[f] / (double)d->grid;
+    } else {
+        CAF_REQUIRE(d->h_freqs_norm, "CAF_FREQ_NORM needs freqs_norm");
+        for (size_t f = 0; f < nu->size(); ++f) (*nu)[f] = d->h_freqs_norm[f];
     }
-    // w[t][f][k] = conj(u_t[n_k]) exp(-j 2 pi nu_f n_k),  u = auto_conj ? tmpl : conj(tmpl)
-    std::vector<std::complex<float>> w((size_t)T * F * K);
+    return CAF_OK;
+}
+
+// Uploads shared by every engine: template scales 1 / energy, the groups, and what the zoom needs beside the coarse
+// result -- the time-domain multiplier of a product row, rx[d + n] * conj(u[n]), and the frequency of each hypothesis
+static int32_t build_scales_groups_zoom(caf_plan p, const Build& b, const std::vector<double>& nu) {
+    const int T = p->T, N = p->N;
+    const std::complex<float>* tm = reinterpret_cast<const std::complex<float>*>(b.d->h_templates);
     std::vector<float> tscale(T);
     for (int t = 0; t < T; ++t) {
         double e = 0.0;
         for (int n = 0; n < N; ++n) e += std::norm(std::complex<double>(tm[(size_t)t * N + n]));
         tscale[t] = (float)(1.0 / e);
+    }
+    std::vector<std::complex<float>> uc((size_t)T * N);
+    for (size_t i = 0; i < uc.size(); ++i) uc[i] = b.d->auto_conj ? std::conj(tm[i]) : tm[i];
+    int rc;
+    if ((rc = p->alloc(&p->d_uconj, (int64_t)T * N)) || (rc = p->alloc(&p->d_nu, p->F))) return rc;
+    CAF_H2D(p->d_tscale, tscale.data(), (size_t)T * 4);
+    CAF_H2D(p->d_uconj, uc.data(), uc.size() * 8);
+    CAF_H2D(p->d_nu, nu.data(), nu.size() * 8);
+    CAF_H2D(p->d_gstart, b.gs.data(), b.gs.size() * 4);
+    CAF_H2D(p->d_glen, b.gl.data(), b.gl.size() * 4);
+    return CAF_OK;
+}
+
+// Direct engine (caf_direct.hip): everything the plan needs is the list of non-zero template positions, one complex
+// multiplier per (template, hypothesis, position), the template scales, the peak records -- and what caf_zoom_czt reads.
+static int32_t plan_build_direct(caf_plan p, const Build& b) {
+    const caf_plan_desc* d = b.d;
+    const int T = p->T, N = p->N, F = p->F, K = (int)b.nz.size();
+    const std::complex<float>* tm = reinterpret_cast<const std::complex<float>*>(d->h_templates);
+    p->direct = true;
+    p->dir_k = K;
+    p->B = p->step = p->nb = 0;
+    p->partial_per_tmpl = (d->max_rx_len - N + 1 + 127) / 128;  // one record per workgroup of 128 delays (caf_direct.hip)
+    std::vector<double> nu;
+    int rc;
+    if ((rc = hyp_freqs(d, &nu))) return rc;
+    // w[t][f][k] = conj(u_t[n_k]) exp(-j 2 pi nu_f n_k),  u = auto_conj ? tmpl : conj(tmpl)
+    std::vector<std::complex<float>> w((size_t)T * F * K);
+    for (int t = 0; t < T; ++t)
         for (int f = 0; f < F; ++f)
             for (int k = 0; k < K; ++k) {
-                std::complex<double> u(tm[(size_t)t * N + nz[k]]);
+                std::complex<double> u(tm[(size_t)t * N + b.nz[k]]);
                 if (d->auto_conj) u = std::conj(u);  // conj(u) with u = tmpl
-                double cyc = nu[f] * (double)nz[k];
+                double cyc = nu[f] * (double)b.nz[k];
                 cyc -= std::floor(cyc);  // phase reduced in cycles before the trig call
                 const double ph = -2.0 * M_PI * cyc;
                 u *= std::complex<double>(std::cos(ph), std::sin(ph));
                 w[((size_t)t * F + f) * K + k] = std::complex<float>((float)u.real(), (float)u.imag());
             }
-    }
-    int rc;
     if ((rc = p->alloc(&p->d_dir_pos, K)) || (rc = p->alloc(&p->d_dir_w, (int64_t)T * F * K)) || (rc = p->alloc(&p->d_tscale, T)) ||
         (rc = p->alloc(&p->d_partial, (int64_t)T * p->partial_per_tmpl + (int64_t)T * PEAK_PARTS)) ||
-        (rc = p->alloc(&p->d_gstart, p->G)) || (rc = p->alloc(&p->d_glen, p->G)) || (rc = p->alloc(&p->d_uconj, (int64_t)T * N)) ||
-        (rc = p->alloc(&p->d_nu, F)))
+        (rc = p->alloc(&p->d_gstart, p->G)) || (rc = p->alloc(&p->d_glen, p->G)))
         return rc;
-    std::vector<std::complex<float>> uc((size_t)T * N);
-    for (size_t i = 0; i < uc.size(); ++i) uc[i] = d->auto_conj ? std::conj(tm[i]) : tm[i];
-    CAF_H2D(p->d_dir_pos, nz.data(), (size_t)K * 4);
+    CAF_H2D(p->d_dir_pos, b.nz.data(), (size_t)K * 4);
     CAF_H2D(p->d_dir_w, w.data(), w.size() * 8);
-    CAF_H2D(p->d_tscale, tscale.data(), (size_t)T * 4);
-    CAF_H2D(p->d_gstart, gs.data(), gs.size() * 4);
-    CAF_H2D(p->d_glen, gl.data(), gl.size() * 4);
-    CAF_H2D(p->d_uconj, uc.data(), uc.size() * 8);
-    CAF_H2D(p->d_nu, nu.data(), nu.size() * 8);
-    return CAF_OK;
+    return build_scales_groups_zoom(p, b, nu);
 }
 
-static int32_t plan_build(caf_plan p, const caf_plan_desc* d) {
-    CAF_REQUIRE(d->num_templates >= 1 && d->template_len >= 1 && d->h_templates, "need >= 1 template");
-    CAF_REQUIRE(d->num_freqs >= 1, "need >= 1 frequency hypothesis");
-    CAF_REQUIRE(d->max_rx_len >= d->template_len, "max_rx_len shorter than the template");
-    CAF_REQUIRE(d->max_rx_len < ((int64_t)1 << 31) - (1 << 20), "rx longer than 2^31 samples is not supported");
-    CAF_REQUIRE(d->freq_mode == CAF_FREQ_BINS || d->freq_mode == CAF_FREQ_NORM, "bad freq_mode");
-    CAF_HIP_TRY(hipGetDevice(&p->device));
-    p->T = d->num_templates;
-    p->N = d->template_len;
-    p->F = d->num_freqs;
-    p->freq_mode = d->freq_mode;
-    p->max_rx = d->max_rx_len;
+// Engine and block choice: sets p->fused / p->persistent and b->fused_lb, or fills b->nz when the direct engine is taken
+static int32_t build_choose_engine(caf_plan p, Build* b) {
+    const caf_plan_desc* d = b->d;
     const int T = p->T, N = p->N, F = p->F;
-
-    // groups (support of the template for the energy normalisation)
-    std::vector<int32_t> gs, gl;
-    if (d->num_groups >= 1 && d->h_group_start && d->h_group_len) {
-        gs.assign(d->h_group_start, d->h_group_start + d->num_groups);
-        gl.assign(d->h_group_len, d->h_group_len + d->num_groups);
-    } else {
-        gs = {0};
-        gl = {N};
-    }
-    p->G = (int)gs.size();
-    for (int g = 0; g < p->G; ++g)
-        CAF_REQUIRE(gs[g] >= 0 && gl[g] >= 1 && (int64_t)gs[g] + gl[g] <= N, "group outside the template span");
-
-    // engine: the fused LDS-resident kernel works on 16384-point blocks
     CAF_REQUIRE(d->engine >= CAF_ENGINE_AUTO && d->engine <= CAF_ENGINE_DIRECT && d->reserved == 0, "bad engine field");
-    {   // the direct engine: asked for, or chosen for composite templates whose groups cover fewer than 64 samples
-        int64_t support = 0;
-        for (int g = 0; g < p->G; ++g) support += gl[g];
-        static const bool auto_direct = [] {
-            const char* e = getenv("CAF_DIRECT");  // A/B switch for AUTO plans, default on
-            return !e || atoi(e);
-        }();
-        const bool composite = d->num_groups >= 1 && d->h_group_start && d->h_group_len;
-        if (d->engine == CAF_ENGINE_DIRECT || (d->engine == CAF_ENGINE_AUTO && auto_direct && composite && support < 64)) {
-            const std::complex<float>* tm0 = reinterpret_cast<const std::complex<float>*>(d->h_templates);
-            std::vector<int32_t> nz;  // union over the templates of their non-zero positions
-            for (int n = 0; n < N && nz.size() <= 64; ++n)
-                for (int t = 0; t < T; ++t)
-                    if (tm0[(size_t)t * N + n] != std::complex<float>(0.f, 0.f)) {
-                        nz.push_back(n);
-                        break;
-                    }
-            const bool ok = !nz.empty() && nz.size() <= 64;
-            CAF_REQUIRE(d->engine != CAF_ENGINE_DIRECT || ok, "the direct engine needs 1 .. 64 non-zero template samples");
-            if (ok) return plan_build_direct(p, d, gs, gl, nz);
-        }
+    // the direct engine: asked for, or chosen for composite templates whose groups cover fewer than 64 samples
+    int64_t support = 0;
+    for (int g = 0; g < p->G; ++g) support += b->gl[g];
+    static const bool auto_direct = env_int("CAF_DIRECT", 1) != 0;  // A/B switch for AUTO plans
+    const bool composite = d->num_groups >= 1 && d->h_group_start && d->h_group_len;
+    if (d->engine == CAF_ENGINE_DIRECT || (d->engine == CAF_ENGINE_AUTO && auto_direct && composite && support < 64)) {
+        const std::complex<float>* tm0 = reinterpret_cast<const std::complex<float>*>(d->h_templates);
+        std::vector<int32_t>& nz = b->nz;
+        for (int n = 0; n < N && nz.size() <= 64; ++n)
+            for (int t = 0; t < T; ++t)
+                if (tm0[(size_t)t * N + n] != std::complex<float>(0.f, 0.f)) {
+                    nz.push_back(n);
+                    break;
+                }
+        const bool ok = !nz.empty() && nz.size() <= 64;
+        CAF_REQUIRE(d->engine != CAF_ENGINE_DIRECT || ok, "the direct engine needs 1 .. 64 non-zero template samples");
+        if (ok) return CAF_OK;
+        nz.clear();
     }
     // the LDS-resident engines: 16384-point blocks for templates up to 8192 samples, 32768-point blocks (two chained
     // 16384-point transforms per hypothesis, persistent engine only) up to 16384
     // (CAF_FUSED_LB15=1: 32768-point blocks for the shorter templates too -- A/B switch: 87.5 % valid outputs per block at
     //  N = 4096 instead of 75 %, against the dearer half-transforms of the 32768-point role)
-    static const bool lb15_env = [] {
-        const char* e = getenv("CAF_FUSED_LB15");
-        return e && atoi(e);
-    }();
+    static const bool lb15_env = env_int("CAF_FUSED_LB15", 0) != 0;
     // (templates of 16385 .. 32768 samples: 65536-point blocks in the folded form, two chained transforms per output residue,
     //  fused_item2q<FOLD>; CAF_FUSED_LB16=0 sends them to the rocfft engine as before -- A/B switch)
-    static const bool lb16_env = [] {
-        const char* e = getenv("CAF_FUSED_LB16");
-        return !e || atoi(e);
-    }();
+    static const bool lb16_env = env_int("CAF_FUSED_LB16", 1) != 0;
     // (templates of 32769 .. 262144 samples: the same 65536-point blocks with the template cut into partitions of 32768
     //  samples -- Z_b = sum_p X_{b + p} . Hc_p, the frequency-domain delay line of partitioned convolution: the products of the
     //  item's block and of the blocks that follow it with the partitions' spectra are summed before the one inverse transform,
     //  fused_item2q<PART>; CAF_FUSED_PARTS = the largest number of partitions taken, 1 sends them to the rocfft engine -- A/B switch)
-    static const int max_parts = [] {
-        const char* e = getenv("CAF_FUSED_PARTS");
-        return e ? std::min(std::max(atoi(e), 1), 16) : 8;
-    }();
-    const int fused_lb = (N <= 8192 && !lb15_env) ? 14 : N <= 16384 ? 15 : 16;
-    const int fused_parts = fused_lb == 16 ? (N + 32767) / 32768 : 1;
+    static const int max_parts = std::min(std::max(env_int("CAF_FUSED_PARTS", 8), 1), 16);
+    const int fused_lb = b->fused_lb = (N <= 8192 && !lb15_env) ? 14 : N <= 16384 ? 15 : 16;
     // on-grid hypotheses are circular shifts of one template spectrum: every bin must land on a whole element of the engine's
     // block (any grid that divides 16384 does; so does bin 0 on any grid), an even one where the rows are read parity-major
     const bool bins_fit = [&] {
@@ -499,11 +514,19 @@ static int32_t plan_build(caf_plan p, const caf_plan_desc* d) {
     // hypotheses with hardware bounds handling, a streaming path for F == 1) and was faster than the two-launch
     // form on every measured shape (C2 1.15x, C4 share 1.25x, C3 with 64 templates and no frequency scan ~10x)
     p->persistent = d->engine == CAF_ENGINE_PERSISTENT || (d->engine == CAF_ENGINE_AUTO && fused_ok);
-    if (const char* e = getenv("CAF_PERSISTENT"))  // A/B switch for AUTO plans
-        if (d->engine == CAF_ENGINE_AUTO && fused_ok && N <= 8192) p->persistent = atoi(e) != 0;
+    bool set = false;
+    const int persistent_env = env_int("CAF_PERSISTENT", 0, &set);  // A/B switch for AUTO plans
+    if (set && d->engine == CAF_ENGINE_AUTO && fused_ok && N <= 8192) p->persistent = persistent_env != 0;
+    p->npart = p->fused && fused_lb == 16 ? (N + 32767) / 32768 : 1;
+    return CAF_OK;
+}
 
+// Block geometry (B, step, pitch) and the frequency hypotheses as shifts of the block spectrum
+static int32_t build_block(caf_plan p, Build* b) {
+    const caf_plan_desc* d = b->d;
+    const int N = p->N, F = p->F;
     // block size: B = 2^k, B >= 2N (>= 50 % valid outputs); default 16 N clipped to [2^12, 2^18]
-    int lb = p->fused ? fused_lb : d->log2_block;
+    int lb = p->fused ? b->fused_lb : d->log2_block;
     const int lmin = ilog2_ceil(2 * (int64_t)N);
     if (lb <= 0) {
         lb = std::min(std::max(ilog2_ceil(16 * (int64_t)N), 12), 18);
@@ -511,7 +534,6 @@ static int32_t plan_build(caf_plan p, const caf_plan_desc* d) {
         lb = std::min(lb, std::max(ilog2_ceil(d->max_rx_len), 12));
         lb = std::max(lb, lmin);
     }
-    p->npart = p->fused ? fused_parts : 1;
     CAF_REQUIRE((lb >= lmin || p->npart > 1) && lb <= 24, "log2_block must satisfy 2N <= 2^log2_block <= 2^24");
     lb = std::max(lb, 9);  // the multiply kernel tiles 512 points per workgroup
     p->B = 1 << lb;
@@ -526,20 +548,20 @@ static int32_t plan_build(caf_plan p, const caf_plan_desc* d) {
     // 32768 delays whatever the template length in (16384, 32768]
     if (p->fused && lb == 16) p->step = 32768;
     p->pitch = p->B + 64;  // break the power-of-two stride between hypothesis rows
-    const int B = p->B;
+    p->tiles_per_blk = (p->step + MAG_S - 1) / MAG_S;
+    b->total_blocks = (d->max_rx_len - N + 1 + p->step - 1) / p->step;
 
     // frequency hypotheses
-    std::vector<int32_t> shifts;
-    bool all_even = true;
     if (d->freq_mode == CAF_FREQ_BINS) {
         CAF_REQUIRE(d->h_bins && d->grid >= 1, "CAF_FREQ_BINS needs bins and grid");
-        shifts.resize(F);
+        bool all_even = true;
+        b->shifts.resize(F);
         for (int f = 0; f < F; ++f) {
-            const int64_t num = (int64_t)d->h_bins[f] * B;
+            const int64_t num = (int64_t)d->h_bins[f] * p->B;
             CAF_REQUIRE(num % d->grid == 0, "every bin must be a whole number of elements of the block: bins * block_size / grid (use CAF_FREQ_NORM otherwise)");
-            int64_t s = (num / d->grid) % B;
-            if (s < 0) s += B;
-            shifts[f] = (int32_t)s;
+            int64_t s = (num / d->grid) % p->B;
+            if (s < 0) s += p->B;
+            b->shifts[f] = (int32_t)s;
             if (s & 1) all_even = false;
         }
         p->mul_mode = all_even ? 0 : 1;
@@ -547,219 +569,257 @@ static int32_t plan_build(caf_plan p, const caf_plan_desc* d) {
         CAF_REQUIRE(d->h_freqs_norm, "CAF_FREQ_NORM needs freqs_norm");
         p->mul_mode = 2;
     }
-    const int NP = p->npart, PLEN = NP > 1 ? 32768 : N;  // partitions per template and their length (one partition: the template)
-    const int64_t nspec = ((p->mul_mode == 2) ? (int64_t)T * F : T) * NP;  // template spectra held (one row per partition)
+    b->nspec = ((p->mul_mode == 2) ? (int64_t)p->T * F : p->T) * p->npart;
+    return CAF_OK;
+}
 
+// Hypotheses per FFT work item
+static int choose_hyp_per_wg(const caf_plan_t* p, const Build& b) {
+    const int64_t TF = (int64_t)p->T * p->F;
+    const int F = p->F, cus = b.cus;
+    int hpw = (int)std::min<int64_t>(p->fused ? 64 : 16, TF);
+    bool forced = false;
+    const int hpw_env = env_int("CAF_HYP_PER_WG", 0, &forced);  // A/B switch; set at all: the heuristics below stand back
+    if (hpw_env >= 1) hpw = (int)std::min<int64_t>(std::min(hpw_env, 256), TF);
+    if (!p->fused) return hpw;
+    // small jobs: fewer hypotheses per FFT work item, so that there are about two items per CU when the job
+    // allows it (one block x 32 hypotheses as ONE item kept 255 CUs idle for 0.25 ms)
+    const int64_t want = (TF * b.total_blocks + 2 * cus - 1) / (2 * cus);
+    hpw = (int)std::min<int64_t>(hpw, std::max<int64_t>(4, want));
+    // whole rounds: 1365 items of 64 hypotheses on 256 CUs are 5.33 rounds, i.e. 6 with a third of the chip idle in
+    // the last one (config C3); halve the items while that buys more than the extra block-spectrum loads cost
+    if (!forced) {
+        auto eff = [&](int hp) {
+            const int64_t items = ((TF + hp - 1) / hp) * b.total_blocks;
+            const int64_t rounds = (items + cus - 1) / cus;
+            return (double)items / (double)(rounds * cus);
+        };
+        int best = hpw;
+        for (int hp = best / 2; hp >= 16; hp /= 2)
+            if (eff(hp) > eff(best) + 0.03) best = hp;
+        hpw = best;
+    }
+    // 65536-point blocks: the role re-reads its block spectrum per sub-transform whatever the item size, and smaller items
+    // keep fewer blocks (512 KB of spectrum each) in flight per XCD: 44.8 -> 43.5 ms at the C2 shape with 32 (16: 43.3)
+    // (partitioned templates read npart block spectra and npart template rows per sub-transform: smaller items again -- 16
+    //  hypotheses at 2 .. 5 partitions (35.7 -> 34.9 ms at two, 59.1 -> 58.1 at four), 8 beyond (127.9 -> 120.8 ms at eight))
+    if (p->B == 65536 && !forced) hpw = std::min(hpw, p->npart >= 6 ? 8 : p->npart > 1 ? 16 : 32);
+    // groups that do not straddle templates allow the no-surface mode (running maxima instead of tiles):
+    // prefer the largest divisor of F that is not much smaller than the group size chosen above
+    if (F % hpw != 0)
+        for (int dv = hpw; dv >= std::max(4, hpw / 3); --dv)
+            if (F % dv == 0) return dv;
+    return hpw;
+}
+
+// "No-surface pairs fit": groups per template with which the persistent engine can keep one (value, hypothesis) pair per
+// delay and hypothesis GROUP in the tile buffer instead of one value per delay and hypothesis; 0 where it cannot.  Needs groups
+// that do not straddle templates, and the two pair arrays must fit the tiles they replace (>= 2 hypotheses per group).
+static int nosurf_groups_per_tmpl(const caf_plan_t* p) {
+    if (!p->persistent || p->B != 16384 || p->F < p->hyp_per_wg) return 0;
+    const int gpt = (p->F + p->hyp_per_wg - 1) / p->hyp_per_wg;
+    return 2 * (int64_t)gpt <= p->F ? gpt : 0;
+}
+// "Writes the hypothesis-major surface": the persistent engine with 16384-point blocks (templates of at most 8192 samples)
+static bool writes_surface_t(const caf_plan_t* p) { return p->persistent && p->B == 16384; }
+// floats of the tile buffer d_vt for `blocks` blocks of `rows` hypotheses (|y|^2 tiles) or pair groups (vmax, then imax)
+static int64_t vt_floats(const caf_plan_t* p, int64_t blocks, int64_t rows) { return blocks * p->tiles_per_blk * rows * 64; }
+
+// Blocks per launch, padded block count, hypotheses per work item, blocks per no-surface launch
+static void build_batch(caf_plan p, const Build& b) {
+    const int T = p->T, F = p->F;
     // batch: aim at ~128 MiB of hypothesis products in flight
-    const int64_t total_blocks = (d->max_rx_len - N + 1 + p->step - 1) / p->step;
-    p->tiles_per_blk = (p->step + MAG_S - 1) / MAG_S;
-    int nb = d->blocks_per_batch;
+    int nb = b.d->blocks_per_batch;
     if (nb <= 0) {
         if (p->fused) {
             // |y|^2 tiles of a batch: up to 18 GiB of the 288 GB HBM, so that config C2 (17.3 GB) is ONE
             // launch of 5460 workgroups (21.3 rounds over 256 CUs: small tail) instead of many short ones
-            const int64_t per_block = (int64_t)p->tiles_per_blk * T * F * 64 * 4;
+            const int64_t per_block = vt_floats(p, 1, (int64_t)T * F) * 4;
             nb = (int)std::max<int64_t>(1, std::min<int64_t>(65535, ((int64_t)18 << 30) / per_block));
         } else {
             const int64_t per_block = (int64_t)T * F * p->pitch * 8;
             nb = (int)std::max<int64_t>(1, std::min<int64_t>(64, ((int64_t)128 << 20) / per_block));
         }
     }
-    nb = (int)std::min<int64_t>(nb, std::max<int64_t>(1, total_blocks));
+    nb = (int)std::min<int64_t>(nb, std::max<int64_t>(1, b.total_blocks));
     p->nb = nb;
-    p->max_blocks = (total_blocks + nb - 1) / nb * nb;
+    p->max_blocks = (b.total_blocks + nb - 1) / nb * nb;
     p->partial_per_tmpl = p->max_blocks * p->tiles_per_blk;
-    p->hyp_per_wg = (int)std::min<int64_t>(p->fused ? 64 : 16, (int64_t)T * F);
-    if (const char* e = getenv("CAF_HYP_PER_WG"))  // A/B switch: hypotheses per FFT work item
-        if (atoi(e) >= 1) p->hyp_per_wg = (int)std::min<int64_t>(std::min(atoi(e), 256), (int64_t)T * F);
-    if (p->fused) {
-        // small jobs: fewer hypotheses per FFT work item, so that there are about two items per CU when the job
-        // allows it (one block x 32 hypotheses as ONE item kept 255 CUs idle for 0.25 ms)
-        int cus = 256;
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device);
-        const int64_t want = ((int64_t)T * F * total_blocks + 2 * cus - 1) / (2 * cus);
-        p->hyp_per_wg = (int)std::min<int64_t>(p->hyp_per_wg, std::max<int64_t>(4, want));
-        // whole rounds: 1365 items of 64 hypotheses on 256 CUs are 5.33 rounds, i.e. 6 with a third of the chip idle in
-        // the last one (config C3); halve the items while that buys more than the extra block-spectrum loads cost
-        if (!getenv("CAF_HYP_PER_WG")) {
-            auto eff = [&](int hp) {
-                const int64_t items = (((int64_t)T * F + hp - 1) / hp) * total_blocks;
-                const int64_t rounds = (items + cus - 1) / cus;
-                return (double)items / (double)(rounds * cus);
-            };
-            int best = p->hyp_per_wg;
-            for (int hp = best / 2; hp >= 16; hp /= 2)
-                if (eff(hp) > eff(best) + 0.03) best = hp;
-            p->hyp_per_wg = best;
-        }
-        // 65536-point blocks: the role re-reads its block spectrum per sub-transform whatever the item size, and smaller items
-        // keep fewer blocks (512 KB of spectrum each) in flight per XCD: 44.8 -> 43.5 ms at the C2 shape with 32 (16: 43.3)
-        // (partitioned templates read npart block spectra and npart template rows per sub-transform: smaller items again -- 16
-        //  hypotheses at 2 .. 5 partitions (35.7 -> 34.9 ms at two, 59.1 -> 58.1 at four), 8 beyond (127.9 -> 120.8 ms at eight))
-        if (lb == 16 && !getenv("CAF_HYP_PER_WG")) p->hyp_per_wg = std::min(p->hyp_per_wg, p->npart >= 6 ? 8 : p->npart > 1 ? 16 : 32);
-        // groups that do not straddle templates allow the no-surface mode (running maxima instead of tiles):
-        // prefer the largest divisor of F that is not much smaller than the group size chosen above
-        if (F % p->hyp_per_wg != 0)
-            for (int dv = p->hyp_per_wg; dv >= std::max(4, p->hyp_per_wg / 3); --dv)
-                if (F % dv == 0) {
-                    p->hyp_per_wg = dv;
-                    break;
-                }
-    }
-
-    // No-surface mode of the persistent engine: one (value, hypothesis) pair per delay and hypothesis GROUP lives in
-    // the tile buffer instead of one value per delay and hypothesis, so the same buffer holds hyp_per_wg / 2 times
-    // as many blocks per launch (config C4's 512 templates x 512 bins on one GPU: 32 blocks instead of 1; fewer,
-    // longer launches = fewer drain tails where the last blocks' reductions run on a handful of CUs).
+    p->hyp_per_wg = choose_hyp_per_wg(p, b);
+    // No-surface mode of the persistent engine: the same buffer holds hyp_per_wg / 2 times as many blocks per launch
+    // (config C4's 512 templates x 512 bins on one GPU: 32 blocks instead of 1; fewer, longer launches = fewer drain
+    // tails where the last blocks' reductions run on a handful of CUs).
     p->nb_nosurf = nb;
-    if (p->persistent && p->B == 16384 && F >= p->hyp_per_wg) {
-        const int64_t gpt = (F + p->hyp_per_wg - 1) / p->hyp_per_wg;
-        if (2 * gpt <= F) {
-            const int64_t cap = (int64_t)nb * F / (2 * gpt);  // nb_nosurf * 2 * T * gpt <= nb * T * F pairs
-            p->nb_nosurf = (int)std::max<int64_t>(nb, std::min<int64_t>(std::min<int64_t>(cap, 4096), std::max<int64_t>(1, total_blocks)));
-        }
+    if (const int64_t gpt = nosurf_groups_per_tmpl(p)) {
+        const int64_t cap = (int64_t)nb * F / (2 * gpt);  // nb_nosurf * 2 * T * gpt <= nb * T * F pairs
+        p->nb_nosurf = (int)std::max<int64_t>(nb, std::min<int64_t>(std::min<int64_t>(cap, 4096), std::max<int64_t>(1, b.total_blocks)));
     }
+}
 
-    // device buffers
+static int32_t build_buffers(caf_plan p, const Build& b) {
+    const int T = p->T, F = p->F, NP = p->npart;
+    const int64_t B = p->B, max_rx = b.d->max_rx_len;
     int rc;
-    if ((rc = p->alloc(&p->d_hc, nspec * B))) return rc;
+    if ((rc = p->alloc(&p->d_hc, b.nspec * B))) return rc;
     if ((rc = p->alloc(&p->d_shifts, std::max(F, 1)))) return rc;
     if ((rc = p->alloc(&p->d_tscale, T))) return rc;
     if ((rc = p->alloc(&p->d_gstart, p->G))) return rc;
     if ((rc = p->alloc(&p->d_glen, p->G))) return rc;
-    if ((rc = p->alloc(&p->d_tile_sums, prefix_num_tiles(d->max_rx_len) + 1024))) return rc;
-    if ((rc = p->alloc(&p->d_prefix, energy_prefix_doubles(d->max_rx_len)))) return rc;
-    if ((rc = p->alloc(&p->d_inv_e, d->max_rx_len))) return rc;
+    if ((rc = p->alloc(&p->d_tile_sums, prefix_num_tiles(max_rx) + 1024))) return rc;
+    if ((rc = p->alloc(&p->d_prefix, energy_prefix_doubles(max_rx)))) return rc;
+    if ((rc = p->alloc(&p->d_inv_e, max_rx))) return rc;
     // all rx block spectra are produced up front, fwd_chunk blocks per rocFFT launch
     // (~32 MiB of spectra per forward launch: 256 blocks of 16384, 64 blocks of 65536, ...)
     p->fwd_chunk = (int)std::min<int64_t>(std::max<int64_t>(1, ((int64_t)1 << 22) / B), p->max_blocks);
     if ((rc = p->alloc(&p->d_xb, (p->max_blocks + NP - 1 + p->fwd_chunk) * B))) return rc;
-    if (p->fused && p->B >= 32768 && (rc = p->alloc(&p->d_xb2, (p->max_blocks + NP - 1 + p->fwd_chunk) * B))) return rc;
+    if (p->fused && B >= 32768 && (rc = p->alloc(&p->d_xb2, (p->max_blocks + NP - 1 + p->fwd_chunk) * B))) return rc;
     if (p->fused) {
-        if ((rc = p->alloc(&p->d_vt, (int64_t)nb * p->tiles_per_blk * T * F * 64))) return rc;
+        if ((rc = p->alloc(&p->d_vt, vt_floats(p, p->nb, (int64_t)T * F)))) return rc;
         if ((rc = fused_twiddles(p->device, &p->d_tw1, &p->d_tw23))) return rc;  // per device, shared by all plans
         if (p->persistent) {
-            int ncu = 0;  // (hipGetDeviceProperties costs ~1 ms per call; the attribute query does not)
-            CAF_HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, p->device));
-            p->n_cus = ncu;  // one resident 1024-thread workgroup per CU
-            p->tr_slots = 12;                     // 96 CUs look at the tile queue first (measured optimum on C2: 10..14)
-            if (const char* e = getenv("CAF_PERSIST_WGS")) p->n_cus = std::max(1, atoi(e));
-            if (const char* e = getenv("CAF_PERSIST_TR_SLOTS")) p->tr_slots = std::max(0, atoi(e));
+            p->n_cus = std::max(1, env_int("CAF_PERSIST_WGS", b.cus));  // one resident 1024-thread workgroup per CU
+            // 96 CUs look at the tile queue first (measured optimum on C2: 10..14)
+            p->tr_slots = std::max(0, env_int("CAF_PERSIST_TR_SLOTS", 12));
             p->tr_slots = std::min(p->tr_slots, 31);  // slot 0 of every XCD never prefers tiles (termination argument)
             if ((rc = p->alloc(&p->d_params, 1))) return rc;
-            if ((rc = p->alloc(&p->d_pq, 12 + std::max(nb, p->nb_nosurf)))) return rc;
+            if ((rc = p->alloc(&p->d_pq, 12 + std::max(p->nb, p->nb_nosurf)))) return rc;
         }
     } else {
-        if ((rc = p->alloc(&p->d_pbuf, (int64_t)nb * T * F * p->pitch))) return rc;
+        if ((rc = p->alloc(&p->d_pbuf, (int64_t)p->nb * T * F * p->pitch))) return rc;
     }
     // tile records + PEAK_PARTS records per template for the two-stage reduction
-    if ((rc = p->alloc(&p->d_partial, (int64_t)T * p->partial_per_tmpl + (int64_t)T * PEAK_PARTS))) return rc;
+    return p->alloc(&p->d_partial, (int64_t)T * p->partial_per_tmpl + (int64_t)T * PEAK_PARTS);
+}
 
-    // template spectra: u = auto_conj ? tmpl : conj(tmpl);  u_f[n] = u[n] exp(+j 2 pi nu_f n);
-    // Hc = conj(FFT_B(u_f)) / B  (rocFFT's inverse is unnormalised, 1/B is folded in here)
-    std::vector<float> tscale(T);
+// template spectra: u = auto_conj ? tmpl : conj(tmpl);  u_f[n] = u[n] exp(+j 2 pi nu_f n);
+// Hc = conj(FFT_B(u_f)) / B  (rocFFT's inverse is unnormalised, 1/B is folded in here)
+static int32_t build_template_spectra(caf_plan p, const Build& b) {
+    const caf_plan_desc* d = b.d;
+    const int T = p->T, N = p->N, F = p->F, B = p->B;
+    const int NP = p->npart, PLEN = NP > 1 ? 32768 : N;  // partitions per template and their length (one partition: the template)
+    const int64_t nspec = b.nspec;
     const std::complex<float>* tm = reinterpret_cast<const std::complex<float>*>(d->h_templates);
-    for (int t = 0; t < T; ++t) {
-        double e = 0.0;
-        for (int n = 0; n < N; ++n) e += std::norm(std::complex<double>(tm[(size_t)t * N + n]));
-        tscale[t] = (float)(1.0 / e);
-    }
-    {  // template spectra on the device; the inputs of the table build go back to the pool at the end of this block
-        Scratch build_in(nullptr);  // inputs of the device-side table build, in use until the synchronisation below
-        if (p->mul_mode == 2 && T <= 65535) {
-            // explicit frequencies: the T*F modulated templates are generated on the device (k_build_hyp_time)
-            float2* tmp_tm = nullptr;
-            double* tmp_nu = nullptr;
-            if ((rc = build_in.get(&tmp_tm, (int64_t)T * N)) || (rc = build_in.get(&tmp_nu, F))) return rc;
-            if ((rc = host_h2d(tmp_tm, tm, (int64_t)T * N * 8, nullptr)) || (rc = host_h2d(tmp_nu, d->h_freqs_norm, (int64_t)F * 8, nullptr)))
-                return rc;
-            launch_build_hyp_time(tmp_tm, tmp_nu, N, B, F, T, d->auto_conj ? 0 : 1, p->d_hc, nullptr, NP, PLEN);
-        } else {
-            std::vector<std::complex<float>> host((size_t)nspec * B, std::complex<float>(0.f, 0.f));
-            for (int t = 0; t < T; ++t) {
-                // (row of partition q of a spectrum: the samples q * PLEN .. of the template at the row's start; the on-grid shifts
-                //  need no phase per partition: an even shift at 65536 points makes nu * 32768 q a whole number of cycles)
-                if (p->mul_mode != 2) {
+    int rc;
+    Scratch build_in(nullptr);  // inputs of the device-side table build, in use until the synchronisation below
+    if (p->mul_mode == 2 && T <= 65535) {
+        // explicit frequencies: the T*F modulated templates are generated on the device (k_build_hyp_time)
+        float2* tmp_tm = nullptr;
+        double* tmp_nu = nullptr;
+        if ((rc = build_in.get(&tmp_tm, (int64_t)T * N)) || (rc = build_in.get(&tmp_nu, F))) return rc;
+        if ((rc = host_h2d(tmp_tm, tm, (int64_t)T * N * 8, nullptr)) || (rc = host_h2d(tmp_nu, d->h_freqs_norm, (int64_t)F * 8, nullptr)))
+            return rc;
+        launch_build_hyp_time(tmp_tm, tmp_nu, N, B, F, T, d->auto_conj ? 0 : 1, p->d_hc, nullptr, NP, PLEN);
+    } else {
+        std::vector<std::complex<float>> host((size_t)nspec * B, std::complex<float>(0.f, 0.f));
+        for (int t = 0; t < T; ++t) {
+            // (row of partition q of a spectrum: the samples q * PLEN .. of the template at the row's start; the on-grid shifts
+            //  need no phase per partition: an even shift at 65536 points makes nu * 32768 q a whole number of cycles)
+            if (p->mul_mode != 2) {
+                for (int n = 0; n < N; ++n) {
+                    std::complex<float> u = tm[(size_t)t * N + n];
+                    host[((size_t)t * NP + n / PLEN) * B + n % PLEN] = d->auto_conj ? u : std::conj(u);
+                }
+            } else {
+                for (int f = 0; f < F; ++f) {
+                    const double nu = d->h_freqs_norm[f];
+                    std::complex<float>* dst0 = &host[((size_t)t * F + f) * NP * B];
                     for (int n = 0; n < N; ++n) {
-                        std::complex<float> u = tm[(size_t)t * N + n];
-                        host[((size_t)t * NP + n / PLEN) * B + n % PLEN] = d->auto_conj ? u : std::conj(u);
-                    }
-                } else {
-                    for (int f = 0; f < F; ++f) {
-                        const double nu = d->h_freqs_norm[f];
-                        std::complex<float>* dst0 = &host[((size_t)t * F + f) * NP * B];
-                        for (int n = 0; n < N; ++n) {
-                            std::complex<float>* dst = dst0 + (size_t)(n / PLEN) * B - (size_t)(n / PLEN) * PLEN;
-                            std::complex<double> u(tm[(size_t)t * N + n]);
-                            if (!d->auto_conj) u = std::conj(u);
-                            // reduce the phase in cycles before the trig call to keep full f64 accuracy
-                            double cyc = nu * (double)n;
-                            cyc -= std::floor(cyc);
-                            const double ph = 2.0 * M_PI * cyc;
-                            u *= std::complex<double>(std::cos(ph), std::sin(ph));
-                            dst[n] = std::complex<float>((float)u.real(), (float)u.imag());
-                        }
+                        std::complex<float>* dst = dst0 + (size_t)(n / PLEN) * B - (size_t)(n / PLEN) * PLEN;
+                        std::complex<double> u(tm[(size_t)t * N + n]);
+                        if (!d->auto_conj) u = std::conj(u);
+                        // reduce the phase in cycles before the trig call to keep full f64 accuracy
+                        double cyc = nu * (double)n;
+                        cyc -= std::floor(cyc);
+                        const double ph = 2.0 * M_PI * cyc;
+                        u *= std::complex<double>(std::cos(ph), std::sin(ph));
+                        dst[n] = std::complex<float>((float)u.real(), (float)u.imag());
                     }
                 }
             }
-            CAF_H2D(p->d_hc, host.data(), host.size() * sizeof(std::complex<float>));
         }
-        {
-            FftPlan tmp;
-            rc = fft_plan_acquire(&tmp, false, (size_t)B, (size_t)nspec, (size_t)B);
-            if (rc == CAF_OK) rc = tmp.exec(p->d_hc, nullptr, nullptr);
-            if (rc == CAF_OK) launch_conj_scale(p->d_hc, nspec * B, 1.0f / (float)B, nullptr);
-            // the in-LDS engines read their template-spectrum rows permuted: d_hc -> a temporary of the same size -> d_hc, on the
-            // null stream, which is synchronised (a blocking Scratch) before the temporary goes back to the pool
-            auto permute_hc = [&](auto&& launch) -> int {
-                Scratch sc(nullptr, true);
-                float2* t = nullptr;
-                const int prc = sc.get(&t, nspec * (int64_t)B);
-                if (prc) return prc;
-                launch(t);
-                CAF_HIP_TRY(hipMemcpyAsync(p->d_hc, t, (size_t)nspec * B * 8, hipMemcpyDeviceToDevice, nullptr));
-                return sc.finish();
-            };
-            // 65536 points: pairs of the two halves of each parity, every 1024-chunk in butterfly order, in one pass
-            if (rc == CAF_OK && p->fused && B == 65536)
-                rc = permute_hc([&](float2* t) { launch_parity_pairs(p->d_hc, t, nspec, B / 4, nullptr); });
-            // 32768 points: parity-major (even samples, then odd samples) ...
-            if (rc == CAF_OK && p->fused && B == 32768)
-                rc = permute_hc([&](float2* t) { launch_parity_major(p->d_hc, t, nspec, B / 2, nullptr); });
-            // ... and, like 16384 points, every 1024-chunk in butterfly order (caf_fused.hip, fp_tid_of)
-            if (rc == CAF_OK && p->fused && B != 65536)
-                rc = permute_hc([&](float2* t) { launch_butterfly_order(p->d_hc, t, nspec * (int64_t)B / 1024, nullptr); });
-            hipError_t e = hipStreamSynchronize(nullptr);
-            fft_plan_release(&tmp);
-            if (rc) return rc;
-            CAF_HIP_TRY(e);
-            if ((rc = build_in.finish())) return rc;
-        }
+        CAF_H2D(p->d_hc, host.data(), host.size() * sizeof(std::complex<float>));
     }
-    if (!shifts.empty())
-        CAF_H2D(p->d_shifts, shifts.data(), shifts.size() * 4);
-    CAF_H2D(p->d_tscale, tscale.data(), (size_t)T * 4);
-    {   // what the zoom needs beside the coarse result: the time-domain multiplier of a product row,
-        // rx[d + n] * conj(u[n]), and the frequency each hypothesis index stands for
-        std::vector<std::complex<float>> uc((size_t)T * N);
-        for (size_t i = 0; i < uc.size(); ++i) uc[i] = d->auto_conj ? std::conj(tm[i]) : tm[i];
-        std::vector<double> nu(F);
-        for (int f = 0; f < F; ++f)
-            nu[f] = d->freq_mode == CAF_FREQ_BINS ? (double)d->h_bins[f] / (double)d->grid : d->h_freqs_norm[f];
-        if ((rc = p->alloc(&p->d_uconj, (int64_t)T * N)) || (rc = p->alloc(&p->d_nu, F))) return rc;
-        CAF_H2D(p->d_uconj, uc.data(), uc.size() * 8);
-        CAF_H2D(p->d_nu, nu.data(), nu.size() * 8);
-    }
-    CAF_H2D(p->d_gstart, gs.data(), gs.size() * 4);
-    CAF_H2D(p->d_glen, gl.data(), gl.size() * 4);
+    FftPlan tmp;
+    rc = fft_plan_acquire(&tmp, false, (size_t)B, (size_t)nspec, (size_t)B);
+    if (rc == CAF_OK) rc = tmp.exec(p->d_hc, nullptr, nullptr);
+    if (rc == CAF_OK) launch_conj_scale(p->d_hc, nspec * B, 1.0f / (float)B, nullptr);
+    // the in-LDS engines read their template-spectrum rows permuted: d_hc -> a temporary of the same size -> d_hc, on the
+    // null stream, which is synchronised (a blocking Scratch) before the temporary goes back to the pool
+    auto permute_hc = [&](auto&& launch) -> int {
+        Scratch sc(nullptr, true);
+        float2* t = nullptr;
+        const int prc = sc.get(&t, nspec * (int64_t)B);
+        if (prc) return prc;
+        launch(t);
+        CAF_HIP_TRY(hipMemcpyAsync(p->d_hc, t, (size_t)nspec * B * 8, hipMemcpyDeviceToDevice, nullptr));
+        return sc.finish();
+    };
+    // 65536 points: pairs of the two halves of each parity, every 1024-chunk in butterfly order, in one pass
+    if (rc == CAF_OK && p->fused && B == 65536)
+        rc = permute_hc([&](float2* t) { launch_parity_pairs(p->d_hc, t, nspec, B / 4, nullptr); });
+    // 32768 points: parity-major (even samples, then odd samples) ...
+    if (rc == CAF_OK && p->fused && B == 32768)
+        rc = permute_hc([&](float2* t) { launch_parity_major(p->d_hc, t, nspec, B / 2, nullptr); });
+    // ... and, like 16384 points, every 1024-chunk in butterfly order (caf_fused.hip, fp_tid_of)
+    if (rc == CAF_OK && p->fused && B != 65536)
+        rc = permute_hc([&](float2* t) { launch_butterfly_order(p->d_hc, t, nspec * (int64_t)B / 1024, nullptr); });
+    hipError_t e = hipStreamSynchronize(nullptr);
+    fft_plan_release(&tmp);
+    if (rc) return rc;
+    CAF_HIP_TRY(e);
+    return build_in.finish();  // the inputs of the table build go back to the pool
+}
 
-    if ((rc = fft_plan_acquire(&p->fwd, false, (size_t)B, (size_t)p->fwd_chunk, (size_t)B))) return rc;
-    if (!p->fused && (rc = fft_plan_acquire(&p->inv, true, (size_t)B, (size_t)nb * T * F, (size_t)p->pitch))) return rc;
-    p->workspace_bytes += (int64_t)p->fwd.work_bytes + (int64_t)p->inv.work_bytes;
-    const char* aux = getenv("CAF_AUX_STREAM");  // A/B switch, default on
-    if (!aux || atoi(aux)) {
-        if ((rc = aux_acquire(p->device, &p->s_aux, &p->ev_fork, &p->ev_join))) return rc;
+static int32_t cu_count(int device, int* cus) {  // (hipGetDeviceProperties costs ~1 ms per call; the attribute query does not)
+    CAF_HIP_TRY(hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, device));
+    return CAF_OK;
+}
+
+static int32_t plan_build(caf_plan p, const caf_plan_desc* d) {
+    CAF_REQUIRE(d->num_templates >= 1 && d->template_len >= 1 && d->h_templates, "need >= 1 template");
+    CAF_REQUIRE(d->num_freqs >= 1, "need >= 1 frequency hypothesis");
+    CAF_REQUIRE(d->max_rx_len >= d->template_len, "max_rx_len shorter than the template");
+    CAF_REQUIRE(d->max_rx_len < ((int64_t)1 << 31) - (1 << 20), "rx longer than 2^31 samples is not supported");
+    CAF_REQUIRE(d->freq_mode == CAF_FREQ_BINS || d->freq_mode == CAF_FREQ_NORM, "bad freq_mode");
+    CAF_HIP_TRY(hipGetDevice(&p->device));
+    p->T = d->num_templates;
+    p->N = d->template_len;
+    p->F = d->num_freqs;
+    p->freq_mode = d->freq_mode;
+    p->max_rx = d->max_rx_len;
+    Build b;
+    b.d = d;
+    if (d->num_groups >= 1 && d->h_group_start && d->h_group_len) {
+        b.gs.assign(d->h_group_start, d->h_group_start + d->num_groups);
+        b.gl.assign(d->h_group_len, d->h_group_len + d->num_groups);
+    } else {
+        b.gs = {0};
+        b.gl = {p->N};
     }
+    p->G = (int)b.gs.size();
+    for (int g = 0; g < p->G; ++g)
+        CAF_REQUIRE(b.gs[g] >= 0 && b.gl[g] >= 1 && (int64_t)b.gs[g] + b.gl[g] <= p->N, "group outside the template span");
+
+    int rc;
+    if ((rc = build_choose_engine(p, &b))) return rc;
+    if (!b.nz.empty()) return plan_build_direct(p, b);
+    if ((rc = build_block(p, &b))) return rc;
+    // the CU count, once per build; the two-launch engine only sizes its work items by it: 256 if the query fails
+    if (p->fused && (rc = cu_count(p->device, &b.cus))) {
+        if (p->persistent) return rc;
+        b.cus = 256;
+    }
+    build_batch(p, b);
+    if ((rc = build_buffers(p, b)) || (rc = build_template_spectra(p, b))) return rc;
+    if (!b.shifts.empty()) CAF_H2D(p->d_shifts, b.shifts.data(), b.shifts.size() * 4);
+    std::vector<double> nu;
+    if ((rc = hyp_freqs(d, &nu)) || (rc = build_scales_groups_zoom(p, b, nu))) return rc;
+
+    if ((rc = fft_plan_acquire(&p->fwd, false, (size_t)p->B, (size_t)p->fwd_chunk, (size_t)p->B))) return rc;
+    if (!p->fused && (rc = fft_plan_acquire(&p->inv, true, (size_t)p->B, (size_t)p->nb * p->T * p->F, (size_t)p->pitch))) return rc;
+    p->workspace_bytes += (int64_t)p->fwd.work_bytes + (int64_t)p->inv.work_bytes;
+    if (env_int("CAF_AUX_STREAM", 1))  // A/B switch
+        if ((rc = aux_acquire(p->device, &p->s_aux, &p->ev_fork, &p->ev_join))) return rc;
     return CAF_OK;
 }
 
@@ -846,75 +906,112 @@ int32_t caf_plan_execute(caf_plan p, const float* d_rx, int64_t rx_len, int64_t 
     return caf_plan_execute2(p, d_rx, rx_len, shift_start, num_shifts, &o2, stream);
 }
 
-int32_t caf_plan_execute2(caf_plan p, const float* d_rx, int64_t rx_len, int64_t shift_start, int64_t num_shifts,
-                          const caf_outputs2* out2, void* stream) {
-    CAF_REQUIRE(p && d_rx && out2, "caf_plan_execute: NULL argument");
-    CAF_REQUIRE(!out2->reserved[0] && !out2->reserved[1] && !out2->reserved[2], "caf_outputs2.reserved must be NULL");
-    // (the engine below works on one flat view of the outputs)
-    struct AllOutputs : caf_outputs {
-        float* d_surface_t;
-    } all;
-    static_cast<caf_outputs&>(all) = out2->base;
-    all.d_surface_t = out2->d_surface_t;
-    const AllOutputs* out = &all;
-    CAF_REQUIRE(rx_len >= p->N && rx_len <= p->max_rx, "rx_len outside [template_len, max_rx_len]");
-    CAF_REQUIRE(shift_start >= 0 && num_shifts >= 1, "need shift_start >= 0 and num_shifts >= 1");
-    CAF_REQUIRE(shift_start + num_shifts - 1 + p->N <= rx_len, "delays run past the end of rx");
-    CAF_REQUIRE((reinterpret_cast<uintptr_t>(d_rx) & 7) == 0, "d_rx must be 8-byte aligned");
-    int cur_dev = -1;
-    CAF_HIP_TRY(hipGetDevice(&cur_dev));
-    CAF_REQUIRE(cur_dev == p->device, "caf_plan_execute: the plan was created on another device than the current one");
-    hipStream_t st = (hipStream_t)stream;
-    const float2* rx = reinterpret_cast<const float2*>(d_rx);
+// ---- execute: one call, one decision, one function per engine ----
+struct Call : caf_outputs {  // one flat view of the outputs, and the delays of the call
+    float* d_surface_t = nullptr;
+    const float2* rx = nullptr;
+    int64_t rx_len = 0, shift_start = 0, num_shifts = 0;
+    int64_t nblk = 0, nblk_pad = 0;  // blocks of this call; padded to whole batches (rocfft engine)
+    bool want_peak = false;
+    hipStream_t st = nullptr;
+};
+
+// Everything the in-LDS engines branch on in one call
+struct PersistMode {
+    int gpt = 0;         // > 0: hypothesis groups per template (no-surface pairs, hypothesis-major surface); 0: flat groups
+    int nosurf = 0;      // 0: |y|^2 tiles; 1: (value, hypothesis) pairs; 2: pairs of normalised values beside surface_t
+    int hyp_per_wg = 0;  // hypotheses per FFT work item
+    int ngroups = 0;     // FFT work items per block
+    int nb_launch = 0;   // blocks per launch
+    int64_t imax_off = 0;  // floats from d_vt (= vmax) to imax
+    bool f1_direct = false, f1_item_peaks = false, cqf_rows = false;
+};
+
+static int32_t decide_mode(const caf_plan_t* p, Call* c, PersistMode* m) {
     const int T = p->T, F = p->F;
-    const bool want_peak = out->d_peak_val || out->d_peak_delay || out->d_peak_freq;
     // hypothesis-major surface [T][F][S]: with one hypothesis per template it IS the delay-major one
-    if (all.d_surface_t && F == 1) {
-        CAF_REQUIRE(!all.d_surface, "d_surface and d_surface_t cannot both be given");
-        all.d_surface = all.d_surface_t;
-        all.d_surface_t = nullptr;
+    if (c->d_surface_t && F == 1) {
+        CAF_REQUIRE(!c->d_surface, "d_surface and d_surface_t cannot both be given");
+        c->d_surface = c->d_surface_t;
+        c->d_surface_t = nullptr;
     }
-    const bool surf_t = out->d_surface_t != nullptr;
-    CAF_REQUIRE(!surf_t || (p->persistent && p->B == 16384 && !out->d_surface && !out->d_cqf),
+    const bool surf_t = c->d_surface_t != nullptr;
+    CAF_REQUIRE(!surf_t || (writes_surface_t(p) && !c->d_surface && !c->d_cqf),
                 "the hypothesis-major surface (d_surface_t) is written by the persistent engine with 16384-point blocks (templates of "
                 "at most 8192 samples), and not together with d_surface or d_cqf");
-
-    if (p->direct) {
-        CAF_REQUIRE(!out->d_cqf, "the direct engine has no complex-QF output (create the plan with CAF_ENGINE_ROCFFT)");
-        p->stage_begin(3, st);
-        launch_direct_caf(rx, shift_start, num_shifts, T, F, p->dir_k, p->d_dir_pos, p->d_dir_w, p->d_tscale, out->d_surface,
-                          out->d_row_max, out->d_row_arg, want_peak ? p->d_partial : nullptr, p->partial_per_tmpl, st);
-        p->stage_end(st);
-        if (want_peak) {
-            p->stage_begin(6, st);
-            launch_peak_reduce(p->d_partial, (num_shifts + 127) / 128, p->partial_per_tmpl, T,
-                               p->d_partial + (int64_t)T * p->partial_per_tmpl, out->d_peak_val, out->d_peak_delay,
-                               out->d_peak_freq, st);
-            p->stage_end(st);
+    if (!p->fused) return CAF_OK;
+    // complex QF rows: written by the FFT items of the one-launch engine themselves (fused_item MODE 4), as the only
+    // output of the call
+    m->cqf_rows = c->d_cqf != nullptr;
+    CAF_REQUIRE(!m->cqf_rows || (p->persistent && !c->d_surface && !c->d_row_max && !c->d_row_arg && !c->want_peak),
+                "the in-LDS engines write the complex-QF plane only from the persistent engine and only as the "
+                "sole output of a call (create the plan with CAF_ENGINE_ROCFFT for the other combinations)");
+    // No surface wanted (per-delay traces / peaks only): the FFT items keep running per-delay maxima and
+    // write one (value, hypothesis) pair per delay and group instead of the |y|^2 tiles (1/32 of the
+    // bytes at 64 hypotheses per group).  With at least one group per template the groups are formed per
+    // template, evenly sized (F = 201: 4 groups of 51/51/51/48).
+    // The pairs live in the tile buffer: vmax [block][group][tile][64] f32, then imax (same shape, i32).
+    if (!c->d_surface && !m->cqf_rows && env_int("CAF_PERSIST_NOSURF", 1)) m->gpt = nosurf_groups_per_tmpl(p);  // A/B switch
+    // A work item costs ~13 us beside its hypotheses (claim, parameters, block spectrum, first row:
+    // profiles/r04/c3_items_and_xcd_groups.log), 3 % of an item of 64: groups of up to 256 hypotheses (the running
+    // maxima pack the index into 8 bits) while the launch keeps >= 40 items per CU -- config C4's share of one GPU
+    // (64 templates x 512 bins) 1010 -> 979 ms; C2 (one template, 1365 x 4 items) stays at 64
+    if (m->gpt && !getenv("CAF_HYP_PER_WG")) {
+        const int64_t blocks_launch = std::min<int64_t>(p->nb_nosurf, c->nblk);
+        while (m->gpt > 1) {
+            const int g2 = (m->gpt + 1) / 2;
+            if ((F + g2 - 1) / g2 > 256 || (int64_t)T * g2 * blocks_launch < (int64_t)40 * p->n_cus) break;
+            m->gpt = g2;
         }
-        CAF_HIP_TRY(hipGetLastError());
-        return CAF_OK;
     }
+    // the hypothesis-major surface rides on the same per-template groups (F >= 2 here; fewer hypotheses than a
+    // group: one group per template)
+    if (surf_t) m->gpt = (F + p->hyp_per_wg - 1) / p->hyp_per_wg;
+    // the |y|^2 tiles of one block are addressed with 32-bit byte offsets (descriptor + SGPR + VGPR offset)
+    CAF_REQUIRE(m->gpt || (int64_t)(p->B / 64) * T * F * 256 < ((int64_t)1 << 32),
+                "too many hypotheses (templates x frequencies) for one launch with |y|^2 tiles: ask for no surface, "
+                "or split the templates over several plans");
+    // No frequency scan (F == 1) with per-delay rows wanted: the FFT items write the finished rows themselves
+    // (fused_item MODE 3) and there are no tile items at all; row_arg is all zeros and the peaks come from the rows.
+    static const bool f1_env = env_int("CAF_PERSIST_F1DIRECT", 1) != 0;  // A/B switch
+    // (CAF_F1_ITEM_PEAKS=0: the peak records from a pass over the finished rows instead of from the items -- A/B switch)
+    static const bool f1_pk_env = env_int("CAF_F1_ITEM_PEAKS", 1) != 0;
+    m->f1_direct = p->persistent && p->B == 16384 && F == 1 && f1_env && !m->cqf_rows &&
+                   (c->d_row_max || c->d_surface || (c->want_peak && f1_pk_env));
+    m->f1_item_peaks = m->f1_direct && c->want_peak && f1_pk_env;
+    m->nosurf = !m->gpt ? 0 : surf_t ? 2 : 1;
+    m->hyp_per_wg = m->gpt ? (F + m->gpt - 1) / m->gpt : p->hyp_per_wg;
+    m->ngroups = m->gpt ? T * m->gpt : (T * F + p->hyp_per_wg - 1) / p->hyp_per_wg;
+    m->nb_launch = m->gpt ? p->nb_nosurf : p->nb;
+    // the pair arrays of a launch: nb_nosurf * 2 * T * gpt <= nb * T * F, the size of d_vt (build_batch, build_buffers)
+    m->imax_off = vt_floats(p, m->nb_launch, m->ngroups);
+    if (p->B == 65536) m->ngroups *= 2;  // one work item per (hypothesis group, output residue): fused_item2q<FOLD>
+    return CAF_OK;
+}
 
-    const int64_t nblk = (num_shifts + p->step - 1) / p->step;
-    const int64_t nblk_pad = (nblk + p->nb - 1) / p->nb * p->nb;
-    // overlap-save blocks of rx -> spectra X[b] for every block of this call
+static int32_t run_direct(caf_plan p, const Call& c) {
+    CAF_REQUIRE(!c.d_cqf, "the direct engine has no complex-QF output (create the plan with CAF_ENGINE_ROCFFT)");
+    p->stage_begin(3, c.st);
+    launch_direct_caf(c.rx, c.shift_start, c.num_shifts, p->T, p->F, p->dir_k, p->d_dir_pos, p->d_dir_w, p->d_tscale, c.d_surface,
+                      c.d_row_max, c.d_row_arg, c.want_peak ? p->d_partial : nullptr, p->partial_per_tmpl, c.st);
+    p->stage_end(c.st);
+    return CAF_OK;
+}
+
+// overlap-save blocks of rx -> spectra X[b] for every block of this call, and the window energies of its delays
+static int32_t run_forward(caf_plan p, const Call& c) {
+    hipStream_t st = c.st;
     // (partitioned templates: block b's products also take the spectra of blocks b + 1 .. b + npart - 1)
-    const int64_t nfwd = ((p->fused ? nblk + p->npart - 1 : nblk_pad) + p->fwd_chunk - 1) / p->fwd_chunk;
+    const int64_t nfwd = ((p->fused ? c.nblk + p->npart - 1 : c.nblk_pad) + p->fwd_chunk - 1) / p->fwd_chunk;
+    const int64_t nspec = nfwd * p->fwd_chunk;
     // LDS engines with 16384-point blocks: gather + forward transform in one launch of the in-LDS FFT, which also
     // writes the sliding energies of each block's delays from the samples it holds anyway.
     // (CAF_FWD_ROCFFT=1: the gather kernel + batched rocFFT transforms that every other block size uses;
     //  CAF_ENERGY_PREFIX=1: the separate float64-prefix pass for the energies)
-    static const bool fwd_rocfft = [] {
-        const char* e = getenv("CAF_FWD_ROCFFT");
-        return e && atoi(e);
-    }();
-    static const bool energy_prefix = [] {
-        const char* e = getenv("CAF_ENERGY_PREFIX");
-        return e && atoi(e);
-    }();
-    const bool lds_fwd = p->fused && p->B == 16384 && !fwd_rocfft;
-    const bool energy_in_fwd = lds_fwd && !energy_prefix;
+    static const bool fwd_rocfft = env_int("CAF_FWD_ROCFFT", 0) != 0;
+    static const bool energy_prefix = env_int("CAF_ENERGY_PREFIX", 0) != 0;
+    const bool lds_fwd = p->fused && !fwd_rocfft;
+    const bool energy_in_fwd = lds_fwd && p->B == 16384 && !energy_prefix;
     // Otherwise the sliding-energy pass (float64 prefix of |rx|^2, then differences) is independent of the block
     // spectra: it runs on the plan's auxiliary stream beside gather + forward FFTs (small memory-bound kernels that do
     // not fill the chip one at a time) and is joined before the first consumer of inv_e.
@@ -926,300 +1023,294 @@ int32_t caf_plan_execute2(caf_plan p, const float* d_rx, int64_t rx_len, int64_t
             CAF_HIP_TRY(hipStreamWaitEvent(p->s_aux, p->ev_fork, 0));
         }
         p->stage_begin(0, se);
-        launch_energy_prefix(rx, rx_len, p->d_tile_sums, p->d_prefix, se);
-        launch_inv_energy(rx, rx_len, p->d_prefix, shift_start, num_shifts, p->d_gstart, p->d_glen, p->G, p->d_inv_e, se);
+        launch_energy_prefix(c.rx, c.rx_len, p->d_tile_sums, p->d_prefix, se);
+        launch_inv_energy(c.rx, c.rx_len, p->d_prefix, c.shift_start, c.num_shifts, p->d_gstart, p->d_glen, p->G, p->d_inv_e, se);
         p->stage_end(se);
         if (aux) CAF_HIP_TRY(hipEventRecord(p->ev_join, p->s_aux));
     }
-    const bool lds_fwd32 = p->fused && p->B == 32768 && !fwd_rocfft;
-    const bool lds_fwd64 = p->fused && p->B == 65536 && !fwd_rocfft;
-    if (lds_fwd32 || lds_fwd64) {
+    if (lds_fwd) {
         p->stage_begin(2, st);
-        const int rc = lds_fwd32 ? launch_block_spectra32(rx, rx_len, shift_start, p->step, nfwd * p->fwd_chunk, p->d_xb2, st)
-                                 : launch_block_spectra64(rx, rx_len, shift_start, p->step, nfwd * p->fwd_chunk, p->d_xb2, st);
-        p->stage_end(st);
-        if (rc) return rc;
-    } else if (lds_fwd) {
-        p->stage_begin(2, st);
-        const int rc = energy_in_fwd
-                           ? launch_block_spectra(rx, rx_len, shift_start, p->step, nfwd * p->fwd_chunk, p->d_xb, st, p->d_inv_e,
-                                                  num_shifts, p->d_gstart, p->d_glen, p->G)
-                           : launch_block_spectra(rx, rx_len, shift_start, p->step, nfwd * p->fwd_chunk, p->d_xb, st);
+        const int rc = p->B == 32768   ? launch_block_spectra32(c.rx, c.rx_len, c.shift_start, p->step, nspec, p->d_xb2, st)
+                       : p->B == 65536 ? launch_block_spectra64(c.rx, c.rx_len, c.shift_start, p->step, nspec, p->d_xb2, st)
+                       : energy_in_fwd ? launch_block_spectra(c.rx, c.rx_len, c.shift_start, p->step, nspec, p->d_xb, st, p->d_inv_e,
+                                                              c.num_shifts, p->d_gstart, p->d_glen, p->G)
+                                       : launch_block_spectra(c.rx, c.rx_len, c.shift_start, p->step, nspec, p->d_xb, st);
         p->stage_end(st);
         if (rc) return rc;
     } else {
         p->stage_begin(1, st);
-        launch_gather_blocks(rx, rx_len, shift_start, p->step, p->B, (int32_t)(nfwd * p->fwd_chunk), p->d_xb, st);
+        launch_gather_blocks(c.rx, c.rx_len, c.shift_start, p->step, p->B, (int32_t)nspec, p->d_xb, st);
         p->stage_end(st);
-        for (int64_t c = 0; c < nfwd; ++c) {
+        for (int64_t k = 0; k < nfwd; ++k) {
             p->stage_begin(2, st);
-            int rc = p->fwd.exec(p->d_xb + c * p->fwd_chunk * (int64_t)p->B, nullptr, st);
+            int rc = p->fwd.exec(p->d_xb + k * p->fwd_chunk * (int64_t)p->B, nullptr, st);
             p->stage_end(st);
             if (rc) return rc;
         }
+        if (p->fused && p->B == 32768)  // block spectra parity-major for the two chained half-transforms
+            launch_parity_major(p->d_xb, p->d_xb2, nspec, p->B / 2, st, true);
+        if (p->fused && p->B == 65536)  // ... as pairs of the two halves of each parity for the folded form
+            launch_parity_pairs(p->d_xb, p->d_xb2, nspec, p->B / 4, st);
     }
-    if (p->fused && p->B == 32768 && !lds_fwd32)  // block spectra parity-major for the two chained half-transforms
-        launch_parity_major(p->d_xb, p->d_xb2, nfwd * p->fwd_chunk, p->B / 2, st, true);
-    if (p->fused && p->B == 65536 && !lds_fwd64)  // ... as pairs of the two halves of each parity for the folded form
-        launch_parity_pairs(p->d_xb, p->d_xb2, nfwd * p->fwd_chunk, p->B / 4, st);
     if (aux) CAF_HIP_TRY(hipStreamWaitEvent(st, p->ev_join, 0));
-    bool f1_direct = false, f1_item_peaks = false;
-    if (p->fused) {
-        // complex QF rows: written by the FFT items of the one-launch engine themselves (fused_item MODE 4), as the only
-        // output of the call
-        const bool cqf_rows = out->d_cqf != nullptr;
-        CAF_REQUIRE(!cqf_rows || (p->persistent && !out->d_surface && !out->d_row_max && !out->d_row_arg && !want_peak),
-                    "the in-LDS engines write the complex-QF plane only from the persistent engine and only as the "
-                    "sole output of a call (create the plan with CAF_ENGINE_ROCFFT for the other combinations)");
-        // No surface wanted (per-delay traces / peaks only): the FFT items keep running per-delay maxima and
-        // write one (value, hypothesis) pair per delay and group instead of the |y|^2 tiles (1/32 of the
-        // bytes at 64 hypotheses per group).  Needs groups that do not straddle templates: with at least one
-        // group per template they are formed per template, evenly sized (F = 201: 4 groups of 51/51/51/48).
-        // The pairs live in the tile buffer: vmax [block][group][tile][64] f32, then imax (same shape, i32).
-        int ns_gpt = 0;
-        {
-            const char* e = getenv("CAF_PERSIST_NOSURF");  // A/B switch, default on
-            if (p->persistent && p->B == 16384 && !out->d_surface && !cqf_rows && F >= p->hyp_per_wg && (!e || atoi(e))) {
-                const int gpt = (F + p->hyp_per_wg - 1) / p->hyp_per_wg;
-                // the two pair arrays must fit the tile buffer they replace (true for >= 2 hypotheses per group)
-                if (2 * (int64_t)T * gpt <= (int64_t)T * F) ns_gpt = gpt;
-            }
-            // A work item costs ~13 us beside its hypotheses (claim, parameters, block spectrum, first row:
-            // profiles/r04/c3_items_and_xcd_groups.log), 3 % of an item of 64: groups of up to 256 hypotheses (the running
-            // maxima pack the index into 8 bits) while the launch keeps >= 40 items per CU -- config C4's share of one GPU
-            // (64 templates x 512 bins) 1010 -> 979 ms; C2 (one template, 1365 x 4 items) stays at 64
-            if (ns_gpt && !getenv("CAF_HYP_PER_WG")) {
-                const int64_t blocks_launch = std::min<int64_t>(p->nb_nosurf, nblk);
-                while (ns_gpt > 1) {
-                    const int g2 = (ns_gpt + 1) / 2;
-                    if ((F + g2 - 1) / g2 > 256 || (int64_t)T * g2 * blocks_launch < (int64_t)40 * p->n_cus) break;
-                    ns_gpt = g2;
-                }
-            }
-            // the hypothesis-major surface rides on the same per-template groups (F >= 2 here; fewer hypotheses than a
-            // group: one group per template)
-            if (surf_t) ns_gpt = (F + p->hyp_per_wg - 1) / p->hyp_per_wg;
+    return CAF_OK;
+}
+
+// The arguments of one launch of the one-launch engine: nbk blocks from block b0 of the call
+static PersistParams fill_persist_params(const caf_plan_t* p, const PersistMode& m, int64_t b0, int32_t nbk, const Call& c) {
+    PersistParams h;
+    std::memset(&h, 0, sizeof(h));
+    h.xb = (p->B >= 32768 ? p->d_xb2 : p->d_xb) + b0 * (int64_t)p->B;
+    h.hc = p->d_hc;
+    h.shifts = p->d_shifts;
+    h.tw1 = p->d_tw1;
+    h.tw23 = p->d_tw23;
+    h.vt = p->d_vt;
+    h.table_mode = p->mul_mode == 2 ? 1 : 0;
+    h.nfreq = p->F;
+    h.nhyp = p->T * p->F;
+    h.hyp_per_wg = m.hyp_per_wg;
+    h.nblk = nbk;
+    h.tiles_per_blk = p->tiles_per_blk;
+    h.block_log2 = p->B == 65536 ? 16 : p->B == 32768 ? 15 : 14;
+    h.dstride = p->B == 65536 ? 2 : 1;
+    h.npart = p->npart;
+    h.ntmpl = p->T;
+    h.step = p->step;
+    h.blk0 = (int32_t)b0;
+    h.gpt = m.gpt;
+    h.tscale = p->d_tscale;
+    h.inv_e = p->d_inv_e;
+    h.num_shifts = c.num_shifts;
+    h.shift_start = c.shift_start;
+    h.surface = c.d_surface;
+    h.row_max = c.d_row_max;
+    h.row_arg = c.d_row_arg;
+    // (f1_direct: the peak records only if the items write them)
+    h.partial = c.want_peak && (!m.f1_direct || m.f1_item_peaks) ? p->d_partial : nullptr;
+    h.partial_per_tmpl = p->partial_per_tmpl;
+    h.pq = p->d_pq;
+    h.tr_slots = p->tr_slots;
+    h.ngroups = m.ngroups;
+    h.n_fft = nbk * m.ngroups;
+    h.ipb = (p->tiles_per_blk + 15) / 16;  // 16 tiles per item (PQ_TILES, caf_fused.hip)
+    h.n_tr = m.f1_direct || m.cqf_rows ? 0 : nbk * h.ipb;  // the FFT items write finished rows: no tile items
+    h.nosurf = m.nosurf;
+    h.f1_direct = m.f1_direct ? 1 : 0;
+    h.cqf = c.d_cqf;
+    h.surface_t = c.d_surface_t;
+    h.vmax = p->d_vt;
+    h.imax = reinterpret_cast<int32_t*>(p->d_vt + m.imax_off);
+    return h;
+}
+
+// CAF_PERSIST_DEBUG: wait (bounded) for the launch and report what the workgroups did: time per role in us (100 MHz device
+// clock).  CAF_PERSIST_TILE_ONLY="16,64,256": then re-run only the tile role on k workgroups over the tiles just produced
+// (per-CU streaming rate of the role at different levels of HBM concurrency)
+static void persist_report(caf_plan p, const PersistParams& h, const int32_t* h_dbg, bool surface, hipStream_t st) {
+    hipEvent_t ev;
+    (void)hipEventCreate(&ev);
+    (void)hipEventRecord(ev, st);
+    bool done = false;
+    for (int i = 0; i < 80 && !done; ++i) {
+        done = hipEventQuery(ev) == hipSuccess;
+        if (!done) usleep(100000);
+    }
+    if (!done) {
+        fprintf(stderr, "[caf persistent] kernel still running after 8 s: aborting the process\n");
+        _exit(3);
+    }
+    std::vector<int32_t> q(4 + h.nblk);
+    (void)hipMemcpy(q.data(), p->d_pq, q.size() * 4, hipMemcpyDeviceToHost);
+    double sum[2][5] = {{0}};
+    int cnt[2] = {0, 0};
+    uint32_t t0 = 0xffffffffu, t1 = 0, tl = 0;
+    for (int w = 0; w < p->n_cus; ++w) {
+        const int pref = ((w >> 3) & 31) >= 32 - p->tr_slots;
+        ++cnt[pref];
+        for (int k = 0; k < 5; ++k) sum[pref][k] += h_dbg[8 * w + k];
+        t0 = std::min(t0, (uint32_t)h_dbg[8 * w + 5]);
+        tl = std::max(tl, (uint32_t)h_dbg[8 * w + 5]);
+        t1 = std::max(t1, (uint32_t)h_dbg[8 * w + 6]);
+    }
+    fprintf(stderr, "[caf persistent] n_fft=%d n_tr=%d | fft_next=%d tr_next=%d watchdog=%d,%d | first start -> last end "
+            "%.0f us, last start +%.0f us\n", h.n_fft, h.n_tr, q[0], q[1], q[2], q[3], (t1 - t0) / 100.0, (tl - t0) / 100.0);
+    for (int r = 0; r < 2; ++r)
+        if (cnt[r])
+            fprintf(stderr,
+                    "  %s workgroups (%d): claim+wait %.0f us, fft %.0f us in %.1f items (%.1f us each), tiles %.0f us "
+                    "in %.1f items (%.1f us each)\n",
+                    r ? "tile-first" : "fft-first", cnt[r], sum[r][0] / cnt[r] / 100.0, sum[r][1] / cnt[r] / 100.0,
+                    sum[r][3] / cnt[r], sum[r][3] > 0 ? sum[r][1] / sum[r][3] / 100.0 : 0.0,
+                    sum[r][2] / cnt[r] / 100.0, sum[r][4] / cnt[r],
+                    sum[r][4] > 0 ? sum[r][2] / sum[r][4] / 100.0 : 0.0);
+    const char* lst = getenv("CAF_PERSIST_TILE_ONLY");
+    if (!lst) return;
+    PersistParams h2 = h;
+    h2.n_fft = 0;
+    h2.ngroups = 0;  // every block counts as published
+    h2.dbg = nullptr;
+    hipEvent_t e0, e1;
+    (void)hipEventCreate(&e0);
+    (void)hipEventCreate(&e1);
+    for (const char* s = lst; *s;) {
+        const int k = atoi(s);
+        while (*s && *s != ',') ++s;
+        if (*s == ',') ++s;
+        if (k < 1) continue;
+        (void)hipEventRecord(e0, st);
+        launch_caf_persistent(&h2, p->d_params, k, st);
+        (void)hipEventRecord(e1, st);
+        (void)hipEventSynchronize(e1);
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, e0, e1);
+        const double bytes = (double)h2.n_tr * 16.0 * 64.0 * p->F * 4.0 * (surface ? 2.0 : 1.0);
+        fprintf(stderr, "  tile role alone on %3d workgroups: %.2f ms, %.1f us per item, %.1f GB/s per CU, %.2f TB/s\n",
+                k, ms, ms * 1e3 * k / h2.n_tr, bytes / (ms * 1e-3) / k / 1e9, bytes / (ms * 1e-3) / 1e12);
+    }
+}
+
+// CAF_PERSIST_POISON=1 (diagnostic, for the protocol tests): the tile / pair buffer is filled with POISON_VT before every
+// launch that has tile items, so that a tile read before its producer published it is wrong data, not the same bits
+// left behind by an earlier call.  The whole allocation is filled: it holds the |y|^2 tiles of nb blocks, and the
+// vmax / imax pairs of nb_nosurf blocks fit in it as well.
+static int32_t poison_tiles(caf_plan p, hipStream_t st) {
+    CAF_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)p->d_vt, (int)POISON_VT, (size_t)vt_floats(p, p->nb, (int64_t)p->T * p->F), st));
+    return CAF_OK;
+}
+
+// One-launch engine: both stages are one kernel, its time is booked on the multiply/FFT stage
+static int32_t run_persistent(caf_plan p, const PersistMode& m, const Call& c) {
+    hipStream_t st = c.st;
+    const bool poison = env_int("CAF_PERSIST_POISON", 0) != 0;
+    for (int64_t b0 = 0; b0 < c.nblk; b0 += m.nb_launch) {
+        PersistParams h = fill_persist_params(p, m, b0, (int32_t)std::min<int64_t>(m.nb_launch, c.nblk - b0), c);
+        // CAF_PERSIST_DEBUG=1: role statistics of every launch; =2: of every 10th launch only, so that the nine before it
+        // run back to back with the plain kernel (the report waits for the launch, which idles the GPU)
+        int32_t* h_dbg = nullptr;
+        static int dbg_launches = 0;
+        bool dbg_set = false;
+        const int dbg = env_int("CAF_PERSIST_DEBUG", 0, &dbg_set);
+        if (dbg_set && (dbg < 2 || ++dbg_launches % 10 == 0)) {  // host-mapped, 8 ints per workgroup
+            (void)hipHostMalloc((void**)&h_dbg, sizeof(int32_t) * 8 * (size_t)p->n_cus, hipHostMallocMapped);
+            std::memset(h_dbg, 0, sizeof(int32_t) * 8 * (size_t)p->n_cus);
+            (void)hipHostGetDevicePointer((void**)&h.dbg, h_dbg, 0);
         }
-        // the |y|^2 tiles of one block are addressed with 32-bit byte offsets (descriptor + SGPR + VGPR offset)
-        CAF_REQUIRE(ns_gpt || (int64_t)(p->B / 64) * T * F * 256 < ((int64_t)1 << 32),
-                    "too many hypotheses (templates x frequencies) for one launch with |y|^2 tiles: ask for no surface, "
-                    "or split the templates over several plans");
-        // No frequency scan (F == 1) with per-delay rows wanted: the FFT items write the finished rows themselves
-        // (fused_item MODE 3) and there are no tile items at all; row_arg is all zeros and the peaks come from the rows.
-        static const bool f1_env = [] {
-            const char* e = getenv("CAF_PERSIST_F1DIRECT");  // A/B switch, default on
-            return !e || atoi(e);
-        }();
-        // (CAF_F1_ITEM_PEAKS=0: the peak records from a pass over the finished rows instead of from the items -- A/B switch)
-        static const bool f1_pk_env = [] {
-            const char* e = getenv("CAF_F1_ITEM_PEAKS");
-            return !e || atoi(e);
-        }();
-        f1_direct = p->persistent && p->B == 16384 && F == 1 && f1_env && !cqf_rows &&
-                    (out->d_row_max || out->d_surface || (want_peak && f1_pk_env));
-        f1_item_peaks = f1_direct && want_peak && f1_pk_env;
-        const int nb_launch = ns_gpt ? p->nb_nosurf : p->nb;  // blocks per launch
-        // CAF_PERSIST_POISON=1 (diagnostic, for the protocol tests): the tile / pair buffer is filled with POISON_VT before every
-        // launch that has tile items, so that a tile read before its producer published it is wrong data, not the same bits
-        // left behind by an earlier call.  Read on every call (a test switches it on and off).  The whole allocation is
-        // filled: it holds the |y|^2 tiles of nb blocks, and the vmax / imax pairs of nb_nosurf blocks fit in it as well.
-        const char* poison_env = getenv("CAF_PERSIST_POISON");
-        const bool poison = poison_env && atoi(poison_env);
-        const size_t vt_count = (size_t)p->nb * p->tiles_per_blk * T * F * 64;
-        for (int64_t b0 = 0; p->persistent && b0 < nblk; b0 += nb_launch) {
-            const int32_t nbk = (int32_t)std::min<int64_t>(nb_launch, nblk - b0);
-            PersistParams h;
-            std::memset(&h, 0, sizeof(h));
-            h.xb = (p->B >= 32768 ? p->d_xb2 : p->d_xb) + b0 * (int64_t)p->B;
-            h.hc = p->d_hc;
-            h.shifts = p->d_shifts;
-            h.tw1 = p->d_tw1;
-            h.tw23 = p->d_tw23;
-            h.vt = p->d_vt;
-            h.table_mode = p->mul_mode == 2 ? 1 : 0;
-            h.nfreq = F;
-            h.nhyp = T * F;
-            h.hyp_per_wg = p->hyp_per_wg;
-            h.nblk = nbk;
-            h.tiles_per_blk = p->tiles_per_blk;
-            h.block_log2 = p->B == 65536 ? 16 : p->B == 32768 ? 15 : 14;
-            h.dstride = p->B == 65536 ? 2 : 1;
-            h.npart = p->npart;
-            h.ntmpl = T;
-            h.step = p->step;
-            h.blk0 = (int32_t)b0;
-            h.tscale = p->d_tscale;
-            h.inv_e = p->d_inv_e;
-            h.num_shifts = num_shifts;
-            h.shift_start = shift_start;
-            h.surface = out->d_surface;
-            h.row_max = out->d_row_max;
-            h.row_arg = out->d_row_arg;
-            h.partial = want_peak ? p->d_partial : nullptr;  // (f1_direct: set only if the items write the records)
-            h.partial_per_tmpl = p->partial_per_tmpl;
-            h.pq = p->d_pq;
-            h.tr_slots = p->tr_slots;
-            h.ngroups = (T * F + p->hyp_per_wg - 1) / p->hyp_per_wg;
-            h.surface_t = out->d_surface_t;
-            if (ns_gpt) {
-                h.nosurf = surf_t ? 2 : 1;
-                h.gpt = ns_gpt;
-                h.hyp_per_wg = (F + ns_gpt - 1) / ns_gpt;
-                h.ngroups = T * ns_gpt;
-            }
-            h.vmax = p->d_vt;
-            h.imax = reinterpret_cast<int32_t*>(p->d_vt + (int64_t)nb_launch * h.ngroups * p->tiles_per_blk * 64);
-            if (h.block_log2 == 16) h.ngroups *= 2;  // one work item per (hypothesis group, output residue): fused_item2q<FOLD>
-            h.n_fft = nbk * h.ngroups;
-            h.ipb = (p->tiles_per_blk + 15) / 16;  // 16 tiles per item (PQ_TILES, caf_fused.hip)
-            h.n_tr = nbk * h.ipb;
-            if (f1_direct) {
-                h.f1_direct = 1;
-                h.n_tr = 0;
-                if (!f1_item_peaks) h.partial = nullptr;
-            }
-            if (cqf_rows) {
-                h.cqf = out->d_cqf;
-                h.n_tr = 0;
-            }
-            // both stages are one kernel: its time is booked on the multiply/FFT stage
-            int32_t* h_dbg = nullptr;
-            // CAF_PERSIST_DEBUG=1: role statistics of every launch; =2: of every 10th launch only, so that the nine before it
-            // run back to back with the plain kernel (the report waits for the launch, which idles the GPU)
-            static int dbg_launches = 0;
-            const char* dbg_env = getenv("CAF_PERSIST_DEBUG");
-            if (dbg_env && (atoi(dbg_env) < 2 || ++dbg_launches % 10 == 0)) {  // host-mapped, 8 ints per workgroup
-                (void)hipHostMalloc((void**)&h_dbg, sizeof(int32_t) * 8 * (size_t)p->n_cus, hipHostMallocMapped);
-                std::memset(h_dbg, 0, sizeof(int32_t) * 8 * (size_t)p->n_cus);
-                (void)hipHostGetDevicePointer((void**)&h.dbg, h_dbg, 0);
-            }
-            if (poison && h.n_tr > 0) CAF_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)p->d_vt, (int)POISON_VT, vt_count, st));
-            p->stage_begin(3, st);
-            launch_caf_persistent(&h, p->d_params, p->n_cus, st);
-            p->stage_end(st);
-            if (h_dbg) {
-                // wait (bounded) and report what the workgroups did: time per role in us (100 MHz device clock)
-                hipEvent_t ev;
-                (void)hipEventCreate(&ev);
-                (void)hipEventRecord(ev, st);
-                bool done = false;
-                for (int i = 0; i < 80 && !done; ++i) {
-                    done = hipEventQuery(ev) == hipSuccess;
-                    if (!done) usleep(100000);
-                }
-                if (!done) {
-                    fprintf(stderr, "[caf persistent] kernel still running after 8 s: aborting the process\n");
-                    _exit(3);
-                }
-                std::vector<int32_t> q(4 + nbk);
-                (void)hipMemcpy(q.data(), p->d_pq, q.size() * 4, hipMemcpyDeviceToHost);
-                double sum[2][5] = {{0}};
-                int cnt[2] = {0, 0};
-                for (int w = 0; w < p->n_cus; ++w) {
-                    const int pref = ((w >> 3) & 31) >= 32 - p->tr_slots;
-                    ++cnt[pref];
-                    for (int k = 0; k < 5; ++k) sum[pref][k] += h_dbg[8 * w + k];
-                }
-                uint32_t t0 = 0xffffffffu, t1 = 0, tl = 0;
-                for (int w = 0; w < p->n_cus; ++w) {
-                    t0 = std::min(t0, (uint32_t)h_dbg[8 * w + 5]);
-                    tl = std::max(tl, (uint32_t)h_dbg[8 * w + 5]);
-                    t1 = std::max(t1, (uint32_t)h_dbg[8 * w + 6]);
-                }
-                fprintf(stderr, "[caf persistent] n_fft=%d n_tr=%d | fft_next=%d tr_next=%d watchdog=%d,%d | first start -> last end "
-                        "%.0f us, last start +%.0f us\n", h.n_fft, h.n_tr, q[0], q[1], q[2], q[3], (t1 - t0) / 100.0, (tl - t0) / 100.0);
-                for (int r = 0; r < 2; ++r)
-                    if (cnt[r])
-                        fprintf(stderr,
-                                "  %s workgroups (%d): claim+wait %.0f us, fft %.0f us in %.1f items (%.1f us each), tiles %.0f us "
-                                "in %.1f items (%.1f us each)\n",
-                                r ? "tile-first" : "fft-first", cnt[r], sum[r][0] / cnt[r] / 100.0, sum[r][1] / cnt[r] / 100.0,
-                                sum[r][3] / cnt[r], sum[r][3] > 0 ? sum[r][1] / sum[r][3] / 100.0 : 0.0,
-                                sum[r][2] / cnt[r] / 100.0, sum[r][4] / cnt[r],
-                                sum[r][4] > 0 ? sum[r][2] / sum[r][4] / 100.0 : 0.0);
-                // CAF_PERSIST_TILE_ONLY="16,64,256": re-run only the tile role on k workgroups over the tiles just
-                // produced (per-CU streaming rate of the role at different levels of HBM concurrency)
-                if (const char* lst = getenv("CAF_PERSIST_TILE_ONLY")) {
-                    PersistParams h2 = h;
-                    h2.n_fft = 0;
-                    h2.ngroups = 0;  // every block counts as published
-                    h2.dbg = nullptr;
-                    hipEvent_t e0, e1;
-                    (void)hipEventCreate(&e0);
-                    (void)hipEventCreate(&e1);
-                    for (const char* c = lst; *c;) {
-                        const int k = atoi(c);
-                        while (*c && *c != ',') ++c;
-                        if (*c == ',') ++c;
-                        if (k < 1) continue;
-                        (void)hipEventRecord(e0, st);
-                        launch_caf_persistent(&h2, p->d_params, k, st);
-                        (void)hipEventRecord(e1, st);
-                        (void)hipEventSynchronize(e1);
-                        float ms = 0.f;
-                        (void)hipEventElapsedTime(&ms, e0, e1);
-                        const double bytes = (double)h2.n_tr * 16.0 * 64.0 * F * 4.0 * (out->d_surface ? 2.0 : 1.0);
-                        fprintf(stderr, "  tile role alone on %3d workgroups: %.2f ms, %.1f us per item, %.1f GB/s per CU, %.2f TB/s\n",
-                                k, ms, ms * 1e3 * k / h2.n_tr, bytes / (ms * 1e-3) / k / 1e9, bytes / (ms * 1e-3) / 1e12);
-                    }
-                }
-                (void)hipHostFree(h_dbg);
-            }
-        }
-        for (int64_t b0 = 0; !p->persistent && b0 < nblk; b0 += p->nb) {
-            const int32_t nbk = (int32_t)std::min<int64_t>(p->nb, nblk - b0);
-            if (poison) CAF_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)p->d_vt, (int)POISON_VT, vt_count, st));
-            p->stage_begin(3, st);
-            launch_fused_caf(p->d_xb + b0 * (int64_t)p->B, p->d_hc, p->d_shifts, p->d_tw1, p->d_tw23,
-                             p->mul_mode == 2 ? 1 : 0, F, T * F, p->hyp_per_wg, nbk, p->tiles_per_blk, p->d_vt, st);
-            p->stage_end(st);
-            p->stage_begin(5, st);
-            launch_transpose_norm_argmax(p->d_vt, T, F, p->d_tscale, p->d_inv_e, num_shifts, shift_start, p->step,
-                                         (int32_t)b0, nbk, p->tiles_per_blk, out->d_surface, out->d_row_max,
-                                         out->d_row_arg, want_peak ? p->d_partial : nullptr, p->partial_per_tmpl, st);
-            p->stage_end(st);
+        int rc;
+        if (poison && h.n_tr > 0 && (rc = poison_tiles(p, st))) return rc;
+        p->stage_begin(3, st);
+        launch_caf_persistent(&h, p->d_params, p->n_cus, st);
+        p->stage_end(st);
+        if (h_dbg) {
+            persist_report(p, h, h_dbg, c.d_surface != nullptr, st);
+            (void)hipHostFree(h_dbg);
         }
     }
-    for (int64_t b0 = 0; !p->fused && b0 < nblk; b0 += p->nb) {
+    // one hypothesis per template: its index is 0 everywhere.  (On this stream, after the launch: a fill running beside
+    // the persistent kernel on another stream takes CUs from its resident workgroups -- measured 0.6 ms slower.)
+    if (m.f1_direct && c.d_row_arg) CAF_HIP_TRY(hipMemsetAsync(c.d_row_arg, 0, (size_t)p->T * (size_t)c.num_shifts * 4, st));
+    return CAF_OK;
+}
+
+// Two-launch engine: in-LDS multiply + inverse FFT to |y|^2 tiles, then transposition, normalisation and maxima
+static int32_t run_fused(caf_plan p, const Call& c) {
+    hipStream_t st = c.st;
+    const int T = p->T, F = p->F;
+    const bool poison = env_int("CAF_PERSIST_POISON", 0) != 0;
+    for (int64_t b0 = 0; b0 < c.nblk; b0 += p->nb) {
+        const int32_t nbk = (int32_t)std::min<int64_t>(p->nb, c.nblk - b0);
         int rc;
+        if (poison && (rc = poison_tiles(p, st))) return rc;
+        p->stage_begin(3, st);
+        launch_fused_caf(p->d_xb + b0 * (int64_t)p->B, p->d_hc, p->d_shifts, p->d_tw1, p->d_tw23,
+                         p->mul_mode == 2 ? 1 : 0, F, T * F, p->hyp_per_wg, nbk, p->tiles_per_blk, p->d_vt, st);
+        p->stage_end(st);
+        p->stage_begin(5, st);
+        launch_transpose_norm_argmax(p->d_vt, T, F, p->d_tscale, p->d_inv_e, c.num_shifts, c.shift_start, p->step,
+                                     (int32_t)b0, nbk, p->tiles_per_blk, c.d_surface, c.d_row_max,
+                                     c.d_row_arg, c.want_peak ? p->d_partial : nullptr, p->partial_per_tmpl, st);
+        p->stage_end(st);
+    }
+    return CAF_OK;
+}
+
+// rocFFT engine: spectral multiply, batched inverse transforms, |y|^2 (and the complex-QF plane) per batch of nb blocks
+static int32_t run_rocfft(caf_plan p, const Call& c) {
+    hipStream_t st = c.st;
+    const int T = p->T, F = p->F;
+    for (int64_t b0 = 0; b0 < c.nblk; b0 += p->nb) {
         p->stage_begin(3, st);
         launch_spectral_mul(p->mul_mode, p->d_xb + b0 * (int64_t)p->B, p->d_hc, p->d_shifts, p->B, p->pitch, F, T * F, p->hyp_per_wg, p->nb,
                             p->d_pbuf, st);
         p->stage_end(st);
 
         p->stage_begin(4, st);
-        rc = p->inv.exec(p->d_pbuf, nullptr, st);
+        const int rc = p->inv.exec(p->d_pbuf, nullptr, st);
         p->stage_end(st);
         if (rc) return rc;
 
-        if (out->d_cqf)
-            launch_complex_norm(p->d_pbuf, p->pitch, F, p->d_tscale, p->d_inv_e, num_shifts, p->step, (int32_t)b0, p->nb,
-                                T * F, reinterpret_cast<float2*>(out->d_cqf), st);
-        const bool want_mag = out->d_surface || out->d_row_max || out->d_row_arg || want_peak;
+        if (c.d_cqf)
+            launch_complex_norm(p->d_pbuf, p->pitch, F, p->d_tscale, p->d_inv_e, c.num_shifts, p->step, (int32_t)b0, p->nb,
+                                T * F, reinterpret_cast<float2*>(c.d_cqf), st);
+        const bool want_mag = c.d_surface || c.d_row_max || c.d_row_arg || c.want_peak;
         p->stage_begin(5, st);
         if (want_mag)
-            launch_magsq(p->d_pbuf, p->pitch, T, F, p->d_tscale, p->d_inv_e, num_shifts, shift_start, p->step, (int32_t)b0,
-                     p->nb, p->tiles_per_blk, out->d_surface, out->d_row_max, out->d_row_arg,
-                     want_peak ? p->d_partial : nullptr, p->partial_per_tmpl, st);
+            launch_magsq(p->d_pbuf, p->pitch, T, F, p->d_tscale, p->d_inv_e, c.num_shifts, c.shift_start, p->step, (int32_t)b0,
+                         p->nb, p->tiles_per_blk, c.d_surface, c.d_row_max, c.d_row_arg,
+                         c.want_peak ? p->d_partial : nullptr, p->partial_per_tmpl, st);
         p->stage_end(st);
     }
-    // one hypothesis per template: its index is 0 everywhere.  (On this stream, after the launch: a fill running beside
-    // the persistent kernel on another stream takes CUs from its resident workgroups -- measured 0.6 ms slower.)
-    if (f1_direct && out->d_row_arg) CAF_HIP_TRY(hipMemsetAsync(out->d_row_arg, 0, (size_t)T * (size_t)num_shifts * 4, st));
-    if (want_peak) {
-        p->stage_begin(6, st);
-        int64_t nrec = (p->fused ? nblk : nblk_pad) * p->tiles_per_blk;  // only the records of the blocks touched by this call
-        if (f1_direct && f1_item_peaks) {
-            nrec = nblk * 16;  // one record per (template, block, wave), written by the FFT items (fused_item PK)
-        } else if (f1_direct) {
-            launch_rows_peak(out->d_row_max ? out->d_row_max : out->d_surface, T, num_shifts, shift_start, p->d_partial,
-                             p->partial_per_tmpl, st);
-            nrec = rows_peak_chunks(num_shifts);
-        }
-        launch_peak_reduce(p->d_partial, nrec, p->partial_per_tmpl, T, p->d_partial + (int64_t)T * p->partial_per_tmpl,
-                           out->d_peak_val, out->d_peak_delay, out->d_peak_freq, st);
-        p->stage_end(st);
+    return CAF_OK;
+}
+
+// Peak records of the engine that ran -> one (value, delay, hypothesis) per template
+static void reduce_peaks(caf_plan p, const PersistMode& m, const Call& c) {
+    hipStream_t st = c.st;
+    p->stage_begin(6, st);
+    // only the records of the blocks touched by this call (direct engine: one per workgroup of 128 delays)
+    int64_t nrec = p->direct ? (c.num_shifts + 127) / 128 : (p->fused ? c.nblk : c.nblk_pad) * p->tiles_per_blk;
+    if (m.f1_item_peaks) {
+        nrec = c.nblk * 16;  // one record per (template, block, wave), written by the FFT items (fused_item PK)
+    } else if (m.f1_direct) {
+        launch_rows_peak(c.d_row_max ? c.d_row_max : c.d_surface, p->T, c.num_shifts, c.shift_start, p->d_partial,
+                         p->partial_per_tmpl, st);
+        nrec = rows_peak_chunks(c.num_shifts);
     }
+    launch_peak_reduce(p->d_partial, nrec, p->partial_per_tmpl, p->T, p->d_partial + (int64_t)p->T * p->partial_per_tmpl,
+                       c.d_peak_val, c.d_peak_delay, c.d_peak_freq, st);
+    p->stage_end(st);
+}
+
+int32_t caf_plan_execute2(caf_plan p, const float* d_rx, int64_t rx_len, int64_t shift_start, int64_t num_shifts,
+                          const caf_outputs2* out2, void* stream) {
+    CAF_REQUIRE(p && d_rx && out2, "caf_plan_execute: NULL argument");
+    CAF_REQUIRE(!out2->reserved[0] && !out2->reserved[1] && !out2->reserved[2], "caf_outputs2.reserved must be NULL");
+    CAF_REQUIRE(rx_len >= p->N && rx_len <= p->max_rx, "rx_len outside [template_len, max_rx_len]");
+    CAF_REQUIRE(shift_start >= 0 && num_shifts >= 1, "need shift_start >= 0 and num_shifts >= 1");
+    CAF_REQUIRE(shift_start + num_shifts - 1 + p->N <= rx_len, "delays run past the end of rx");
+    CAF_REQUIRE((reinterpret_cast<uintptr_t>(d_rx) & 7) == 0, "d_rx must be 8-byte aligned");
+    int cur_dev = -1;
+    CAF_HIP_TRY(hipGetDevice(&cur_dev));
+    CAF_REQUIRE(cur_dev == p->device, "caf_plan_execute: the plan was created on another device than the current one");
+    Call c;
+    static_cast<caf_outputs&>(c) = out2->base;
+    c.d_surface_t = out2->d_surface_t;
+    c.rx = reinterpret_cast<const float2*>(d_rx);
+    c.rx_len = rx_len;
+    c.shift_start = shift_start;
+    c.num_shifts = num_shifts;
+    c.want_peak = c.d_peak_val || c.d_peak_delay || c.d_peak_freq;
+    c.st = (hipStream_t)stream;
+    if (!p->direct) {
+        c.nblk = (num_shifts + p->step - 1) / p->step;
+        c.nblk_pad = (c.nblk + p->nb - 1) / p->nb * p->nb;
+    }
+    PersistMode m;
+    int32_t rc = decide_mode(p, &c, &m);
+    if (!rc) rc = p->direct ? run_direct(p, c) : run_forward(p, c);
+    if (!rc && !p->direct) rc = p->persistent ? run_persistent(p, m, c) : p->fused ? run_fused(p, c) : run_rocfft(p, c);
+    if (rc) return rc;
+    if (c.want_peak) reduce_peaks(p, m, c);
     CAF_HIP_TRY(hipGetLastError());
     return CAF_OK;
 }
@@ -1238,11 +1329,8 @@ int32_t caf_plan_execute_host(caf_plan p, const float* h_rx, int64_t rx_len, int
     // blocks: no |y|^2 tiles, no tile role -- 10.5 instead of 13.2 ms at config C2) that launch runs, and the transposition to the
     // reference's (delays, frequencies) layout happens in the download (host_d2h_transposed): the same numbers bit for bit
     // (tests/test_gpu_fullsize.py::test_c2_hypothesis_major_surface).  CAF_HOST_SURFACE_DELAY_MAJOR=1: the delay-major launch (A/B).
-    static const bool host_delay_major = [] {
-        const char* e = getenv("CAF_HOST_SURFACE_DELAY_MAJOR");
-        return e && atoi(e);
-    }();
-    const bool surf_t = h_surface && p->persistent && p->B == 16384 && F > 1 && F <= 65536 && !host_delay_major;
+    static const bool host_delay_major = env_int("CAF_HOST_SURFACE_DELAY_MAJOR", 0) != 0;
+    const bool surf_t = h_surface && writes_surface_t(p) && F > 1 && F <= 65536 && !host_delay_major;
     Scratch sc(nullptr);  // device copies of rx and of the outputs, cached across calls (caf_pool.hip)
     int rc = sc.get(&d_rx, rx_len);
     if (!rc && h_surface) rc = sc.get(surf_t ? &o2.d_surface_t : &o.d_surface, (int64_t)T * num_shifts * F);
