@@ -524,6 +524,29 @@ CAF_EXPORT int32_t caf_amble_search_bits(const uint8_t* d_syms, int64_t rows, in
                                          uint32_t* d_syms_out, int32_t* d_best_matches, int32_t* d_best_rotations,
                                          int32_t* d_best_idx, uint8_t* d_bits, int64_t bits_length, void* stream);
 
+/* ---- CP2FSK demodulation (demodulationRoutines.py:20-37, 1214-1330).  Added after ABI 1.10 without a version bump, detected by
+ * symbol.  With g[n] = exp(j pi h n / up), n < up (float64, rounded once to float32), for a position i of a row:
+ *   c0[i] = |sum_n x[i + n] g[n]|, c1[i] = |sum_n x[i + n] conj(g[n])|, bit[i] = (c1[i] > c0[i]), m[i] = max(c0[i], c1[i])
+ * (float32 sums in a fixed order).  1 <= up <= 256.  No argument combination reaches outside a row: what does not fit is
+ * refused with CAF_ERR_INVALID before anything is launched. */
+/* the positions i = start + k step, k < count, of every row of d_x (rows, xlength) complex64: step = 1 slides, step = up walks
+ * symbol by symbol.  d_c0, d_c1, d_max (rows, count) float32 and d_bits (rows, count) uint8; any of them may be NULL. */
+CAF_EXPORT int32_t caf_cp2fsk_tone_metric(const float* d_x, int64_t rows, int64_t xlength, int32_t up, double h, int64_t start,
+                                          int64_t step, int64_t count, float* d_c0, float* d_c1, float* d_max, uint8_t* d_bits,
+                                          void* stream);
+/* d_costs[row][k] (float64) = sum_b sum_{j < burst_len} d_max[row][search_start + k + burst_starts[b] + j up], k < search_count.
+ * burst_starts is a HOST array of num_bursts sample offsets >= 0 (up to 128 of them travel with the launch; a longer list is
+ * uploaded first, which waits for the stream once). */
+CAF_EXPORT int32_t caf_cp2fsk_comb_costs(const float* d_max, int64_t rows, int64_t mlength, int32_t up, int32_t burst_len,
+                                         const int64_t* burst_starts, int32_t num_bursts, int64_t search_start,
+                                         int64_t search_count, double* d_costs, void* stream);
+/* BurstyDemodulatorCP2FSK.demod of every row: sliding metrics, costs of the search range, d_mi[row] (int64) = search_start + the
+ * first arg max of the row's costs, d_dbits (rows, num_bursts burst_len) uint8 = bit[mi + burst_starts[b] + j up];
+ * d_costs (rows, search_count) float64 is optional. */
+CAF_EXPORT int32_t caf_cp2fsk_bursty_demod(const float* d_x, int64_t rows, int64_t xlength, int32_t up, double h, int32_t burst_len,
+                                           const int64_t* burst_starts, int32_t num_bursts, int64_t search_start,
+                                           int64_t search_count, int64_t* d_mi, uint8_t* d_dbits, double* d_costs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

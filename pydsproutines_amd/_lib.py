@@ -232,6 +232,9 @@ _SIGNATURES = {
     "caf_compare_int_preambles": [_P, _I64, _I64, _I32, _I32, _P, _I32, _P, _I32, _I32, _I32, _P, _P, _P],
     "caf_cut_rotate_gray": [_P, _I64, _P, _I64, _P, _I32, _P, _I32, _I64, _P, _P, _P, _P],
     "caf_amble_search_bits": [_P, _I64, _I64, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I64, _P],
+    "caf_cp2fsk_tone_metric": [_P, _I64, _I64, _I32, ct.c_double, _I64, _I64, _I64, _P, _P, _P, _P, _P],
+    "caf_cp2fsk_comb_costs": [_P, _I64, _I64, _I32, _I32, _P, _I32, _I64, _I64, _P, _P],
+    "caf_cp2fsk_bursty_demod": [_P, _I64, _I64, _I32, ct.c_double, _I32, _P, _I32, _I64, _I64, _P, _P, _P, _P],
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

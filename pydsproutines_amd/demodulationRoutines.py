@@ -6,6 +6,10 @@ no CPU path for the signal; host arrays are uploaded, ``DeviceArray``s are used 
 what went in.  The byte bookkeeping the reference does in NumPy (``symsToBits``, ``unpackToBinaryBytes``,
 ``packBinaryBytesToBits``, ``findPlainText``, ``prepareIntPreambles``) stays NumPy.
 
+``demodulateCP2FSK`` / ``cupyDemodulateCP2FSK`` and ``BurstyDemodulator`` / ``BurstyDemodulatorCP2FSK`` (ref :20-37, 1214-1353) run
+the kernels of ``csrc/caf_cpfsk.hip``: the two tone correlations of every position in one pass, the bursts' costs as a moving sum
+along the polyphase branches, the arg max and the bits on the device.
+
 CUDA tuning arguments (THREADS_PER_BLOCK, THREADS_PER_BLK) are accepted and ignored, and the 48 000-byte shared-memory
 ``MemoryError`` does not exist: a row of any length is processed (DESIGN 4.9 lists every deviation).  The device phase lock
 takes the leading eigenvector in closed form, so a burst agrees with a LAPACK-based demodulator up to one constellation
@@ -22,7 +26,8 @@ from .devarray import DeviceArray, asarray, empty, requireDtype
 from .timingRoutines import Timer
 
 __all__ = ["SimpleDemodulatorPSK", "SimpleDemodulatorBPSK", "SimpleDemodulatorQPSK", "SimpleDemodulator8PSK",
-           "CupyDemodulatorPSK", "CupyDemodulatorQPSK", "demodulateBursts", "DemodulatedBursts"]
+           "CupyDemodulatorPSK", "CupyDemodulatorQPSK", "demodulateBursts", "DemodulatedBursts", "demodulateCP2FSK",
+           "cupyDemodulateCP2FSK", "BurstyDemodulator", "BurstyDemodulatorCP2FSK"]
 
 cupyRequireDtype = requireDtype
 
@@ -741,3 +746,181 @@ def demodulateBursts(d_xbatch, osr: int, m, preambles=None, searchStart: int = 0
                     want=("eo_index", "eo_metric", "angle", "svd"), preambles=pre, stream=stream)
     return DemodulatedBursts(syms=out["syms"], eo_index=out["eo_index"], eo_metric=out["eo_metric"], angle=out["angle"],
                              svd_metric=out["svd"], best=out.get("best"), payload=out.get("payload"), count=out.get("count"))
+
+
+# %% CP2FSK
+def _cp2fsk_tones(h, up):
+    """(2, up) complex128: row 0 the tone of bit 0, exp(-j pi h n / up), row 1 the tone of bit 1, its conjugate"""
+    g = np.exp(1j * np.pi * h * np.arange(up) / up)
+    return np.vstack((g.conj(), g))
+
+
+def _tone_metric(d_x, rows, xlength, up, h, start, step, count, want, stream=None):
+    """One launch of caf_cp2fsk_tone_metric; the dict of the (rows, count) outputs named in ``want``: c0, c1, max, bits."""
+    out = {k: DeviceArray((rows, count), np.uint8 if k == "bits" else np.float32) for k in want}
+    _lib.check(_lib.load().caf_cp2fsk_tone_metric(_p(d_x), rows, xlength, int(up), float(h), int(start), int(step), int(count),
+                                                  _p(out.get("c0")), _p(out.get("c1")), _p(out.get("max")), _p(out.get("bits")),
+                                                  _st(stream)), "caf_cp2fsk_tone_metric")
+    for arr in out.values():
+        arr._base = d_x  # (asynchronous: the input lives as long as the results)
+    return out
+
+
+def _cp2fsk_symbols(x, h, up):
+    """the symbol-aligned launch of a host or device row; (None, 0) for a row shorter than one symbol"""
+    if not 1 <= up <= 256:
+        raise ValueError("up must be within 1 .. 256.")
+    numSyms = x.size // int(up)
+    if numSyms < 1:
+        return None, numSyms
+    _lib.require_device()
+    return _tone_metric(asarray(x), 1, x.size, up, h, 0, up, numSyms, ("c0", "c1", "bits")), numSyms
+
+
+def demodulateCP2FSK(syms, h, up):
+    """Symbol-by-symbol CP2FSK decisions of ``syms`` (``up`` samples per symbol, the symbols starting at sample 0):
+    returns (demodBits uint8[numSyms], bitCost float64 (2, numSyms), tones complex128 (2, up)), numSyms = len(syms) // up.
+    bitCost[k, i] = |vdot(symbol i, tones[k])| and demodBits[i] is its arg max (a tie gives 0).
+
+    NumPy in, NumPy out.  The samples are processed as complex64 and the correlations are float32 sums: complex128 input is
+    rounded once on the way in."""
+    x = np.ascontiguousarray(np.asarray(syms).reshape(-1), dtype=np.complex64)
+    out, numSyms = _cp2fsk_symbols(x, h, up)
+    tones = _cp2fsk_tones(h, up)
+    if out is None:
+        return np.zeros(0, np.uint8), np.zeros((2, 0)), tones
+    bitCost = np.vstack((out["c0"].get(), out["c1"].get())).astype(np.float64)
+    return out["bits"].get().reshape(numSyms), bitCost, tones
+
+
+def cupyDemodulateCP2FSK(syms, h: float, up: int):
+    """``demodulateCP2FSK`` of a complex64 device array; the three results are device arrays (demodBits uint8, bitCost float64
+    (2, numSyms), tones complex128 (2, up)).  A host array raises TypeError.  The float32 correlations are widened to the
+    reference's float64 on the host (2 numSyms values), the decisions never leave the device."""
+    if not isinstance(syms, DeviceArray):
+        raise TypeError("Must be a device array (pydsproutines_amd.devarray.DeviceArray).")
+    cupyRequireDtype(np.complex64, syms)
+    if syms.ndim != 1:
+        raise ValueError("Input array must be 1D.")
+    out, numSyms = _cp2fsk_symbols(syms, h, up)
+    tones = _cp2fsk_tones(h, up)
+    if out is None:
+        return asarray(np.zeros(0, np.uint8)), asarray(np.zeros((2, 0))), asarray(tones)
+    bitCost = np.vstack((out["c0"].get(), out["c1"].get())).astype(np.float64)
+    return out["bits"].reshape(numSyms), asarray(bitCost), asarray(tones)
+
+
+class BurstyDemodulator:
+    """Demodulators that align all bursts of a record at once: one cost per candidate start, summed over every symbol of
+    every burst, so that no burst can slip by a symbol against the others (ref :1237-1257).  burstLen and guardLen count
+    symbols; ``up`` is the number of samples per symbol."""
+
+    def __init__(self, burstLen: int, guardLen: int, up: int = 1):
+        self.burstLen = burstLen
+        self.guardLen = guardLen
+        self.period = self.burstLen + self.guardLen
+        self.up = up
+
+    def demod(self, x: np.ndarray, numBursts: int, searchIdx: np.ndarray = None):
+        raise NotImplementedError("Only invoke with derived classes.")
+
+
+class BurstyDemodulatorCP2FSK(BurstyDemodulator):
+    """CP2FSK bursts of burstLen symbols every burstLen + guardLen symbols (ref :1261-1353).  With m[i] the larger of the two
+    tone correlations at sample i, the cost of a start s is the sum of m[s + genIdx], genIdx the first sample of every symbol
+    of every burst; the start with the largest cost (the first of equals) wins and the bits are the decisions at its symbols.
+
+    The samples are processed as complex64 and the correlations are float32 sums (complex128 input is rounded once); the
+    costs are accumulated in float64.  ``plotCosts`` is not provided, as with the other plotting methods."""
+
+    def __init__(self, burstLen: int, guardLen: int, up: int = 1, h: float = 0.5):
+        super().__init__(burstLen, guardLen, up)
+        self.h = h
+        self.burstIdxs = None
+        self.d_costs = None
+        self.searchIdx = None
+
+    def setBurstIdxs(self, burstIdxs: np.ndarray = None):
+        """The indices of the bursts to demodulate (in periods from the first one); bursts may be left out."""
+        self.burstIdxs = burstIdxs
+
+    def _starts(self, numBursts):
+        if self.burstIdxs is None:
+            if numBursts is None:
+                raise ValueError("Please call setBurstIdxs() before demodulating or set the numBursts argument.")
+            self.setBurstIdxs(np.arange(numBursts))
+        starts = np.ascontiguousarray(np.asarray(self.burstIdxs, dtype=np.int64).reshape(-1) * (self.period * self.up))
+        if starts.size < 1 or starts.min() < 0:
+            raise ValueError("burstIdxs must hold at least one index, none of them negative.")
+        return starts
+
+    def _run(self, d_x, rows, n, starts, searchStart, searchCount, stream=None):
+        d_mi = DeviceArray((rows,), np.int64)
+        d_dbits = DeviceArray((rows, starts.size, self.burstLen), np.uint8)
+        d_costs = DeviceArray((rows, searchCount), np.float64)
+        _lib.check(_lib.load().caf_cp2fsk_bursty_demod(_p(d_x), rows, n, int(self.up), float(self.h), int(self.burstLen),
+                                                       starts.ctypes.data, int(starts.size), int(searchStart), int(searchCount),
+                                                       _p(d_mi), _p(d_dbits), _p(d_costs), _st(stream)), "caf_cp2fsk_bursty_demod")
+        for arr in (d_mi, d_dbits, d_costs):
+            arr._base = d_x
+        return d_dbits, d_mi, d_costs
+
+    def _default_count(self, n, starts):
+        """upstream's range: every start at which the LAST listed symbol still has its correlation"""
+        return (n - self.up + 1) - int(starts[-1] + (self.burstLen - 1) * self.up)
+
+    def demod(self, x, numBursts: int = None, searchIdx: np.ndarray = None):
+        """(dbits (numBursts, burstLen) uint8, mi) of one record, NumPy or device array.  searchIdx: the candidate starts;
+        by default every start that keeps the last symbol inside the record.  An arbitrary searchIdx is served by its
+        covering contiguous range on the device, from which the listed starts are selected on the host.
+        Leaves burstIdxs, d_costs (float64, one per searchIdx) and searchIdx behind."""
+        starts = self._starts(numBursts)
+        if isinstance(x, DeviceArray):
+            cupyRequireDtype(np.complex64, x)
+            d_x = x
+        else:
+            d_x = np.ascontiguousarray(np.asarray(x), dtype=np.complex64)
+        if d_x.ndim != 1:
+            raise ValueError("Input array must be 1D.")
+        n = d_x.size
+        if searchIdx is None:
+            count = self._default_count(n, starts)
+            if count < 1:
+                raise ValueError("The record is too short for the bursts: the search range is empty.")
+            searchIdx = np.arange(count)
+        else:
+            searchIdx = np.asarray(searchIdx).reshape(-1)
+            if searchIdx.size < 1 or not np.issubdtype(searchIdx.dtype, np.integer) or searchIdx.min() < 0:
+                raise ValueError("searchIdx must hold at least one index, all of them integers >= 0.")
+        _lib.require_device()
+        d_x = asarray(d_x)
+        lo, hi = int(searchIdx.min()), int(searchIdx.max())
+        d_dbits, d_mi, d_costs = self._run(d_x, 1, n, starts, lo, hi - lo + 1)
+        costs = d_costs.get()[0]
+        self.d_costs = costs[searchIdx - lo]
+        mi = searchIdx[np.argmax(self.d_costs)]
+        if int(d_mi.get()[0]) != int(mi):  # (the best of the covering range is not one of the listed starts)
+            d_dbits = self._run(d_x, 1, n, starts, int(mi), 1)[0]
+        self.searchIdx = searchIdx
+        return d_dbits.get()[0], mi
+
+    def demodBatch(self, d_x, numBursts: int = None, searchStart: int = 0, searchCount: int = None, stream=None):
+        """Every row of a (rows, n) complex64 device array at once, nothing returning to the host: device arrays
+        dbits (rows, numBursts, burstLen) uint8, mi (rows,) int64 and costs (rows, searchCount) float64 of the starts
+        searchStart .. searchStart + searchCount - 1 (by default up to the last start that keeps every symbol in the row).
+        Asynchronous on ``stream``."""
+        if not isinstance(d_x, DeviceArray):
+            raise TypeError("Must be a device array (pydsproutines_amd.devarray.DeviceArray).")
+        cupyRequireDtype(np.complex64, d_x)
+        if d_x.ndim == 1:
+            d_x = d_x.reshape((1, -1))
+        if d_x.ndim != 2:
+            raise ValueError("Input must be 1D or 2D array.")
+        starts = self._starts(numBursts)
+        rows, n = d_x.shape
+        if searchCount is None:
+            searchCount = (n - self.up + 1) - int(starts.max() + (self.burstLen - 1) * self.up) - int(searchStart)
+        if searchStart < 0 or searchCount < 1:
+            raise ValueError("The search range is empty.")
+        _lib.require_device()
+        return self._run(d_x, rows, n, starts, searchStart, searchCount, stream)

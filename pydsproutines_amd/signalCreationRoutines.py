@@ -1,6 +1,7 @@
 """Synthetic-signal helpers the xcorr benchmarks use (host side, NumPy): same names, arguments and
 return values as the reference's signalCreationRoutines.py (makeFreq :380-386, randBits :20-21,
-symsFromBits :24-43, randPSKsyms :47-69, randnoise :72-104, addSigToNoise :107-145)."""
+symsFromBits :24-43, randPSKsyms :47-69, randnoise :72-104, addSigToNoise :107-145, makeCPFSKsyms :220-251,
+makePulsedCPFSKsyms :254-293)."""
 
 import numpy as np
 
@@ -73,3 +74,31 @@ def addManySigToNoise(noiseLen, sigStartIdxList, signalList, bw_signal, chnBW, s
         return noise, parts.sum(axis=0) + noise
     tones = np.exp(2j * np.pi * np.asarray(fshifts, dtype=np.float64)[:, None] * np.arange(noiseLen) / chnBW)
     return noise, (parts * tones).sum(axis=0) + noise, tones
+
+
+def makeCPFSKsyms(bits, baud, m=2, h=0.5, up=8, phase=0.0):
+    """CPFSK with a rectangular frequency pulse of one symbol: bits (0 / 1) become data = bits * m - 1, the phase moves by
+    pi h data[i] over symbol i, ``up`` samples per symbol, starting from ``phase``.  Returns (sig, fs, data)."""
+    bits = np.asarray(bits)
+    T = 1.0 / baud
+    fs = baud * up
+    data = bits.astype(np.int8) * m - 1
+    k = np.arange(len(bits) * up)
+    i = k // up
+    before = np.concatenate(([0], np.cumsum(data)))[: len(data)]  # the symbols already sent
+    theta = data[i] * np.pi * h * (k / fs - i * T) / T + np.pi * h * before[i] + phase
+    return np.exp(1j * theta), fs, data
+
+
+def makePulsedCPFSKsyms(bits, baud, g=np.ones(8) / 16, m=2, h=0.5, up=8, phase=0.0):
+    """CPFSK with the frequency pulse ``g`` (given at the sample rate, integral 1/2 over its length): the data impulses, one
+    every ``up`` samples from sample 1 on, are convolved with g, accumulated and scaled by 2 pi h.  The full convolution
+    is returned, len(bits) * up + len(g) samples; with the default pulse the first len(bits) * up of them are
+    makeCPFSKsyms.  Returns (sig, fs, data, the phase)."""
+    bits = np.asarray(bits)
+    fs = baud * up
+    data = bits.astype(np.int8) * m - 1
+    impulses = np.zeros(len(bits) * up + 1)
+    impulses[1::up] = data
+    css = np.cumsum(np.convolve(impulses, np.asarray(g, dtype=np.float64))) * 2 * np.pi * h + phase
+    return np.exp(1j * css), fs, data, css
