@@ -161,4 +161,22 @@ void fft_plan_release(FftPlan* p, hipStream_t st) {
     for (FftPlan& e : evicted) e.destroy();  // (outside the lock: hipFree waits for the device)
 }
 
+// rows FFT of a (rows, len) matrix, chunked so that the plan batch is bounded; a plan is checked out per chunk
+int fft_rows(const float2* in, float2* out, int64_t rows, int64_t len, bool inverse, hipStream_t st) {
+    const bool inplace = (out == in);
+    for (int64_t done = 0; done < rows;) {
+        // largest power-of-two chunk <= remaining keeps the number of distinct plans small
+        int64_t chunk = 1;
+        while (chunk * 2 <= rows - done && chunk * 2 * len <= ((int64_t)1 << 27)) chunk *= 2;
+        FftPlan p;
+        int rc = fft_plan_acquire(&p, inverse, (size_t)len, (size_t)chunk, (size_t)len, inplace);
+        if (rc) return rc;
+        rc = p.exec((void*)(in + done * len), inplace ? nullptr : (void*)(out + done * len), st);
+        fft_plan_release(&p, st);
+        if (rc) return rc;
+        done += chunk;
+    }
+    return CAF_OK;
+}
+
 }  // namespace caf

@@ -9,7 +9,7 @@
 //     -> forward transform in LDS -> x taps spectrum (L2-resident table) -> inverse transform in LDS -> kept outputs.
 //     The two transforms chain in registers (caf_ldsfft.h), so a block makes one trip through HBM in each direction.
 //   * longer tap sets: the same algebra on rocFFT rows (gather / multiply / scatter kernels here, orchestration in
-//     caf_ops.hip), any length.
+//     caf_fir.hip), any length.
 #include "caf_internal.h"
 #include "caf_ldsfft.h"
 

@@ -142,6 +142,8 @@ inline int upload_table(const void* host, int64_t bytes, bool pooled, void** out
 int64_t prefix_num_tiles(int64_t m);
 // prefix: energy_prefix_doubles(m) entries (the prefix itself, then the 64-sample chunk energies: caf_energy.h)
 void launch_energy_prefix(const float2* rx, int64_t m, double* tile_sums, double* prefix, hipStream_t st);
+// tile scratch and the prefix for n samples from `sc`, then launch_energy_prefix
+int energy_prefix(const float2* x, int64_t n, Scratch& sc, double** prefix, hipStream_t st);
 void launch_inv_energy(const float2* rx, int64_t rx_len, const double* prefix, int64_t shift_start, int64_t num_shifts,
                        const int32_t* gstart, const int32_t* glen, int32_t ngroups, float* inv_e, hipStream_t st);
 // peak records from finished (T, S) rows: rows_peak_chunks(S) records per template
@@ -169,7 +171,8 @@ void launch_peak_reduce(const PeakRec* partial, int64_t count, int64_t stride, i
                         float* pv, int32_t* pd, int32_t* pf, hipStream_t st);
 void scan_tiles(double* tile_sums, int64_t ntiles, hipStream_t st);
 
-// caf_rows.hip
+// caf_rows.hip: the toolbox kernels that more than one translation unit launches
+inline unsigned cdiv(int64_t a, int64_t b) { return (unsigned)((a + b - 1) / b); }
 void launch_sliding_multiply(const float2* x, int32_t xlen, const float2* y, int64_t ylen, const double* prefix,
                              int64_t start, int64_t step, int64_t rows, double coef, int32_t zero_oor, float2* z,
                              hipStream_t st, const double* d_coef = nullptr);  // d_coef: device scalar multiplied into coef (launch_cutout_norm's result)
@@ -178,47 +181,15 @@ void launch_rows_argmax(const float2* z, int64_t rows, int64_t len, int32_t use_
                         float* maxv, float* plane, hipStream_t st, unsigned long long* part = nullptr,
                         int32_t nan_empty = 0);  // nan_empty: an all-NaN row is (NaN, 0), not the CUDA workspace's (0, 0)
 int rows_argmax_chunks(int64_t rows, int64_t len);
-void launch_magnsq(const void* x, int64_t n, int in_c128, void* out, int out_f64, hipStream_t st);
-int64_t moving_num_tiles(int64_t n);
-void launch_moving_average(const float* x, int64_t n, int32_t L, int32_t sum_instead, double* tile_sums,
-                           double* prefix, float* out, hipStream_t st);
-int moving_tile_max_window();
-void launch_moving_tile(const float* x, int64_t rows, int64_t n, int32_t L, int32_t sum_instead, float* out,
-                        hipStream_t st);
-void launch_complex_moving_sum(const float2* x, int64_t n, int32_t L, float* out, hipStream_t st);
-void launch_multi_template_dot(const float2* tm, const float* te, int32_t ntm, int32_t L, const float2* x, int64_t xlen,
-                               const double* prefix, int64_t start, int64_t nslides, int32_t* tidx, float* qf2,
-                               hipStream_t st);
-void launch_multiply_indexed_rows(const float2* x, int64_t xlen, const float2* rows, int32_t row_len,
-                                  const int32_t* slice_start, const int32_t* slice_lens, const int32_t* row_idx,
-                                  int32_t slice_len, int64_t nslices, float2* out, hipStream_t st);
-void launch_copy_slices(const float2* x, int64_t xlen, const int32_t* starts, int32_t starts_stride, int64_t start0,
-                        int64_t inc, int32_t len, int64_t rows, float2* out, hipStream_t st);
-void launch_copy_groups(const float2* x, float2* y, const int32_t* xs, const int32_t* ys, const int32_t* lens,
-                        int32_t ngroups, hipStream_t st);
 int64_t local_maxima_scratch_ints(int64_t n);
 void launch_find_local_maxima(const float* x, int64_t n, float min_height, int32_t* tile_scratch, int32_t max_out,
                               int32_t* idx, int32_t* count, hipStream_t st);
-void launch_gather_b32(const void* x, int64_t xlen, const int32_t* idx, int64_t n, void* out, hipStream_t st);
-void launch_gather_f32_f64(const float* x, int64_t xlen, const int32_t* idx, int64_t n, double* out, hipStream_t st);
-// (these three return the name of the kernel they launched, for the CAF_FIR_DEBUG report)
-const char* launch_fir(const float2* x, int64_t n, const float* taps, int32_t ntaps, const float2* delay, int32_t dlen,
-                int32_t dsr, int32_t phase, float2* out, int64_t nout, hipStream_t st);
-bool fir_decim_ok(int32_t ntaps, int32_t dsr);
-bool fir_poly_fits(int32_t ntaps, int32_t dsr);  // ... and the register-tiled polyphase kernel takes it (small decimation factors)
-const char* launch_iq16_fir(const int16_t* iq, int64_t n, float scale, const float* taps, int32_t ntaps, const int16_t* delay,
-                     int32_t dlen, int32_t dsr, int32_t phase, float2* out, int64_t nout, hipStream_t st);
-const char* launch_upfirdn(const float2* x, int64_t rows, int64_t n, const float* taps, int32_t ntaps, int32_t up, int32_t down,
-                    int64_t nout, float2* out, float* out_abs, hipStream_t st);
 void launch_rows_mul_vec(const float2* x, int64_t in_pitch, int64_t in_off, const float2* v, int64_t len, float2* y,
                          int64_t out_pitch, int64_t pad_to, int64_t rows, float scale, hipStream_t st);
 void launch_complex_norm(const float2* pbuf, int32_t pitch, int32_t nfreq, const float* tscale, const float* inv_e,
                          int64_t num_shifts, int32_t step, int32_t blk0, int32_t nblk, int32_t nhyp, float2* cqf,
                          hipStream_t st);
 void launch_scale(float2* y, int64_t n, float scale, hipStream_t st);
-void launch_iq16_to_c64(const short* in, int64_t nsamp, float scale, float2* out, hipStream_t st);
-void launch_argmax3d_u32(const uint32_t* x, int64_t items, int32_t d1, int32_t d2, int32_t d3, uint32_t* argmax,
-                         uint32_t* maxv, hipStream_t st);
 
 // caf_perdelay.hip: fused per-delay correlator (product -> LDS FFT -> |.|^2 -> argmax), power-of-two n in [64, 16384]
 bool perdelay_fused_ok(int32_t n);
@@ -277,16 +248,6 @@ void launch_zoom_finish(const float* trace, const int32_t* row_arg, const double
                         int32_t* o_count, int32_t* o_delay, int32_t* o_cidx, float* o_cqf2, int32_t* o_fidx, double* o_ffreq,
                         float* o_fqf2, hipStream_t st);
 
-// caf_wola.hip: WOLA channeliser.  Fused in-LDS kernel for N = 2^6 .. 2^14 and P = L / N <= WOLA_FUSED_PMAX; the polyphase
-// sums of any N for the rocFFT rows (rotation of the odd rows folded in), and the (rows, N) -> (N, rows) transpose
-constexpr int WOLA_FUSED_PMAX = 64;
-bool wola_fused_ok(int32_t N, int64_t P);
-int launch_wola_fused(const float2* x, const float2* hist, int64_t hlen, const float* taps, int32_t P, int32_t N, int32_t dec,
-                      int32_t layout, float2* out, int64_t rows, hipStream_t st);
-int launch_wola_poly(const float2* x, const float2* hist, int64_t hlen, const float* taps, int32_t P, int32_t N, int32_t dec,
-                     float2* V, int64_t rows, hipStream_t st);
-int launch_wola_transpose(const float2* src, int64_t rows, int32_t N, float2* dst, hipStream_t st);
-
 // caf_firos.hip: overlap-save FIR (fused in-LDS form for <= 8192 taps; gather / scatter kernels for the rocFFT rows)
 int fir_os_fused_block(int32_t ntaps);
 // rows > 1: independent signals x + r x_row_stride -> out + r out_row_stride in one launch (no carried-in history)
@@ -314,17 +275,6 @@ void launch_transpose_norm_argmax(const float* vt, int32_t ntmpl, int32_t nfreq,
                                   const float* inv_e, int64_t num_shifts, int64_t shift_start, int32_t step,
                                   int32_t blk0, int32_t nblk, int32_t tiles_per_blk, float* surface, float* row_max,
                                   int32_t* row_arg, PeakRec* partial, int64_t partial_per_tmpl, hipStream_t st);
-void launch_colmax_abs(const float2* z, int32_t rows, int64_t n, float* maxv, void* arg, int32_t arg64, hipStream_t st);
-void launch_colmax_sqrt(const float* q, int32_t rows, int64_t n, float* maxv, int64_t* arg, hipStream_t st);
-void launch_dot_tones(double f0, double fstep, int32_t num_freqs, int64_t len, const float2* src, float2* out,
-                      hipStream_t st);
-void launch_mul_conj(const float2* a, const float2* b, int64_t n, float2* out, hipStream_t st);
-void launch_steer_dot(const float2* vec, const double2* steer, int64_t rows, int64_t n, double scale, double2* out,
-                      hipStream_t st);
-void launch_sum_planes_qf2(const float2* planes, int64_t plane_elems, int32_t cols, const int32_t* h_idx, int32_t nsel,
-                           const double* row_norm, double ynormsq, double* out, hipStream_t st);
-void launch_sum_groups_qf2(const float2* planes, int32_t ngroups, int64_t plane_elems, int32_t cols, const float2* phase,
-                           const double* row_norm, double ynormsq, double* out, hipStream_t st);
 
 // Arguments of the work-queue kernel k_caf_persistent, kept in device memory: each role reads the fields it
 // needs at the start of a work item (scalar loads), so the other role's arguments do not occupy SGPRs.
@@ -398,6 +348,8 @@ private:
 // stream takes no scratch (caf_fft_rows), behind the event recorded here.
 int fft_plan_acquire(FftPlan* out, bool inverse, size_t len, size_t batch, size_t dist, bool inplace = true);
 void fft_plan_release(FftPlan* p, hipStream_t st = nullptr);
+// rows FFT of a (rows, len) matrix, chunked so that the plan batch is bounded; a plan is checked out per chunk
+int fft_rows(const float2* in, float2* out, int64_t rows, int64_t len, bool inverse, hipStream_t st);
 
 #define CAF_REQUIRE(cond, msg)      \
     do {                            \

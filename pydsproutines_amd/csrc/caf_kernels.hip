@@ -567,6 +567,15 @@ void launch_energy_prefix(const float2* rx, int64_t m, double* tile_sums, double
     launch_prefix_tiles<1>(rx, m, tile_sums, prefix, st);
 }
 
+int energy_prefix(const float2* x, int64_t n, Scratch& sc, double** prefix, hipStream_t st) {
+    double* tiles = nullptr;
+    int rc = sc.get(&tiles, prefix_num_tiles(n) + 1024);
+    if (rc) return rc;
+    if ((rc = sc.get(prefix, energy_prefix_doubles(n)))) return rc;
+    launch_energy_prefix(x, n, tiles, *prefix, st);
+    return CAF_OK;
+}
+
 void scan_tiles(double* tile_sums, int64_t ntiles, hipStream_t st) {
     hipLaunchKernelGGL(k_scan_tile_sums, dim3(1), dim3(1024), 0, st, tile_sums, ntiles);
 }

@@ -9,8 +9,10 @@
 //     transform runs in LDS, the row leaves once.  A workgroup holds consecutive rows; the overlapping input windows of
 //     neighbouring rows are re-read from L1/L2.
 //   * general (k_wola_poly + rocFFT rows): any N; the (rows, N) matrix of polyphase sums (rotation folded in) is
-//     transformed in place by a batched backward rocFFT (caf_ops.hip, caf_wola).
+//     transformed in place by a batched backward rocFFT (caf_wola below).
 #include <algorithm>
+#include <cstdio>
+#include <cstdlib>
 
 #include "caf_internal.h"
 #include "caf_ldsfft.h"
@@ -18,6 +20,8 @@
 namespace caf {
 
 namespace {
+
+constexpr int WOLA_FUSED_PMAX = 64;
 
 // extended input: i in [-hlen, 0) -> carried-in history, [0, n) -> x, before the history 0 (i < n always holds here)
 __device__ __forceinline__ float2 wola_xe(const float2* __restrict__ x, const float2* __restrict__ hist, int64_t hlen, int64_t i) {
@@ -169,8 +173,6 @@ int wola_fused_launch(const float2* x, const float2* hist, int64_t hlen, const f
     return CAF_OK;
 }
 
-}  // namespace
-
 bool wola_fused_ok(int32_t N, int64_t P) {
     return N >= 64 && N <= 16384 && (N & (N - 1)) == 0 && P >= 1 && P <= WOLA_FUSED_PMAX;
 }
@@ -216,4 +218,44 @@ int launch_wola_transpose(const float2* src, int64_t rows, int32_t N, float2* ds
     return CAF_OK;
 }
 
+}  // namespace
+
 }  // namespace caf
+
+using namespace caf;
+
+int32_t caf_wola(const float* d_x, int64_t n, const float* d_hist, int64_t hist_len, const float* d_taps, int64_t num_taps,
+                 int32_t num_channels, int32_t dec, int32_t layout, float* d_out, int64_t rows, void* stream) {
+    const int32_t N = num_channels;
+    CAF_REQUIRE(N >= 1 && dec >= 1 && (N == dec || N == 2 * dec),
+                "caf_wola: num_channels must equal dec or 2 * dec (the reference's phase correction)");
+    CAF_REQUIRE(num_taps >= 1 && num_taps % N == 0, "caf_wola: num_taps must be a positive multiple of num_channels");
+    CAF_REQUIRE(layout == 0 || layout == 1, "caf_wola: layout must be 0 (rows, N) or 1 (N, rows)");
+    CAF_REQUIRE(n >= 0 && rows >= 0 && rows <= n / dec, "caf_wola: rows must be <= n / dec");
+    CAF_REQUIRE(hist_len >= 0 && (hist_len == 0 || d_hist), "caf_wola: hist_len > 0 needs d_hist");
+    if (rows == 0) return CAF_OK;
+    CAF_REQUIRE(d_x && d_taps && d_out, "caf_wola: NULL buffer");
+    const int64_t P = num_taps / N;
+    CAF_REQUIRE(P <= 0x7fffffff, "caf_wola: too many taps");
+    hipStream_t st = (hipStream_t)stream;
+    const float2* x = (const float2*)d_x;
+    const float2* h = (const float2*)d_hist;
+    float2* out = (float2*)d_out;
+    // CAF_WOLA_FUSED=0 forces the rocFFT rows (A/B and cross-checks); read per call like CAF_JIT
+    const char* ef = std::getenv("CAF_WOLA_FUSED");
+    const bool fused = wola_fused_ok(N, P) && !(ef && ef[0] == '0');
+    if (const char* ed = std::getenv("CAF_WOLA_DEBUG"))
+        if (ed[0] == '1')
+            std::fprintf(stderr, "[caf wola] path=%s N=%d dec=%d P=%lld rows=%lld layout=%d\n", fused ? "fused" : "rocfft", (int)N,
+                         (int)dec, (long long)P, (long long)rows, (int)layout);
+    if (fused) return launch_wola_fused(x, h, hist_len, d_taps, (int32_t)P, N, dec, layout, out, rows, st);
+    // general path: polyphase sums (rotation folded in) -> batched backward rocFFT in place -> (layout 1) transpose
+    Scratch sc(st);
+    float2* V = out;
+    int rc;
+    if (layout == 1 && (rc = sc.get(&V, rows * (int64_t)N))) return rc;
+    if ((rc = launch_wola_poly(x, h, hist_len, d_taps, (int32_t)P, N, dec, V, rows, st))) return rc;
+    if ((rc = fft_rows(V, V, rows, N, true, st))) return rc;
+    if (layout == 1 && (rc = launch_wola_transpose(V, rows, N, out, st))) return rc;
+    return sc.finish();
+}

@@ -720,7 +720,7 @@ def synthetic_traces(S):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
-# The rows toolbox (csrc/caf_rows.hip): sliding normalised product, multi-template dot, moving sums, row and column maxima
+# The rows toolbox (csrc/caf_rows.hip, caf_slices.hip, caf_reduce.hip, caf_refine.hip): sliding normalised product, multi-template dot, moving sums, row and column maxima
 # and the elementwise kernels.  Every reference below is a DIRECT float64 / complex128 sum -- no difference of running sums
 # anywhere, which is what oracle.kernels.movingAverage / movingComplexSum are and why they are not the reference here -- and
 # every bound is derived from the arithmetic the kernel does ("The rows toolbox"); none is calibrated on a GPU.

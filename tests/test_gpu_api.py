@@ -925,6 +925,53 @@ def test_copy_and_peak_kernels():
         gather(asarray(np.zeros(4, np.float64)), asarray(np.zeros(1, np.int32)))
 
 
+def test_slice_kernels_beyond_one_launch_of_rows():
+    """65537 slices: the slice copies and the indexed-row product launch at most 65535 rows at a time, so slices 65535 and
+    65536 come from a second launch that has to pick up the tables, the incremental start and the output where the first
+    one stopped.  Starts, lengths and row indices on both sides of that boundary differ from those of slice 0."""
+    import ref64 as R
+    from pydsproutines_amd import asarray
+    from pydsproutines_amd.cupyExtensions import (
+        cupyCopyEqualSlicesToMatrix_32fc,
+        cupyCopyIncrementalEqualSlicesToMatrix_32fc,
+        cupyCopySlicesToMatrix_32fc,
+        multiplySlicesOptimistically,
+    )
+
+    rng = np.random.default_rng(65537)
+    ns, ln, n = 65537, 3, 4096
+    x = cn(rng, n)
+    dx = asarray(x)
+    t = np.arange(ln)
+    starts = rng.integers(0, n - ln + 1, ns).astype(np.int32)
+    starts[[0, 65534, 65535, 65536]] = [7, 100, 200, 300]
+    ref = x[starts[:, None] + t[None, :]]
+    np.testing.assert_array_equal(cupyCopyEqualSlicesToMatrix_32fc(dx, asarray(starts), ln).get(), ref)
+    bounds = np.stack((starts, starts + ln), axis=1).astype(np.int32)
+    np.testing.assert_array_equal(cupyCopySlicesToMatrix_32fc(dx, asarray(bounds), rowLength=ln).get(), ref)
+    np.testing.assert_array_equal(cupyCopyIncrementalEqualSlicesToMatrix_32fc(dx, 1, 0, ln, ns).get(),
+                                  np.broadcast_to(x[1 : 1 + ln], (ns, ln)))
+    xl = cn(rng, 262144)
+    np.testing.assert_array_equal(cupyCopyIncrementalEqualSlicesToMatrix_32fc(asarray(xl), 1, 3, ln, ns).get(),
+                                  xl[(1 + 3 * np.arange(ns))[:, None] + t[None, :]])
+
+    rows = cn(rng, 5 * ln).reshape(5, ln)
+    lens = rng.integers(1, ln + 1, ns).astype(np.int32)
+    ridx = rng.integers(0, 5, ns).astype(np.int32)
+    lens[[0, 65534, 65535, 65536]] = [3, 2, 1, 2]
+    ridx[[0, 65534, 65535, 65536]] = [0, 2, 3, 4]
+    got = multiplySlicesOptimistically(dx, asarray(rows), asarray(starts), asarray(lens), asarray(ridx), outlength=ln).get()
+    # reference and bound of tests/test_gpu_f64_rows.py::test_multiply_slices_indexed_rows: the complex128 product, two
+    # float32 roundings of |row| |x| per component, exact zeros beyond a slice's length
+    g = ref.astype(np.complex128)
+    r = rows[ridx].astype(np.complex128)
+    live = t[None, :] < lens[:, None]
+    want = np.where(live, r * g, 0)
+    unit = np.where(live, 2 * R.EPS32 * np.abs(r) * np.abs(g), 0)
+    ratio = max(R.worst_ratio(got.real, want.real, unit), R.worst_ratio(got.imag, want.imag, unit))
+    assert ratio <= 1.0, "indexed rows over two launches: %.4g of the bound" % ratio
+
+
 def test_czt_objects(golden):
     from pydsproutines_amd import asarray
     from pydsproutines_amd.spectralRoutines import CZTCached, CZTCachedGPU, czt, next_fast_len, pbIppCZT32fc

@@ -1,4 +1,4 @@
-"""The rows toolbox (csrc/caf_rows.hip) against float64, element by element (tests/ref64.py, DESIGN §5 "The rows toolbox"):
+"""The rows toolbox (csrc/caf_rows.hip, caf_slices.hip, caf_reduce.hip, caf_refine.hip, caf_fir.hip) against float64, element by element (tests/ref64.py, DESIGN §5 "The rows toolbox"):
 caf_sliding_multiply_normalised, caf_multi_template_sliding_dot, caf_argmax_abs_rows, caf_complex_magnsq, caf_moving_average,
 caf_complex_moving_sum, caf_multiply_slices_indexed_rows, caf_mul_conj, caf_steer_dot, caf_colmax_abs, caf_colmax_sqrt and
 caf_iq16_to_c64.  Every reference is a direct float64 / complex128 sum, every bound is derived next to its reference in
@@ -23,7 +23,7 @@ Shape -> form (decided by shape alone):
     moving average    L <= 1024 and rows <= 65535: k_moving_tile; else tile-local prefixes in global memory, one row after another
 
 What the C ABI does not reach, and is therefore not here.  caf_sliding_multiply_normalised fixes step = 1 and zero_oor = 0
-and takes the coefficient from the host (caf_ops.hip); start_idx >= 0, so rows leave y at its end only.  The other steps,
+and takes the coefficient from the host (caf_rows.hip); start_idx >= 0, so rows leave y at its end only.  The other steps,
 zero_oor = 1 and the device-side coefficient exist only inside caf_xcorr_perdelay, whose product rows go through the row FFT
 before anything is returned: tests/test_gpu_f64_reference.py holds those planes to float64.  Likewise caf_argmax_abs_rows
 fixes scale = 1, no |z|^2 plane and nan_empty = 0; the plane, nan_empty = 1 and other scales are reached through
