@@ -547,6 +547,43 @@ CAF_EXPORT int32_t caf_cp2fsk_bursty_demod(const float* d_x, int64_t rows, int64
                                            const int64_t* burst_starts, int32_t num_bursts, int64_t search_start,
                                            int64_t search_count, int64_t* d_mi, uint8_t* d_dbits, double* d_costs, void* stream);
 
+/* ---- TDOA / FDOA grid-search geolocation (localizationRoutines.py:510-748, 1380-1511).  Added after ABI 1.10 without a version
+ * bump, detected by symbol.  Everything is float64.  For a grid point p and a measurement record (s1, s2, v1, v2, r, wr, d, wd):
+ *   rho1 = |p - s1|, rho2 = |p - s2|, e = r - (rho2 - rho1), f = d - ((p - s2).v2 / rho2 - (p - s1).v1 / rho1),
+ *   cost[p] = sum_k (wr_k e_k^2 + wd_k f_k^2), in the order of k, the TD term before the FD term of the same k.
+ * The library knows nothing of seconds, hertz or carrier frequencies: r and d are a range difference and a range-rate
+ * difference, wr and wd their weights. */
+#define CAF_LOCATE_POINTS 0   /* d_points: an (n, 3) matrix of points                                               */
+#define CAF_LOCATE_MESH 1     /* p(i, j) = (A[i] C[j], A[i] S[j], Z[i]), flat index i nj + j; never materialised     */
+#define CAF_LOCATE_MESH_XY 2  /* p(i, j) = (X[j], Y[i], z) with X = d_c (nj), Y = d_a (ni); d_z and d_s are not read */
+#define CAF_LOCATE_TD 1       /* the e terms alone: velocities, d and wd are never read                             */
+#define CAF_LOCATE_FD 2       /* the f terms alone                                                                  */
+#define CAF_LOCATE_TDFD 3
+typedef struct {
+    int32_t source;         /* CAF_LOCATE_POINTS, CAF_LOCATE_MESH or CAF_LOCATE_MESH_XY                              */
+    int32_t mode;           /* CAF_LOCATE_TD, CAF_LOCATE_FD or CAF_LOCATE_TDFD                                       */
+    int32_t cost_f32;       /* 1: d_cost is float32 (the float64 cost rounded once), 0: float64                     */
+    int32_t reserved;
+    int64_t n;              /* CAF_LOCATE_POINTS: rows of d_points                                                   */
+    const double* d_points;
+    int32_t ni, nj;         /* the meshes: ni nj points                                                              */
+    const double* d_a;      /* [ni] */
+    const double* d_z;      /* [ni] */
+    const double* d_c;      /* [nj] */
+    const double* d_s;      /* [nj] */
+    double z;               /* CAF_LOCATE_MESH_XY: the constant third coordinate                                     */
+} caf_locate_desc;
+/* d_records: K records of 16 doubles, s1(3) s2(3) v1(3) v2(3) r wr d wd.  d_set_starts (optional, DEVICE, B + 1 increasing
+ * offsets from 0 to K) cuts the table into B sets of at least one record each: B cost grids over the same points in one
+ * launch (offsets are clamped into [0, K], so no content of that array reaches outside the table); NULL: B = 1.
+ * Outputs, each optional: d_cost (B, N) float64 or float32; d_min_val (B) float64 and d_min_idx (B) int64, the minimum of
+ * each set's costs and the FIRST index that has it.  A NaN cost (an FD term at a point that coincides with a sensor is 0 / 0)
+ * is stored as NaN and never wins; a set with nothing but NaN reports (NaN, -1). */
+CAF_EXPORT int32_t caf_locate_grid(const caf_locate_desc* desc, const double* d_records, int64_t K, const int64_t* d_set_starts,
+                                   int32_t B, void* d_cost, double* d_min_val, int64_t* d_min_idx, void* stream);
+/* the launch geometry: points per workgroup and records per staged chunk (the sizes at which the kernel changes path) */
+CAF_EXPORT int32_t caf_locate_geometry(int32_t* points_per_workgroup, int32_t* records_per_chunk);
+
 #ifdef __cplusplus
 }
 #endif

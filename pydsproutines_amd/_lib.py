@@ -141,6 +141,31 @@ class CafDemodDesc(ct.Structure):
     ]
 
 
+class CafLocateDesc(ct.Structure):
+    _fields_ = [
+        ("source", ct.c_int32),
+        ("mode", ct.c_int32),
+        ("cost_f32", ct.c_int32),
+        ("reserved", ct.c_int32),
+        ("n", ct.c_int64),
+        ("d_points", ct.c_void_p),
+        ("ni", ct.c_int32),
+        ("nj", ct.c_int32),
+        ("d_a", ct.c_void_p),
+        ("d_z", ct.c_void_p),
+        ("d_c", ct.c_void_p),
+        ("d_s", ct.c_void_p),
+        ("z", ct.c_double),
+    ]
+
+
+CAF_LOCATE_POINTS = 0
+CAF_LOCATE_MESH = 1
+CAF_LOCATE_MESH_XY = 2
+CAF_LOCATE_TD = 1
+CAF_LOCATE_FD = 2
+CAF_LOCATE_TDFD = 3
+
 CAF_DEMOD_LOCK_EIG = 0
 CAF_DEMOD_LOCK_POWERSUM = 1
 CAF_DEMOD_LOCK_NONE = 2
@@ -235,6 +260,8 @@ _SIGNATURES = {
     "caf_cp2fsk_tone_metric": [_P, _I64, _I64, _I32, ct.c_double, _I64, _I64, _I64, _P, _P, _P, _P, _P],
     "caf_cp2fsk_comb_costs": [_P, _I64, _I64, _I32, _I32, _P, _I32, _I64, _I64, _P, _P],
     "caf_cp2fsk_bursty_demod": [_P, _I64, _I64, _I32, ct.c_double, _I32, _P, _I32, _I64, _I64, _P, _P, _P, _P],
+    "caf_locate_grid": [ct.POINTER(CafLocateDesc), _P, _I64, _P, _I32, _P, _P, _P, _P],
+    "caf_locate_geometry": [ct.POINTER(_I32), ct.POINTER(_I32)],
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -1,0 +1,331 @@
+// TDOA / FDOA grid-search geolocation (localizationRoutines.py:510-748: gridSearchTDOA, gridSearchFDOA, gridSearchTDOA_direct,
+// gridSearchTDFD_direct and the gridsearchtdoa_kernel of gridSearchTDOA_gpu).  Everything is float64.  For a grid point p and the
+// measurement record k = (s1, s2, v1, v2, r, wr, d, wd):
+//   rho1 = |p - s1|, rho2 = |p - s2|,   e = r - (rho2 - rho1),   f = d - ((p - s2).v2 / rho2 - (p - s1).v1 / rho1)
+//   cost[p] = sum_k (wr e^2 + wd f^2)       in the order of k, the TD term before the FD term of the same k.
+//
+//   k_locate<TD, FD, SRC>  one workgroup per LOC_P = 1024 consecutive points (four per thread, 256 apart, all in registers, so the
+//                          reciprocal-square-root chains of different points overlap) and per measurement set (blockIdx.y).  The
+//                          records are staged in LDS LOC_C = 64 at a time -- read from global memory once per workgroup -- and read
+//                          back as broadcasts, one record for the thread's four points.  A TD instantiation never reads a velocity.
+//                          SRC: an (N, 3) matrix, or a separable mesh that is never materialised,
+//                          p(i, j) = (A[i] C[j], A[i] S[j], Z[i]) or (XY) p(i, j) = (X[j], Y[i], z), flat index i nj + j.
+//   k_locate_fold          the workgroups' (minimum, index) partials of each set -> one (value, index) per set.
+//
+// One range costs: a = p - s (3 subtractions), d2 = a.a (one product and two fma), y = 1 / sqrt(d2) from v_rsq_f64 and ONE
+// third-order correction y0 + y0 e (1/2 + 3/8 e), e = 1 - d2 y0^2 (the hardware estimate is good to about 2^-23, so the e^3 that is
+// left is below 2^-65), and rho = d2 y.  The same y scales the dot product (p - s).v, so no division and no second root is taken.
+// In units of eps = 2^-53 relative to rho: 1 (the subtractions: every component of a is off by at most eps, and so is its norm)
+// + 1.5 (three roundings in d2, halved by the root) + 1.5 (the correction: e is known to eps absolute and enters with weight 1/2,
+// and the closing fma rounds once) + 1 (the product d2 y) = 5; the difference rho2 - rho1 rounds once more, at most eps max(rho1,
+// rho2).  tests/locate_ref.py therefore bounds the error of rho2 - rho1 by c1 eps (rho1 + rho2) with c1 = 6.  A projected velocity
+// a.v y: 1 (a) + 3 (one product and two fma) relative to sum_i |a_i v_i|, 4 for y as above, 1 for the product with y, and the
+// difference of the two rounds once: c2 = 10 relative to sum_i |a_i v1_i| / rho1 + sum_i |a_i v2_i| / rho2.
+//
+// A point ON a sensor has d2 = 0: its range is 0 (selected, not computed) and its unit vector is 0 / 0 = NaN as in the reference, so
+// its TD cost is finite and its FD cost NaN.  A NaN cost is stored as NaN and never wins the arg min.
+//
+// Arg min, in a fixed order and without atomics: a thread visits its points in increasing index and keeps the first minimum (strict
+// <); across lanes caf::wave_argmax on the negated cost (lower index wins a tie); the workgroup's four waves through LDS with the
+// same comparison; the partials of a set, in increasing order of workgroup, by k_locate_fold in the same way.
+// Floating-point contraction is off in this file: every product and sum is rounded where it is written, and each fma is spelled.
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+
+#include "caf_internal.h"
+#include "caf_wave.h"
+
+#pragma clang fp contract(off)
+
+namespace caf {
+
+namespace {
+
+constexpr int LOC_T = 256;              // threads per workgroup
+constexpr int LOC_PPT = 4;              // points per thread
+constexpr int LOC_P = LOC_T * LOC_PPT;  // points per workgroup
+constexpr int LOC_C = 64;               // records per LDS chunk (8 KiB)
+constexpr int LOC_REC = 16;             // doubles per record: s1(3) s2(3) v1(3) v2(3) r wr d wd
+constexpr long long NO_INDEX = INT64_MAX;
+
+struct LocSrc {
+    const double* pts;                  // CAF_LOCATE_POINTS: (n, 3)
+    const double *a, *z, *c, *s;        // meshes: a, z of ni entries (XY: a = Y), c, s of nj entries (XY: c = X)
+    double z0;                          // XY: the constant height
+    int32_t ni, nj;
+    int32_t step_i, step_j;             // LOC_T / nj and LOC_T % nj: the mesh coordinates of a thread's next point
+};
+
+// 1 / sqrt(x), x > 0 finite: the hardware estimate and one third-order correction (see the head of the file)
+__device__ __forceinline__ double rsqrt_once(double x) {
+    const double y0 = __builtin_amdgcn_rsq(x);
+    const double t = x * y0;
+    const double e = fma(-t, y0, 1.0);
+    return fma(y0 * e, fma(e, 0.375, 0.5), y0);
+}
+
+__device__ __forceinline__ bool less_first(double v, long long i, double bv, long long bi) { return v < bv || (v == bv && i < bi); }
+
+// the workgroup's (minimum, index) from every thread's: left in thread 0
+__device__ __forceinline__ void group_argmin(double& bv, long long& bi, double* s_v, long long* s_i) {
+    double nv = -bv;
+    wave_argmax(nv, bi);
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        s_v[w] = -nv;
+        s_i[w] = bi;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        bv = s_v[0];
+        bi = s_i[0];
+        for (int k = 1; k < LOC_T / 64; k++)
+            if (less_first(s_v[k], s_i[k], bv, bi)) {
+                bv = s_v[k];
+                bi = s_i[k];
+            }
+    }
+}
+
+template <bool TD, bool FD, int SRC>
+__global__ __launch_bounds__(LOC_T) void k_locate(const LocSrc src, int64_t N, const double* __restrict__ rec, int64_t K,
+                                                  const int64_t* __restrict__ set_starts, void* __restrict__ cost, int cost_f32,
+                                                  double* __restrict__ part_v, int64_t* __restrict__ part_i) {
+    __shared__ double s_rec[LOC_C * LOC_REC];
+    __shared__ double s_v[LOC_T / 64];
+    __shared__ long long s_i[LOC_T / 64];
+    const int tid = threadIdx.x;
+    const int64_t base = (int64_t)blockIdx.x * LOC_P;
+    const int set = blockIdx.y;
+
+    // the records of this set, clamped into the table whatever the offsets say
+    int64_t k0 = 0, k1 = K;
+    if (set_starts) {
+        k0 = std::min(std::max<int64_t>(set_starts[set], 0), K);
+        k1 = std::min(std::max<int64_t>(set_starts[set + 1], k0), K);
+    }
+
+    // the thread's points (one past the end repeats the last point and stores nothing)
+    double px[LOC_PPT], py[LOC_PPT], pz[LOC_PPT], acc[LOC_PPT];
+    if constexpr (SRC == CAF_LOCATE_POINTS) {
+#pragma unroll
+        for (int j = 0; j < LOC_PPT; j++) {
+            const int64_t at = std::min(base + tid + j * LOC_T, N - 1);
+            px[j] = src.pts[3 * at];
+            py[j] = src.pts[3 * at + 1];
+            pz[j] = src.pts[3 * at + 2];
+        }
+    } else {
+        const int64_t at = std::min(base + tid, N - 1);
+        int32_t mi, mj;
+        if (N <= (int64_t)UINT32_MAX) {
+            mi = (int32_t)((uint32_t)at / (uint32_t)src.nj);
+            mj = (int32_t)((uint32_t)at - (uint32_t)mi * (uint32_t)src.nj);
+        } else {
+            mi = (int32_t)(at / src.nj);
+            mj = (int32_t)(at - (int64_t)mi * src.nj);
+        }
+#pragma unroll
+        for (int j = 0; j < LOC_PPT; j++) {
+            const int32_t ci = std::min(mi, src.ni - 1);
+            if constexpr (SRC == CAF_LOCATE_MESH) {
+                const double a = src.a[ci];
+                px[j] = a * src.c[mj];
+                py[j] = a * src.s[mj];
+                pz[j] = src.z[ci];
+            } else {
+                px[j] = src.c[mj];
+                py[j] = src.a[ci];
+                pz[j] = src.z0;
+            }
+            mi += src.step_i;
+            mj += src.step_j;
+            if (mj >= src.nj) {
+                mj -= src.nj;
+                mi++;
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < LOC_PPT; j++) acc[j] = 0.0;
+
+    for (int64_t kc = k0; kc < k1; kc += LOC_C) {
+        const int nrec = (int)std::min<int64_t>(LOC_C, k1 - kc);
+        const double* g = rec + kc * LOC_REC;
+        for (int q = tid; q < nrec * LOC_REC; q += LOC_T) s_rec[q] = g[q];
+        __syncthreads();
+        for (int k = 0; k < nrec; k++) {
+            const double* r = s_rec + k * LOC_REC;  // the same address in every lane: broadcast reads
+            const double s1x = r[0], s1y = r[1], s1z = r[2], s2x = r[3], s2y = r[4], s2z = r[5];
+            double v1x = 0, v1y = 0, v1z = 0, v2x = 0, v2y = 0, v2z = 0, rr = 0, wr = 0, dd = 0, wd = 0;
+            if constexpr (FD) {
+                v1x = r[6], v1y = r[7], v1z = r[8], v2x = r[9], v2y = r[10], v2z = r[11];
+                dd = r[14], wd = r[15];
+            }
+            if constexpr (TD) rr = r[12], wr = r[13];
+#pragma unroll
+            for (int j = 0; j < LOC_PPT; j++) {
+                const double a1x = px[j] - s1x, a1y = py[j] - s1y, a1z = pz[j] - s1z;
+                const double a2x = px[j] - s2x, a2y = py[j] - s2y, a2z = pz[j] - s2z;
+                const double q1 = fma(a1z, a1z, fma(a1y, a1y, a1x * a1x));
+                const double q2 = fma(a2z, a2z, fma(a2y, a2y, a2x * a2x));
+                const double y1 = rsqrt_once(q1), y2 = rsqrt_once(q2);
+                if constexpr (TD) {
+                    const double rho1 = q1 == 0.0 ? 0.0 : q1 * y1;
+                    const double rho2 = q2 == 0.0 ? 0.0 : q2 * y2;
+                    const double e = rr - (rho2 - rho1);
+                    acc[j] = fma(wr, e * e, acc[j]);
+                }
+                if constexpr (FD) {
+                    const double u1 = fma(a1z, v1z, fma(a1y, v1y, a1x * v1x)) * y1;
+                    const double u2 = fma(a2z, v2z, fma(a2y, v2y, a2x * v2x)) * y2;
+                    const double f = dd - (u2 - u1);
+                    acc[j] = fma(wd, f * f, acc[j]);
+                }
+            }
+        }
+        __syncthreads();  // the chunk is overwritten next
+    }
+
+    const int64_t out0 = (int64_t)set * N;
+    if (cost) {
+#pragma unroll
+        for (int j = 0; j < LOC_PPT; j++) {
+            const int64_t at = base + tid + j * LOC_T;
+            if (at >= N) continue;
+            if (cost_f32) ((float*)cost)[out0 + at] = (float)acc[j];
+            else ((double*)cost)[out0 + at] = acc[j];
+        }
+    }
+    if (part_v) {
+        double bv = INFINITY;
+        long long bi = NO_INDEX;
+#pragma unroll
+        for (int j = 0; j < LOC_PPT; j++) {
+            const int64_t at = base + tid + j * LOC_T;
+            if (at < N && less_first(acc[j], at, bv, bi)) {
+                bv = acc[j];
+                bi = at;
+            }
+        }
+        group_argmin(bv, bi, s_v, s_i);
+        if (tid == 0) {
+            const int64_t o = (int64_t)set * gridDim.x + blockIdx.x;
+            part_v[o] = bv;
+            part_i[o] = (int64_t)bi;
+        }
+    }
+}
+
+// the partials of set blockIdx.x (in increasing order of index) -> min_val[set], min_idx[set]; nothing but NaN: (NaN, -1)
+__global__ __launch_bounds__(LOC_T) void k_locate_fold(const double* __restrict__ part_v, const int64_t* __restrict__ part_i, int64_t nparts,
+                                                       double* __restrict__ min_val, int64_t* __restrict__ min_idx) {
+    __shared__ double s_v[LOC_T / 64];
+    __shared__ long long s_i[LOC_T / 64];
+    const int64_t o = (int64_t)blockIdx.x * nparts;
+    double bv = INFINITY;
+    long long bi = NO_INDEX;
+    for (int64_t e = threadIdx.x; e < nparts; e += LOC_T) {
+        const double v = part_v[o + e];
+        const long long i = (long long)part_i[o + e];
+        if (less_first(v, i, bv, bi)) {
+            bv = v;
+            bi = i;
+        }
+    }
+    group_argmin(bv, bi, s_v, s_i);
+    if (threadIdx.x == 0) {
+        const bool none = bi == NO_INDEX;
+        if (min_val) min_val[blockIdx.x] = none ? (double)NAN : bv;
+        if (min_idx) min_idx[blockIdx.x] = none ? (int64_t)-1 : (int64_t)bi;
+    }
+}
+
+template <bool TD, bool FD>
+void launch_mode(int source, dim3 grid, hipStream_t st, const LocSrc& src, int64_t N, const double* rec, int64_t K, const int64_t* starts,
+                 void* cost, int cost_f32, double* pv, int64_t* pi) {
+    if (source == CAF_LOCATE_POINTS)
+        hipLaunchKernelGGL((k_locate<TD, FD, CAF_LOCATE_POINTS>), grid, dim3(LOC_T), 0, st, src, N, rec, K, starts, cost, cost_f32, pv, pi);
+    else if (source == CAF_LOCATE_MESH)
+        hipLaunchKernelGGL((k_locate<TD, FD, CAF_LOCATE_MESH>), grid, dim3(LOC_T), 0, st, src, N, rec, K, starts, cost, cost_f32, pv, pi);
+    else
+        hipLaunchKernelGGL((k_locate<TD, FD, CAF_LOCATE_MESH_XY>), grid, dim3(LOC_T), 0, st, src, N, rec, K, starts, cost, cost_f32, pv, pi);
+}
+
+}  // namespace
+
+}  // namespace caf
+
+using namespace caf;
+
+int32_t caf_locate_geometry(int32_t* points_per_workgroup, int32_t* records_per_chunk) {
+    if (points_per_workgroup) *points_per_workgroup = LOC_P;
+    if (records_per_chunk) *records_per_chunk = LOC_C;
+    return CAF_OK;
+}
+
+int32_t caf_locate_grid(const caf_locate_desc* desc, const double* d_records, int64_t K, const int64_t* d_set_starts, int32_t B,
+                        void* d_cost, double* d_min_val, int64_t* d_min_idx, void* stream) {
+    CAF_REQUIRE(desc != nullptr, "caf_locate_grid: NULL descriptor");
+    CAF_REQUIRE(desc->mode == CAF_LOCATE_TD || desc->mode == CAF_LOCATE_FD || desc->mode == CAF_LOCATE_TDFD,
+                "caf_locate_grid: mode must be CAF_LOCATE_TD, CAF_LOCATE_FD or CAF_LOCATE_TDFD");
+    CAF_REQUIRE(desc->cost_f32 == 0 || desc->cost_f32 == 1, "caf_locate_grid: cost_f32 must be 0 or 1");
+    CAF_REQUIRE(K >= 1 && K <= ((int64_t)1 << 40), "caf_locate_grid: the table needs at least one record");
+    CAF_REQUIRE(B >= 1 && B <= 65535 && (d_set_starts != nullptr || B == 1),
+                "caf_locate_grid: 1 <= sets <= 65535, and more than one set needs set_starts");
+    CAF_REQUIRE((int64_t)B <= K, "caf_locate_grid: every set needs at least one record");
+    LocSrc src = {};
+    int64_t N = 0;
+    if (desc->source == CAF_LOCATE_POINTS) {
+        N = desc->n;
+        CAF_REQUIRE(N >= 1, "caf_locate_grid: the point matrix needs at least one row");
+        CAF_REQUIRE(desc->d_points != nullptr, "caf_locate_grid: NULL point matrix");
+        src.pts = desc->d_points;
+    } else if (desc->source == CAF_LOCATE_MESH || desc->source == CAF_LOCATE_MESH_XY) {
+        CAF_REQUIRE(desc->ni >= 1 && desc->nj >= 1, "caf_locate_grid: the mesh needs ni >= 1 and nj >= 1");
+        N = (int64_t)desc->ni * desc->nj;
+        CAF_REQUIRE(desc->d_a != nullptr && desc->d_c != nullptr, "caf_locate_grid: NULL mesh table");
+        if (desc->source == CAF_LOCATE_MESH) {
+            CAF_REQUIRE(desc->d_z != nullptr && desc->d_s != nullptr, "caf_locate_grid: NULL mesh table");
+        }
+        src.a = desc->d_a;
+        src.z = desc->d_z;
+        src.c = desc->d_c;
+        src.s = desc->d_s;
+        src.z0 = desc->z;
+        src.ni = desc->ni;
+        src.nj = desc->nj;
+        src.step_i = LOC_T / desc->nj;
+        src.step_j = LOC_T % desc->nj;
+    } else {
+        CAF_REQUIRE(false, "caf_locate_grid: unknown point source");
+    }
+    const int64_t tiles = (N + LOC_P - 1) / LOC_P;
+    CAF_REQUIRE(tiles <= 0x7fffffff, "caf_locate_grid: too many points for one launch");
+    CAF_REQUIRE(d_records != nullptr, "caf_locate_grid: NULL record table");
+    const bool want_min = d_min_val != nullptr || d_min_idx != nullptr;
+    if (!d_cost && !want_min) return CAF_OK;
+
+    hipStream_t st = (hipStream_t)stream;
+    Scratch sc(st);
+    double* pv = nullptr;
+    int64_t* pi = nullptr;
+    if (want_min) {
+        int rc;
+        if ((rc = sc.get(&pv, (int64_t)B * tiles)) || (rc = sc.get(&pi, (int64_t)B * tiles))) return rc;
+    }
+    const dim3 grid((unsigned)tiles, (unsigned)B);
+    if (desc->mode == CAF_LOCATE_TD)
+        launch_mode<true, false>(desc->source, grid, st, src, N, d_records, K, d_set_starts, d_cost, desc->cost_f32, pv, pi);
+    else if (desc->mode == CAF_LOCATE_FD)
+        launch_mode<false, true>(desc->source, grid, st, src, N, d_records, K, d_set_starts, d_cost, desc->cost_f32, pv, pi);
+    else
+        launch_mode<true, true>(desc->source, grid, st, src, N, d_records, K, d_set_starts, d_cost, desc->cost_f32, pv, pi);
+    CAF_HIP_TRY(hipGetLastError());
+    if (want_min) {
+        hipLaunchKernelGGL(k_locate_fold, dim3((unsigned)B), dim3(LOC_T), 0, st, pv, pi, tiles, d_min_val, d_min_idx);
+        CAF_HIP_TRY(hipGetLastError());
+    }
+    return sc.finish();
+}

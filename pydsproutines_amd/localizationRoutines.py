@@ -1,0 +1,563 @@
+"""TDOA / FDOA grid-search geolocation on the GPU: the consumers of the CAF peak table (the reference's localizationRoutines.py).
+
+Every (TDOA, FDOA) pair goes into a weighted least-squares cost over a grid of candidate positions,
+
+    cost[p] = sum_k  wr_k (r_k - (|p - s2_k| - |p - s1_k|))^2  +  wd_k (d_k - ((p - s2_k).v2_k / |p - s2_k| - (p - s1_k).v1_k / |p - s1_k|))^2
+
+evaluated in float64 by ``caf_locate_grid`` (csrc/caf_locate.hip) in the order of k, the TD term before the FD term.  The host
+prepares one table of K records (s1, s2, v1, v2, r, wr, d, wd); seconds, hertz and ``fc`` never reach the device.  The grid is
+either an (N, 3) matrix, uploaded once per localizer, or a separable mesh that is never materialised (four small tables for a
+WGS84 lat/lon grid, two and a constant for an XY mesh).  ``locate()`` fuses the arg min and writes no cost grid at all.
+
+The host preparation reproduces the reference's roundings of the measurements (see ``_records_*``); the geometry itself is
+float64 throughout, where the reference's flat functions and its CUDA kernel are float32 (half a metre per ulp in ECEF).
+
+Not provided: ``plot``, ``SatellitePairTDFDMixin`` (needs skyfield and sgp4), the RTT searches, the hyperbola helpers and the
+tangent-plane functions.  There is no CPU path: without a GPU every search raises RuntimeError (argument checks come first).
+The CRB functions are host NumPy, as in the reference.
+"""
+
+import ctypes as ct
+
+import numpy as np
+
+from . import _lib
+from .devarray import DeviceArray, asarray, empty
+
+__all__ = ["gridSearchTDOA", "gridSearchFDOA", "gridSearchTDOA_direct", "gridSearchTDFD_direct", "gridSearchTDOA_gpu",
+           "latlongrid_to_ecef", "calcCRB_TD", "calcCRB_TDFD", "projectCRBtoEllipse", "GridLocalizer", "LatLonGridLocalizer",
+           "TDMixin", "TDFDMixin", "LatLonGridLocalizerTD", "LatLonGridLocalizerTDFD", "locate_geometry"]
+
+LIGHTSPD = 299792458.0
+WGS84_A = 6378137.0            # the two defining constants of WGS84: semi-major axis (m) ...
+WGS84_INV_F = 298.257223563    # ... and inverse flattening
+
+_REC = 16  # doubles per record: s1(3) s2(3) v1(3) v2(3) r wr d wd
+_MODES = {"td": _lib.CAF_LOCATE_TD, "fd": _lib.CAF_LOCATE_FD, "tdfd": _lib.CAF_LOCATE_TDFD}
+
+
+def _p(a):
+    return ct.c_void_p(a.ptr) if a is not None else None
+
+
+def _st(stream):
+    if stream is None or isinstance(stream, ct.c_void_p):
+        return stream
+    return ct.c_void_p(int(stream))
+
+
+def locate_geometry():
+    """(points per workgroup, records per staged chunk) of the kernel: the sizes at which it changes path."""
+    p, c = ct.c_int32(0), ct.c_int32(0)
+    _lib.check(_lib.load().caf_locate_geometry(ct.byref(p), ct.byref(c)), "caf_locate_geometry")
+    return int(p.value), int(c.value)
+
+
+# ---- host preparation of the measurement records ------------------------------------------------------------------------------
+def _k3(a, name, k=None):
+    a = np.asarray(a, dtype=np.float64)
+    if a.ndim != 2 or a.shape[1] != 3 or a.shape[0] < 1:
+        raise ValueError("Ensure %s has 3 columns (and at least one row)." % name)
+    if k is not None and a.shape[0] != k:
+        raise ValueError("%s has %d rows, expected %d." % (name, a.shape[0], k))
+    return a
+
+
+def _k1(a, name, k):
+    a = np.asarray(a, dtype=np.float64).reshape(-1)
+    if a.size != k:
+        raise ValueError("%s has %d entries, expected %d." % (name, a.size, k))
+    return a
+
+
+def _table(s1, s2, v1=None, v2=None, r=None, wr=None, d=None, wd=None):
+    rec = np.zeros((s1.shape[0], _REC), np.float64)
+    rec[:, 0:3], rec[:, 3:6] = s1, s2
+    if v1 is not None:
+        rec[:, 6:9], rec[:, 9:12] = v1, v2
+        rec[:, 14], rec[:, 15] = d, wd
+    if r is not None:
+        rec[:, 12], rec[:, 13] = r, wr
+    return rec
+
+
+def _records_td_direct(s1x_list, s2x_list, tdoa_list, td_sigma_list):
+    """gridSearchTDOA_direct's roundings: r = float32(tdoa c); the reference squares the float32 sigma_r = float32(sigma c) as a
+    float32 scalar before it divides, so wr = 1 / float32(sigma_r^2).  The sensor positions stay float64."""
+    s1 = _k3(s1x_list, "s1x_list")
+    s2 = _k3(s2x_list, "s2x_list", s1.shape[0])
+    k = s1.shape[0]
+    r = (_k1(tdoa_list, "tdoa_list", k) * LIGHTSPD).astype(np.float32)
+    sr = (_k1(td_sigma_list, "td_sigma_list", k) * LIGHTSPD).astype(np.float32)
+    wr = 1.0 / (sr * sr).astype(np.float64)  # (float32 product, rounded to float32, then the division in double)
+    return _table(s1, s2, r=r.astype(np.float64), wr=wr)
+
+
+def _records_tdfd_direct(s1x_list, s2x_list, tdoa_list, td_sigma_list, s1v_list, s2v_list, fdoa_list, fd_sigma_list, fc):
+    """gridSearchTDFD_direct's roundings: r = float32(tdoa c), sigma_r = float32(sigma_t c), d = float32(fdoa / fc c) and
+    sigma_d = float32(sigma_f / fc c); the weights 1 / sigma^2 are formed in double."""
+    s1 = _k3(s1x_list, "s1x_list")
+    k = s1.shape[0]
+    s2, v1, v2 = _k3(s2x_list, "s2x_list", k), _k3(s1v_list, "s1v_list", k), _k3(s2v_list, "s2v_list", k)
+    fc = float(fc)
+    if not fc > 0:
+        raise ValueError("fc must be positive.")
+    f64 = lambda a: a.astype(np.float32).astype(np.float64)
+    r = f64(_k1(tdoa_list, "tdoa_list", k) * LIGHTSPD)
+    sr = f64(_k1(td_sigma_list, "td_sigma_list", k) * LIGHTSPD)
+    d = f64(_k1(fdoa_list, "fdoa_list", k) / fc * LIGHTSPD)
+    sd = f64(_k1(fd_sigma_list, "fd_sigma_list", k) / fc * LIGHTSPD)
+    return _table(s1, s2, v1, v2, r, 1.0 / (sr * sr), d, 1.0 / (sd * sd))
+
+
+def _f32(a):
+    return np.asarray(a, dtype=np.float64).astype(np.float32).astype(np.float64)
+
+
+def _records_td_flat(s1x_list, s2x_list, tdoa_list, td_sigma_list):
+    """gridSearchTDOA's and gridSearchTDOA_gpu's roundings: sensor positions, tdoa and sigma are each rounded to float32 first;
+    the products with c are formed in double and rounded to float32 once; w = 1 / sigma_r^2 in double."""
+    s1 = _f32(_k3(s1x_list, "s1x_list"))
+    k = s1.shape[0]
+    s2 = _f32(_k3(s2x_list, "s2x_list", k))
+    r = _f32(_f32(_k1(tdoa_list, "tdoa_list", k)) * LIGHTSPD)
+    sr = _f32(_f32(_k1(td_sigma_list, "td_sigma_list", k)) * LIGHTSPD)
+    return _table(s1, s2, r=r, wr=1.0 / (sr * sr))
+
+
+def _records_fd_flat(s1x_list, s2x_list, s1v_list, s2v_list, fdoa_list, fd_sigma_list, fc):
+    """gridSearchFDOA's roundings: positions and velocities are rounded to float32; d = float32(fdoa / fc c) from the double
+    quotient; sigma_f / fc is rounded to float32, multiplied by c in double and rounded once more; w = 1 / sigma_d^2 in double."""
+    s1 = _f32(_k3(s1x_list, "s1x_list"))
+    k = s1.shape[0]
+    s2, v1, v2 = _f32(_k3(s2x_list, "s2x_list", k)), _f32(_k3(s1v_list, "s1v_list", k)), _f32(_k3(s2v_list, "s2v_list", k))
+    fc = float(fc)
+    if not fc > 0:
+        raise ValueError("fc must be positive.")
+    d = _f32(_k1(fdoa_list, "fdoa_list", k) / fc * LIGHTSPD)
+    sd = _f32(_f32(_k1(fd_sigma_list, "fd_sigma_list", k) / fc) * LIGHTSPD)
+    return _table(s1, s2, v1, v2, d=d, wd=1.0 / (sd * sd))
+
+
+# ---- point sources --------------------------------------------------------------------------------------------------------------
+class _Source:
+    """Where the grid points come from: an (N, 3) matrix or the tables of a separable mesh, on the device once uploaded."""
+
+    def __init__(self, kind, n, host, ni=0, nj=0, z=0.0):
+        self.kind, self.n, self.host, self.ni, self.nj, self.z = kind, int(n), host, int(ni), int(nj), float(z)
+        self.dev = None
+
+    @classmethod
+    def points(cls, gridmat):
+        g = np.asarray(gridmat)
+        if g.ndim != 2 or g.shape[1] != 3 or g.shape[0] < 1:
+            raise ValueError("gridmat must be an N x 3 matrix, found shape %s." % (g.shape,))
+        return cls(_lib.CAF_LOCATE_POINTS, g.shape[0], (np.ascontiguousarray(g, dtype=np.float64),))
+
+    @classmethod
+    def mesh(cls, a, z, c, s):
+        """p(i, j) = (a[i] c[j], a[i] s[j], z[i]), flat index i len(c) + j"""
+        a, z, c, s = (np.ascontiguousarray(t, dtype=np.float64).reshape(-1) for t in (a, z, c, s))
+        if a.size < 1 or c.size < 1 or z.size != a.size or s.size != c.size:
+            raise ValueError("mesh tables: a, z of ni >= 1 entries and c, s of nj >= 1 entries.")
+        return cls(_lib.CAF_LOCATE_MESH, a.size * c.size, (a, z, c, s), a.size, c.size)
+
+    @classmethod
+    def xy(cls, x, y, z):
+        """p(i, j) = (x[j], y[i], z), flat index i len(x) + j: np.meshgrid(x, y) flattened"""
+        x, y = (np.ascontiguousarray(t, dtype=np.float64).reshape(-1) for t in (x, y))
+        if x.size < 1 or y.size < 1:
+            raise ValueError("xrange and yrange need at least one entry each.")
+        return cls(_lib.CAF_LOCATE_MESH_XY, x.size * y.size, (y, x), y.size, x.size, z)
+
+    def upload(self):
+        if self.dev is None:
+            self.dev = tuple(asarray(t) for t in self.host)
+        return self.dev
+
+    def matrix(self):
+        """the points as an (N, 3) matrix, with the roundings of the kernel (one product per mesh coordinate)"""
+        if self.kind == _lib.CAF_LOCATE_POINTS:
+            return self.host[0]
+        return self.point(np.arange(self.n))
+
+    def point(self, idx):
+        idx = np.asarray(idx, dtype=np.int64)
+        if self.kind == _lib.CAF_LOCATE_POINTS:
+            return self.host[0][idx]
+        i, j = idx // self.nj, idx % self.nj
+        if self.kind == _lib.CAF_LOCATE_MESH:
+            a, z, c, s = self.host
+            return np.stack((a[i] * c[j], a[i] * s[j], z[i]), axis=-1)
+        y, x = self.host
+        return np.stack((x[j], y[i], np.full(idx.shape, self.z)), axis=-1)
+
+    def desc(self, mode, cost_f32):
+        d = _lib.CafLocateDesc()
+        d.source, d.mode, d.cost_f32, d.n, d.ni, d.nj, d.z = self.kind, mode, int(cost_f32), self.n, self.ni, self.nj, self.z
+        dev = self.upload()
+        if self.kind == _lib.CAF_LOCATE_POINTS:
+            d.d_points = dev[0].ptr
+        elif self.kind == _lib.CAF_LOCATE_MESH:
+            d.d_a, d.d_z, d.d_c, d.d_s = (t.ptr for t in dev)
+        else:
+            d.d_a, d.d_c = dev[0].ptr, dev[1].ptr
+        return d
+
+
+def _check_sets(set_starts, k):
+    if set_starts is None:
+        return None, 1
+    ss = np.ascontiguousarray(set_starts, dtype=np.int64).reshape(-1)
+    if ss.size < 2 or ss[0] != 0 or ss[-1] != k or np.any(np.diff(ss) < 1):
+        raise ValueError("set_starts must rise from 0 to the number of records, at least one record per set.")
+    if ss.size - 1 > 65535:
+        raise ValueError("at most 65535 measurement sets per call.")
+    return ss, ss.size - 1
+
+
+def _search(source, mode, records, set_starts=None, cost=None, argmin=False, stream=None):
+    """One launch of caf_locate_grid.  cost: None, np.float64 or np.float32 -> DeviceArray (B, N) or None;
+    argmin -> DeviceArrays (B,) float64 and (B,) int64 or (None, None).  Returns (d_cost, d_min_val, d_min_idx)."""
+    records = np.ascontiguousarray(records, dtype=np.float64)
+    if records.ndim != 2 or records.shape[1] != _REC or records.shape[0] < 1:
+        raise ValueError("records must be a K x 16 table with K >= 1.")
+    k = records.shape[0]
+    ss, b = _check_sets(set_starts, k)
+    if cost is not None and np.dtype(cost) not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise ValueError("the cost grid is float64 or float32.")
+    _lib.require_device()
+    desc = source.desc(_MODES[mode], cost is not None and np.dtype(cost) == np.dtype(np.float32))
+    d_rec = asarray(records)
+    d_ss = asarray(ss) if ss is not None else None
+    d_cost = empty((b, source.n), np.dtype(cost)) if cost is not None else None
+    d_val = empty((b,), np.float64) if argmin else None
+    d_idx = empty((b,), np.int64) if argmin else None
+    _lib.check(_lib.load().caf_locate_grid(ct.byref(desc), _p(d_rec), k, _p(d_ss), b, _p(d_cost), _p(d_val), _p(d_idx), _st(stream)),
+               "caf_locate_grid")
+    if stream is not None:  # the uploads above go back to the pool on return: on a caller's stream nothing may still read them
+        _lib.check(_lib.load().caf_stream_sync(_st(stream)), "caf_stream_sync")
+    return d_cost, d_val, d_idx
+
+
+def _grid(source, mode, records, dtype, device):
+    d_cost = _search(source, mode, records, cost=dtype)[0].reshape(source.n)
+    return d_cost if device else d_cost.get()
+
+
+# ---- the reference's functions ---------------------------------------------------------------------------------------------------
+def gridSearchTDOA_direct(s1x_list, s2x_list, tdoa_list, td_sigma_list, gridmat, verb=True, device=False):
+    """TDOA cost of every row of gridmat (N x 3), float64.  Measurements are rounded as the reference rounds them
+    (r = float32(tdoa c), weights from the squared float32 sigma); the geometry is float64.  device=True returns a DeviceArray."""
+    rec = _records_td_direct(s1x_list, s2x_list, tdoa_list, td_sigma_list)
+    return _grid(_Source.points(gridmat), "td", rec, np.float64, device)
+
+
+def gridSearchTDFD_direct(s1x_list, s2x_list, tdoa_list, td_sigma_list, s1v_list, s2v_list, fdoa_list, fd_sigma_list, fc, gridmat,
+                          verb=True, device=False):
+    """TDOA + FDOA cost of every row of gridmat (N x 3), float64; r, sigma_r, d = fdoa / fc c and sigma_d are each rounded to
+    float32 as in the reference, the weights formed in double."""
+    rec = _records_tdfd_direct(s1x_list, s2x_list, tdoa_list, td_sigma_list, s1v_list, s2v_list, fdoa_list, fd_sigma_list, fc)
+    return _grid(_Source.points(gridmat), "tdfd", rec, np.float64, device)
+
+
+def _flat_mesh(xrange, yrange, z):
+    return _Source.xy(_f32(xrange), _f32(yrange), float(np.float32(z)))
+
+
+def gridSearchTDOA(s1x_list, s2x_list, tdoa_list, td_sigma_list, xrange, yrange, z, verb=True):
+    """TDOA cost over np.meshgrid(xrange, yrange) at height z (flat surface), returned as float32 like the reference's.  Sensor
+    positions, mesh coordinates, tdoa and sigma are rounded to float32 first, as there; the products with c are formed in double
+    and rounded once; the cost itself is evaluated in float64 and rounded to float32 at the end."""
+    rec = _records_td_flat(s1x_list, s2x_list, tdoa_list, td_sigma_list)
+    return _grid(_flat_mesh(xrange, yrange, z), "td", rec, np.float32, False)
+
+
+def gridSearchFDOA(s1x_list, s2x_list, s1v_list, s2v_list, fdoa_list, fd_sigma_list, xrange, yrange, z, fc, verb=True):
+    """FDOA cost over np.meshgrid(xrange, yrange) at height z, returned as float32; positions, velocities and mesh coordinates are
+    rounded to float32 first and the range-rate differences as the reference rounds them; evaluated in float64."""
+    rec = _records_fd_flat(s1x_list, s2x_list, s1v_list, s2v_list, fdoa_list, fd_sigma_list, fc)
+    return _grid(_flat_mesh(xrange, yrange, z), "fd", rec, np.float32, False)
+
+
+def gridSearchTDOA_gpu(s1x_list, s2x_list, tdoa_list, td_sigma_list, xrange, yrange, z, verb=True, moveToCPU=False):
+    """The reference's CUDA grid search: a float32 DeviceArray of len(xrange) len(yrange) costs (the host array with moveToCPU).
+    The mesh is x0 + col xp, y0 + row yp from the first point and spacing of each range, each value rounded to float32 once;
+    inputs are rounded as in gridSearchTDOA; the cost is evaluated in float64, where the reference's kernel is float32."""
+    xrange, yrange = np.asarray(xrange, dtype=np.float64).reshape(-1), np.asarray(yrange, dtype=np.float64).reshape(-1)
+    if xrange.size < 2 or yrange.size < 2:
+        raise ValueError("xrange and yrange need at least two entries each (the spacing is taken from the first two).")
+    x0, xp = float(np.float32(np.min(xrange))), float(np.float32(xrange[1] - xrange[0]))
+    y0, yp = float(np.float32(np.min(yrange))), float(np.float32(yrange[1] - yrange[0]))
+    rec = _records_td_flat(s1x_list, s2x_list, tdoa_list, td_sigma_list)
+    src = _Source.xy(_f32(x0 + np.arange(xrange.size) * xp), _f32(y0 + np.arange(yrange.size) * yp), float(np.float32(z)))
+    return _grid(src, "td", rec, np.float32, not moveToCPU)
+
+
+def _wgs84_tables(latlist, lonlist, h=0.0):
+    """A = (N + h) cos(lat), Z = (N (1 - e^2) + h) sin(lat), C = cos(lon), S = sin(lon): ECEF = (A C, A S, Z)"""
+    f = 1.0 / WGS84_INV_F
+    e2 = f * (2.0 - f)
+    lat, lon = np.radians(np.asarray(latlist, dtype=np.float64)), np.radians(np.asarray(lonlist, dtype=np.float64))
+    sl = np.sin(lat)
+    n = WGS84_A / np.sqrt(1.0 - e2 * sl * sl)
+    return (n + h) * np.cos(lat), (n * (1.0 - e2) + h) * sl, np.cos(lon), np.sin(lon)
+
+
+def latlongrid_to_ecef(centrelat, centrelon, latspan, lonspan, numLat, numLon):
+    """A latitude / longitude grid round a centre (degrees; the spans are full widths) on the WGS84 ellipsoid, as ECEF points in
+    closed form from the defining constants a and 1 / f.  Returns (ecefgrid (numLat numLon, 3), lonlist, latlist); the point of
+    (latlist[i], lonlist[j]) is row i numLon + j."""
+    lonlist = np.linspace(centrelon - lonspan / 2, centrelon + lonspan / 2, numLon)
+    latlist = np.linspace(centrelat - latspan / 2, centrelat + latspan / 2, numLat)
+    return _Source.mesh(*_wgs84_tables(latlist, lonlist)).matrix(), lonlist, latlist
+
+
+# ---- CRB routines (host NumPy) ----------------------------------------------------------------------------------------------------
+def _column(x):
+    x = np.asarray(x, dtype=np.float64)
+    return x.reshape(-1, 1) if x.ndim == 1 else x
+
+
+def _invert_fim(fim, cmat):
+    if cmat is None:
+        return np.linalg.inv(fim)
+    from scipy.linalg import null_space
+
+    u = null_space(np.asarray(cmat).T)
+    return u @ np.linalg.inv(u.T @ fim @ u) @ u.T
+
+
+def _pairs(pairs, m):
+    return np.arange(m).reshape(-1, 2) if pairs is None else np.asarray(pairs)
+
+
+def calcCRB_TD(x, S, sig_r, pairs=None, cmat=None):
+    """CRB of a position from range differences.  S holds the sensors column-wise (3 x m); pairs (default: (0, 1), (2, 3), ...)
+    names the two sensors of every measurement; cmat holds constraint gradients column-wise.  Returns (crb, FIM)."""
+    x, S = _column(x), np.asarray(S, dtype=np.float64)
+    diff = x - S
+    unit = diff / np.linalg.norm(diff, axis=0)
+    pairs = _pairs(pairs, S.shape[1])
+    R = unit[:, pairs[:, 0]] - unit[:, pairs[:, 1]]
+    fim = R @ np.diag(np.asarray(sig_r, dtype=np.float64) ** -2) @ R.T
+    return _invert_fim(fim, cmat), fim
+
+
+def calcCRB_TDFD(x, S, sig_r, xdot, Sdot, sig_r_dot, pairs=None, cmat=None):
+    """CRB of position and velocity (6 x 6) from range and range-rate differences; S and Sdot column-wise (3 x m)."""
+    x, xdot = _column(x), _column(xdot)
+    S, Sdot = np.asarray(S, dtype=np.float64), np.asarray(Sdot, dtype=np.float64)
+    diff = x - S
+    rng = np.linalg.norm(diff, axis=0)
+    unit = diff / rng
+    rate = np.sum((xdot - Sdot) * diff, axis=0) / rng
+    rate_dx = (-unit * rate + xdot - Sdot) / rng
+    pairs = _pairs(pairs, S.shape[1])
+    c1, c2 = pairs[:, 0], pairs[:, 1]
+    R = np.zeros((6, pairs.shape[0]))
+    Rdot = np.zeros((6, pairs.shape[0]))
+    R[0:3] = unit[:, c1] - unit[:, c2]  # (a range does not depend on the velocity: rows 3..5 stay zero)
+    Rdot[0:3] = rate_dx[:, c1] - rate_dx[:, c2]
+    Rdot[3:6] = unit[:, c1] - unit[:, c2]
+    fim = R @ np.diag(np.asarray(sig_r, dtype=np.float64) ** -2) @ R.T
+    fim = fim + Rdot @ np.diag(np.asarray(sig_r_dot, dtype=np.float64) ** -2) @ Rdot.T
+    return _invert_fim(fim, cmat)
+
+
+def projectCRBtoEllipse(crb, pos, percent, dof=2, theta=None):
+    """The confidence ellipse of a CRB round pos, in the plane of its two largest singular vectors: (3, len(theta)) points."""
+    from scipy.stats.distributions import chi2
+
+    pos = _column(pos)
+    sigval = chi2.ppf(percent, df=dof)
+    u, s, _ = np.linalg.svd(crb)
+    a, b = s[0] ** 0.5, s[1] ** 0.5
+    if theta is None:
+        theta = np.arange(0, 2 * np.pi, 0.01)
+    r = sigval ** 0.5 * a * b / np.sqrt(b ** 2 * np.cos(theta) ** 2 + a ** 2 * np.sin(theta) ** 2)
+    return (r * np.cos(theta)) * u[:, 0].reshape(-1, 1) + (r * np.sin(theta)) * u[:, 1].reshape(-1, 1) + pos
+
+
+# ---- localizers --------------------------------------------------------------------------------------------------------------------
+class GridLocalizer:
+    """Searches a grid of points: gridmat is N x 3 (one point per row), xrange / yrange the axes it was made from."""
+
+    def __init__(self, gridmat, xrange, yrange):
+        self.gridmat = gridmat
+        self.xrange = xrange
+        self.yrange = yrange
+        self._src = None
+        self._src_of = None
+
+    @classmethod
+    def fromXYMeshgrid(cls, xrange, yrange):
+        """As the reference: the matrix holds the two mesh coordinates only, so a search needs a third column added first."""
+        xm, ym = np.meshgrid(xrange, yrange)
+        return cls(np.hstack((xm.reshape((-1, 1)), ym.reshape((-1, 1)))), xrange, yrange)
+
+    def _source(self):
+        """the point source of this localizer; an explicit gridmat is uploaded once and kept"""
+        if self._src is None or self._src_of is not self.gridmat:
+            self._src = _Source.points(self.gridmat)
+            self._src_of = self.gridmat
+        return self._src
+
+    def run(self):
+        raise NotImplementedError("This method is only defined in subclasses.")
+
+    def locate(self):
+        raise NotImplementedError("This method is only defined in subclasses.")
+
+    def localize(self, cost_grid):
+        return self.gridmat[int(np.argmin(_host(cost_grid)))]
+
+    def crb(self):
+        raise NotImplementedError("This method is only defined in subclasses.")
+
+    def _locate(self, mode, record_sets):
+        """record_sets: a list of K_b x 16 tables.  One launch, no cost grid: (index, cost, point) per set."""
+        starts = np.concatenate(([0], np.cumsum([r.shape[0] for r in record_sets])))
+        src = self._source()
+        _, d_val, d_idx = _search(src, mode, np.concatenate(record_sets), set_starts=starts if len(record_sets) > 1 else None, argmin=True)
+        idx, val = d_idx.get(), d_val.get()
+        pts = np.full((idx.size, 3), np.nan)
+        ok = idx >= 0
+        pts[ok] = src.point(idx[ok])
+        return idx, val, pts
+
+
+def _host(cost_grid):
+    return cost_grid.get() if isinstance(cost_grid, DeviceArray) else np.asarray(cost_grid)
+
+
+class LatLonGridLocalizer(GridLocalizer):
+    """A localizer over a latitude / longitude grid; the search itself runs in Cartesian (ECEF) space."""
+
+    def __init__(self, latlist, lonlist, gridmat):
+        super().__init__(gridmat, lonlist, latlist)
+        self.lonlist = lonlist
+        self.latlist = latlist
+        self._tables = None
+
+    @classmethod
+    def fromLatLonLimits(cls, centrelat, centrelon, latspan, lonspan, numLat, numLon):
+        """Keeps the four WGS84 tables of the grid: searches then use the mesh source and never read the N x 3 matrix."""
+        ecefgrid, lonlist, latlist = latlongrid_to_ecef(centrelat, centrelon, latspan, lonspan, numLat, numLon)
+        self = cls(latlist, lonlist, ecefgrid)
+        self._tables = _wgs84_tables(latlist, lonlist)
+        self._tables_of = ecefgrid
+        return self
+
+    def _source(self):
+        if self._tables is not None and self._tables_of is self.gridmat:
+            if self._src is None or self._src_of is not self.gridmat:
+                self._src = _Source.mesh(*self._tables)
+                self._src_of = self.gridmat
+            return self._src
+        return super()._source()
+
+    def localize(self, cost_grid):
+        """(longitude, latitude, point) of the smallest cost.  The mesh is laid out latitude-major, so the flat index is divided by
+        the number of LONGITUDES (the reference divides by the number of latitudes, which is the same only on square grids)."""
+        idx = int(np.argmin(_host(cost_grid)))
+        nlon = np.asarray(self.lonlist).size
+        return self.lonlist[idx % nlon], self.latlist[idx // nlon], self.gridmat[idx]
+
+
+def _is_batch(s1x_list):
+    """one set: a K x 3 matrix; B sets: a sequence of K_b x 3 matrices (or a B x K x 3 array)"""
+    return not (hasattr(s1x_list, "ndim") and s1x_list.ndim == 2) and np.ndim(s1x_list[0]) == 2
+
+
+def _per_set(args, batch, scalars=()):
+    """the arguments of run() as one tuple per measurement set; the arguments named in `scalars` may be given once for all sets"""
+    if not batch:
+        return [tuple(args)]
+    b = len(args[0])
+    cols = []
+    for n, a in enumerate(args):
+        if n in scalars and np.ndim(a) == 0:
+            a = [a] * b
+        if len(a) != b:
+            raise ValueError("every argument must hold one entry per measurement set (%d)." % b)
+        cols.append(a)
+    return list(zip(*cols))
+
+
+def _unbatch(out, batch):
+    idx, val, pts = out
+    return (idx, val, pts) if batch else (int(idx[0]), float(val[0]), pts[0])
+
+
+class TDMixin:
+    def run(self, s1x_list, s2x_list, tdoa_list, td_sigma_list, device=False):
+        """TDOA weighted least-squares cost of every grid point (length N, float64); TDOA = (time to sensor 2) - (time to sensor
+        1).  s1x_list, s2x_list: K x 3 (m); tdoa_list, td_sigma_list: length K (s).  Rounded as gridSearchTDOA_direct rounds.
+        device=True leaves the grid on the device (a DeviceArray)."""
+        rec = _records_td_direct(s1x_list, s2x_list, tdoa_list, td_sigma_list)
+        if np.ndim(self.gridmat) != 2 or np.shape(self.gridmat)[1] != 3:
+            raise ValueError("Ensure gridmat has 3 columns.")
+        return _grid(self._source(), "td", rec, np.float64, device)
+
+    def locate(self, s1x_list, s2x_list, tdoa_list, td_sigma_list):
+        """The arg min of run() without its grid: (index, cost, point).  With a sequence of B measurement sets in every argument
+        (K_b x 3 matrices and length K_b arrays, the K_b need not agree) all B are searched in one launch: (B,), (B,), (B, 3).
+        The first index wins a tie; NaN costs never win; nothing but NaN gives (-1, NaN, NaN point)."""
+        batch = _is_batch(s1x_list)
+        recs = [_records_td_direct(*a) for a in _per_set((s1x_list, s2x_list, tdoa_list, td_sigma_list), batch)]
+        if np.ndim(self.gridmat) != 2 or np.shape(self.gridmat)[1] != 3:
+            raise ValueError("Ensure gridmat has 3 columns.")
+        return _unbatch(self._locate("td", recs), batch)
+
+    def crb(self, gridmin, s1x_list, s2x_list, td_sigma_list):
+        """CRB (3 x 3) of a TDOA fix at gridmin under a known-altitude (vector length) constraint, the TD counterpart of
+        TDFDMixin.crb (the reference defines none for TD)."""
+        s1, s2 = _k3(s1x_list, "s1x_list"), _k3(s2x_list, "s2x_list")
+        S = np.zeros((2 * s1.shape[0], 3))
+        S[0::2], S[1::2] = s2, s1
+        gridmin = np.asarray(gridmin, dtype=np.float64)
+        return calcCRB_TD(gridmin, S.T, np.asarray(td_sigma_list) * LIGHTSPD, cmat=gridmin.reshape(3, 1))[0]
+
+
+class TDFDMixin:
+    def run(self, s1x_list, s2x_list, tdoa_list, td_sigma_list, s1v_list, s2v_list, fdoa_list, fd_sigma_list, fc, device=False):
+        """TDOA + FDOA weighted least-squares cost of every grid point (length N, float64); both differences are (sensor 2) -
+        (sensor 1).  Positions K x 3 (m), velocities K x 3 (m/s), tdoa / td_sigma (s), fdoa / fd_sigma (Hz), fc the centre
+        frequency that normalises the FDOAs.  Rounded as gridSearchTDFD_direct rounds.  device=True returns a DeviceArray."""
+        rec = _records_tdfd_direct(s1x_list, s2x_list, tdoa_list, td_sigma_list, s1v_list, s2v_list, fdoa_list, fd_sigma_list, fc)
+        if np.ndim(self.gridmat) != 2 or np.shape(self.gridmat)[1] != 3:
+            raise ValueError("Ensure gridmat has 3 columns.")
+        return _grid(self._source(), "tdfd", rec, np.float64, device)
+
+    def locate(self, s1x_list, s2x_list, tdoa_list, td_sigma_list, s1v_list, s2v_list, fdoa_list, fd_sigma_list, fc):
+        """The arg min of run() without its grid: (index, cost, point); B measurement sets at once as in TDMixin.locate (fc may
+        be one value for all sets)."""
+        batch = _is_batch(s1x_list)
+        args = (s1x_list, s2x_list, tdoa_list, td_sigma_list, s1v_list, s2v_list, fdoa_list, fd_sigma_list, fc)
+        recs = [_records_tdfd_direct(*a) for a in _per_set(args, batch, scalars=(8,))]
+        if np.ndim(self.gridmat) != 2 or np.shape(self.gridmat)[1] != 3:
+            raise ValueError("Ensure gridmat has 3 columns.")
+        return _unbatch(self._locate("tdfd", recs), batch)
+
+    def crb(self, gridmin, s1x_list, s2x_list, s1v_list, s2v_list, td_sigma_list, fd_sigma_list, fc):
+        """CRB (6 x 6) of a TD + FD fix at gridmin for a stationary target, under a known-altitude (vector length) constraint
+        and zero-velocity constraints."""
+        s1, s2 = np.asarray(s1x_list, dtype=np.float64), np.asarray(s2x_list, dtype=np.float64)
+        S = np.zeros((2 * s1.shape[0], 3))
+        S[0::2], S[1::2] = s2, s1  # (sensor 2 first: the differences are 2 - 1)
+        Sdot = np.zeros_like(S)
+        Sdot[0::2], Sdot[1::2] = s2v_list, s1v_list
+        cmat = np.zeros((6, 4))
+        cmat[0:3, 0] = gridmin
+        cmat[3:6, 1:4] = np.eye(3)
+        return calcCRB_TDFD(gridmin, S.T, np.asarray(td_sigma_list) * LIGHTSPD, np.zeros(3), Sdot.T,
+                            np.asarray(fd_sigma_list) / fc * LIGHTSPD, cmat=cmat)
+
+
+class LatLonGridLocalizerTD(TDMixin, LatLonGridLocalizer):
+    pass
+
+
+class LatLonGridLocalizerTDFD(TDFDMixin, LatLonGridLocalizer):
+    pass
