@@ -584,6 +584,44 @@ CAF_EXPORT int32_t caf_locate_grid(const caf_locate_desc* desc, const double* d_
 /* the launch geometry: points per workgroup and records per staged chunk (the sizes at which the kernel changes path) */
 CAF_EXPORT int32_t caf_locate_geometry(int32_t* points_per_workgroup, int32_t* records_per_chunk);
 
+/* ---- Viterbi sequence detection (viterbiDemodClasses.py: ViterbiDemodulator, BurstyViterbiDemodulator).  Added after ABI 1.10
+ * without a version bump, detected by symbol.  Everything is float64.  With A states, T pretransitions per state, L sources:
+ *   P_n[m] = sum_i exp(-j omegas[i] (n up + m)) pulses[i][m], m < pulselen, and the signal of a symbol sequence g is
+ *   x[w] = sum_k g[k] P_k[w - k up].  Step n of state p over its pretransitions q: long = |y - x|^2 over [n up, n up + pulselen)
+ *   with the survivor of q followed by alphabet[p], short = the same over the first up samples; the FIRST minimum of the long
+ *   metric alone wins, and the path metric grows by the winner's short metric.  (csrc/caf_viterbi.hip has the whole rule.) */
+/* d_table (pathlen, pulselen) complex128 = P_n[m] from d_pulses (L, pulselen) complex128 and d_omegas (L) float64 */
+CAF_EXPORT int32_t caf_viterbi_table(const double* d_pulses, const double* d_omegas, int32_t L, int32_t pulselen, int32_t up,
+                                     int32_t pathlen, double* d_table, void* stream);
+typedef struct {
+    int32_t num_states;             /* A, 1..8                                                                          */
+    int32_t num_trans;              /* T, 1..A                                                                          */
+    int32_t up;                     /* samples per symbol, >= 1                                                         */
+    int32_t pulselen;               /* up..512                                                                          */
+    int32_t pathlen;                /* symbols per row, >= 1                                                            */
+    int32_t num_burst_syms;         /* 0 (with num_guard_syms = 0): no burst period, the plain class                    */
+    int32_t num_guard_syms;         /* a new-burst step every num_burst_syms + num_guard_syms symbols                   */
+    int32_t y_c128;                 /* 1: d_y is complex128, 0: complex64                                               */
+    const double* h_alphabet;       /* HOST: A complex128 values                                                        */
+    const int32_t* h_pretransitions;/* HOST: (A, T), every entry in [0, A)                                              */
+    const int32_t* h_allowed;       /* HOST: the states that may start (a burst), num_allowed of them in [0, A)         */
+    int32_t num_allowed;
+    int32_t reserved;
+    const double* d_table;          /* caf_viterbi_table of the same pulselen and up, at least pathlen rows             */
+    const void* d_y;                /* (rows, ylength), ylength >= (pathlen - 1) up + pulselen                          */
+    int64_t rows, ylength;
+    uint8_t* d_states;              /* outputs, each optional: (rows, A, pathlen) state per slot, 255 = never written   */
+    double* d_metrics;              /* (rows, A) path metrics, +inf for a state without a survivor                      */
+    int32_t* d_best;                /* (rows) the first arg min of the path metrics                                     */
+    uint8_t* d_best_path;           /* (rows, pathlen) = d_states[row][best]                                            */
+} caf_viterbi_desc;
+/* Every row of either class in one launch; rows are independent and a row's outputs do not depend on the batch.  What is not
+ * supported (more than 8 states, pulselen > 512, a short row, a pretransition outside [0, A)) is refused with CAF_ERR_INVALID
+ * before anything is launched; there is no other path. */
+CAF_EXPORT int32_t caf_viterbi_demod(const caf_viterbi_desc* desc, void* stream);
+/* the limits and the traceback chunk (the size at which the kernel changes path) */
+CAF_EXPORT int32_t caf_viterbi_geometry(int32_t* max_states, int32_t* max_pulselen, int32_t* decision_chunk);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,6 +159,32 @@ class CafLocateDesc(ct.Structure):
     ]
 
 
+class CafViterbiDesc(ct.Structure):
+    _fields_ = [
+        ("num_states", ct.c_int32),
+        ("num_trans", ct.c_int32),
+        ("up", ct.c_int32),
+        ("pulselen", ct.c_int32),
+        ("pathlen", ct.c_int32),
+        ("num_burst_syms", ct.c_int32),
+        ("num_guard_syms", ct.c_int32),
+        ("y_c128", ct.c_int32),
+        ("h_alphabet", ct.c_void_p),
+        ("h_pretransitions", ct.c_void_p),
+        ("h_allowed", ct.c_void_p),
+        ("num_allowed", ct.c_int32),
+        ("reserved", ct.c_int32),
+        ("d_table", ct.c_void_p),
+        ("d_y", ct.c_void_p),
+        ("rows", ct.c_int64),
+        ("ylength", ct.c_int64),
+        ("d_states", ct.c_void_p),
+        ("d_metrics", ct.c_void_p),
+        ("d_best", ct.c_void_p),
+        ("d_best_path", ct.c_void_p),
+    ]
+
+
 CAF_LOCATE_POINTS = 0
 CAF_LOCATE_MESH = 1
 CAF_LOCATE_MESH_XY = 2
@@ -262,6 +288,9 @@ _SIGNATURES = {
     "caf_cp2fsk_bursty_demod": [_P, _I64, _I64, _I32, ct.c_double, _I32, _P, _I32, _I64, _I64, _P, _P, _P, _P],
     "caf_locate_grid": [ct.POINTER(CafLocateDesc), _P, _I64, _P, _I32, _P, _P, _P, _P],
     "caf_locate_geometry": [ct.POINTER(_I32), ct.POINTER(_I32)],
+    "caf_viterbi_table": [_P, _P, _I32, _I32, _I32, _I32, _P, _P],
+    "caf_viterbi_demod": [ct.POINTER(CafViterbiDesc), _P],
+    "caf_viterbi_geometry": [ct.POINTER(_I32), ct.POINTER(_I32), ct.POINTER(_I32)],
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
