@@ -18,6 +18,15 @@ Seeds 0 .. 9 of every float64 case below on one MI355X (the two HDR records then
     per-delay     k_perdelay_fused 0.325, k_perdelay_r10 0.461, k_perdelay_mr 0.381, JIT single image 0.167,
                   JIT split form 0.213, Bluestein 0.212                                         -> C_PD = 2
 
+The forms of tests/test_gpu_f64_modes.py (no frequency scan; no-surface items of production size), same seeds, same device:
+
+    F = 1         persistent 16384-point role (f1_direct: rows and peak records from the FFT items, up to 64 templates per
+                  item, TemplateCrossCorrelator) 0.318, fused 0.308, rocfft 0.308, chained 32768 0.124, folded 65536 0.163,
+                  partitioned 65536 0.146                                                       -> C_OS = 2 stands
+                  direct 0.907                                                                  -> C_DIRECT = 8 stands
+    no surface    items of 64 hypotheses 0.142, of 51/51/51/48 0.178, one item of 256 0.151, the call's own widening
+                  to 2 x 125 (windowed reference) 0.143                                         -> C_OS = 2 stands
+
 Each constant is the smallest power of two at least 4x above the worst ratio of its family.
 
 Second, power-of-two scale equivariance: rx * 2^k and the template * 2^j change no rounding anywhere (products, FFTs and
@@ -34,7 +43,7 @@ from ref64 import amp_bound, amp_ratio, caf64, complex_ratio, perdelay64
 
 pytestmark = pytest.mark.gpu
 
-C_OS = 2.0      # overlap-save engines and roles (worst calibrated ratio 0.258)
+C_OS = 2.0      # overlap-save engines and roles (worst calibrated ratio 0.318: F = 1 on the 16384-point role)
 C_DIRECT = 8.0  # the direct engine (worst calibrated ratio 1.155)
 C_PD = 2.0      # per-delay kernels (worst calibrated ratio 0.461)
 
@@ -62,7 +71,10 @@ def _record(path, r, c):
 # ------------------------------------------------------------------------------------------------------------------------------
 # the overlap-save engines
 
-def _caf_case(seed, n, T, m, freqs=None, bins=None, grid=None, groups=False, hdr=False, zeros=False, sub=False):
+def _caf_case(seed, n, T, m, freqs=None, bins=None, grid=None, groups=False, hdr=False, zeros=False, sub=False, one_each=False, scaled=False):
+    """scaled: template i times 0.5 + (i mod 7) / 4, its planted copies divided by it (a different 1 / ||t||^2 per template).
+    one_each: ONE strong copy per template (any T; the three amplitudes per template below need 3 T of 64 slots) at delays
+    drawn from the whole record -- template 0 at the first delay, the last template at the last one."""
     rng = np.random.default_rng(seed + 1000 * SEED)
     tm = np.stack([qpsk(rng, n) for _ in range(T)])
     gs = gl = None
@@ -76,6 +88,8 @@ def _caf_case(seed, n, T, m, freqs=None, bins=None, grid=None, groups=False, hdr
         tm = (tm * mask).astype(np.complex64)
     nu = np.asarray(freqs, np.float64) if freqs is not None else np.asarray(bins) / grid
     F = nu.size
+    scale = 0.5 + 0.25 * (np.arange(T) % 7) if scaled else np.ones(T)
+    tm = (tm * scale[:, None]).astype(np.complex64)
     rx = cn(rng, m)
     S = m - n + 1
     if hdr:  # a stretch of 3000 samples 60 dB louder, beyond the windows of the planted copies
@@ -85,14 +99,20 @@ def _caf_case(seed, n, T, m, freqs=None, bins=None, grid=None, groups=False, hdr
         z = int(rng.integers(S // 2, 3 * S // 4))
         rx[z : z + n + 40] = 0
     # planted copies at several amplitudes, one strong one per template (the peak)
-    slots = rng.choice(np.arange(0, S // 2, max(1, S // 128))[:64], 3 * T, replace=False)
+    if one_each:
+        free = np.arange(1, S - 1)
+        if zeros:
+            free = free[(free < z - n) | (free >= z + n + 40)]
+        slots = np.concatenate(([0], rng.choice(free, T - 2, replace=False), [S - 1]))
+    else:
+        slots = rng.choice(np.arange(0, S // 2, max(1, S // 128))[:64], 3 * T, replace=False)
     for i in range(T):
-        for k, amp in enumerate((3.0, 0.5, 0.1)):
-            d = int(slots[3 * i + k])
+        for k, amp in enumerate((3.0,) if one_each else (3.0, 0.5, 0.1)):
+            d = int(slots[i] if one_each else slots[3 * i + k])
             if zeros and z - n <= d < z + n + 40:
                 continue
             f = int(rng.integers(0, F))
-            rx[d : d + n] += (amp * tm[i] * np.exp(2j * np.pi * nu[f] * np.arange(n))).astype(np.complex64)
+            rx[d : d + n] += (amp / scale[i] * tm[i] * np.exp(2j * np.pi * nu[f] * np.arange(n))).astype(np.complex64)
     lo, cnt = 0, S
     if sub:
         lo = int(rng.integers(1, S // 4))
@@ -103,15 +123,17 @@ def _caf_case(seed, n, T, m, freqs=None, bins=None, grid=None, groups=False, hdr
     return dict(n=n, tm=tm, rx=rx, nu=nu, kw=kw, gs=gs, gl=gl, lo=lo, cnt=cnt)
 
 
-def _run_caf(plan, rx, lo, cnt, cqf, surface_t):
+def _run_caf(plan, rx, lo, cnt, cqf, surface_t, surface=True):
     from pydsproutines_amd import asarray
 
     d_rx = asarray(rx)
     g = lambda r, names: {k: getattr(r, k).get() for k in names}  # noqa: E731
     rows = ("row_max", "row_arg", "peak_val", "peak_delay", "peak_freq")
-    out = {"surface": g(plan.run(d_rx, shift_start=lo, num_shifts=cnt, surface=True), ("surface",) + rows),
-           "rows": g(plan.run(d_rx, shift_start=lo, num_shifts=cnt, surface=False, rows=True, peak=True), rows),
-           "peak": g(plan.run(d_rx, shift_start=lo, num_shifts=cnt, surface=False, rows=False, peak=True), rows[2:])}
+    out = {}
+    if surface:  # (off: the no-surface forms alone)
+        out["surface"] = g(plan.run(d_rx, shift_start=lo, num_shifts=cnt, surface=True), ("surface",) + rows)
+    out["rows"] = g(plan.run(d_rx, shift_start=lo, num_shifts=cnt, surface=False, rows=True, peak=True), rows)
+    out["peak"] = g(plan.run(d_rx, shift_start=lo, num_shifts=cnt, surface=False, rows=False, peak=True), rows[2:])
     if surface_t:
         out["surface_t"] = g(plan.run(d_rx, shift_start=lo, num_shifts=cnt, surface_t=True), ("surface_t",) + rows)
     if cqf:
@@ -119,11 +141,12 @@ def _run_caf(plan, rx, lo, cnt, cqf, surface_t):
     return out
 
 
-def _check_caf(path, out, lo, ref, refz, bound, c):
-    """Every output against the float64 surface ref (T, S, F); bound (S,) is the unit of the error bound (times c)."""
+def _ref_conditions(path, ref, bound, c, peaks=True):
+    """What the float64 surface itself must satisfy for the checks below to mean something (no GPU: tests/test_ref64.py runs
+    this on every case of tests/test_gpu_f64_modes.py): at least 95 % of the live rows clear of their runner-up by 2 c bound,
+    and every template's peak clear of the second value of its surface.  Returns (rmax, live, clear, ref_arg, flat, pk)."""
     bnd = c * bound
     amp = np.sqrt(ref)
-    worst = 0.0
     T, S, F = ref.shape
     with np.errstate(invalid="ignore"):
         rmax = np.nanmax(np.where(np.isnan(ref), -1.0, ref), axis=2)
@@ -141,6 +164,20 @@ def _check_caf(path, out, lo, ref, refz, bound, c):
     ref_arg = np.argmax(np.where(np.isnan(ref), -1.0, ref), axis=2)
     flat = np.where(np.isnan(ref), -1.0, ref).reshape(T, -1)
     pk = np.argmax(flat, axis=1)
+    if peaks:
+        for t in range(T):
+            # the peak must be clear of the runner-up on the surface, or the test's planting is wrong
+            second = np.partition(flat[t], -2)[-2]
+            assert np.sqrt(flat[t, pk[t]]) - np.sqrt(max(second, 0.0)) > 2 * bnd[pk[t] // F], "%s: planted peak not clear" % path
+    return rmax, live, clear, ref_arg, flat, pk
+
+
+def _check_caf(path, out, lo, ref, refz, bound, c, peaks=True):
+    """Every output against the float64 surface ref (T, S, F); bound (S,) is the unit of the error bound (times c).
+    peaks=False: ref covers a window of the delays only, and `out` holds no peak triple."""
+    worst = 0.0
+    T, S, F = ref.shape
+    rmax, live, clear, ref_arg, flat, pk = _ref_conditions(path, ref, bound, c, peaks)
     pk_d, pk_f = pk // F, pk % F
     for mode, o in out.items():
         if "surface" in o:
@@ -154,10 +191,7 @@ def _check_caf(path, out, lo, ref, refz, bound, c):
             np.testing.assert_array_equal(o["row_arg"][clear], ref_arg[clear], err_msg="%s %s: row_arg" % (path, mode))
             assert np.all(o["row_arg"][~live] == 0)
         if "peak_val" in o:
-            for t in range(T):
-                # the peak must be clear of the runner-up on the surface, or the test's planting is wrong
-                second = np.sort(np.sqrt(np.maximum(flat[t], 0.0)))[-2]
-                assert np.sqrt(flat[t, pk[t]]) - second > 2 * bnd[pk_d[t]], "%s: planted peak not clear" % path
+            assert peaks
             np.testing.assert_array_equal(o["peak_delay"], pk_d + lo, err_msg="%s %s: peak delay" % (path, mode))
             np.testing.assert_array_equal(o["peak_freq"], pk_f, err_msg="%s %s: peak frequency" % (path, mode))
             r = np.abs(np.sqrt(o["peak_val"].astype(np.float64)) - np.sqrt(flat[np.arange(T), pk])) / bound[pk_d]
@@ -171,11 +205,13 @@ def _parts(plan, n):
     return 32768 if (plan.engine_used == "persistent" and plan.block == 65536 and n > 32768) else None
 
 
-def _caf_path(c, engine, path, lb=0, cqf=False, surface_t=False, nb=0):
+def _caf_path(c, engine, path, lb=0, cqf=False, surface_t=False, nb=0, max_rx_len=None, surface=True, probe=None):
+    """max_rx_len: the record the plan is made for (the item size is fixed at plan build from it; the call runs c["rx"]).
+    probe(plan): called after the runs, while the plan lives (which form ran: tests/test_gpu_f64_modes.py)."""
     from pydsproutines_amd import CAFPlan
 
     n, m = c["n"], c["rx"].size
-    plan = CAFPlan(c["tm"], max_rx_len=m, engine=engine, log2_block=lb, blocks_per_batch=nb, **c["kw"])
+    plan = CAFPlan(c["tm"], max_rx_len=max_rx_len or m, engine=engine, log2_block=lb, blocks_per_batch=nb, **c["kw"])
     try:
         assert plan.engine_used == engine
         shifts = c["lo"] + np.arange(c["cnt"])
@@ -183,7 +219,9 @@ def _caf_path(c, engine, path, lb=0, cqf=False, surface_t=False, nb=0):
             bound = amp_bound(c["rx"], n, shifts, 64, None, c["gs"], c["gl"], transform_energy=False)
         else:
             bound = amp_bound(c["rx"], n, shifts, plan.block, _parts(plan, n), c["gs"], c["gl"])
-        out = _run_caf(plan, c["rx"], c["lo"], c["cnt"], cqf, surface_t)
+        out = _run_caf(plan, c["rx"], c["lo"], c["cnt"], cqf, surface_t, surface)
+        if probe is not None:
+            probe(plan)
     finally:
         plan.close()
     return out, bound, plan.block
@@ -239,6 +277,45 @@ CASES_LONG = {
 CASES_DIRECT = {
     "n64_direct": dict(seed=21, n=64, T=2, m=20000, bins=np.arange(-32, 32), grid=64),
     "n500_3x16_direct": dict(seed=22, n=500, T=2, m=20000, freqs=_F37),
+}
+
+
+def os_step(n, B=16384):
+    """New delays per overlap-save block of the in-LDS engines (build_block, csrc/caf_plan.hip)."""
+    if B == 65536:
+        return 32768
+    s = B - n + 1
+    return s - s % 64 if s % 64 and (s % 64) * 300 <= s else s
+
+
+def _m(n, blocks, extra, B=16384):
+    """Record length that gives `blocks` whole blocks of delays and a ragged one of `extra`."""
+    return blocks * os_step(n, B) + extra + n - 1
+
+
+# No frequency scan (F = 1; tests/test_gpu_f64_modes.py).  The 16384-point role: n = 1000, 4098 and 8192 are the three
+# instantiations of the FFT item (4, 3 and 2 output quarters hold valid delays); one explicit frequency (table mode), one bin
+# off zero (circular-shift mode), bin 0.  T = 5: items of 4 + 1 templates.
+CASES_F1 = {
+    "n1000_t5_table": dict(seed=31, n=1000, T=5, m=_m(1000, 3, 1001), freqs=[0.013], zeros=True, sub=True, scaled=True),
+    "n4098_groups_shift": dict(seed=32, n=4098, T=2, m=_m(4098, 3, 1001), bins=[3], grid=8192, groups=True, sub=True),
+    "n8192_hdr": dict(seed=33, n=8192, T=3, m=_m(8192, 9, 1001), bins=[0], grid=8192, hdr=True),
+}
+# 130 templates, one strong copy each, on a plan made for a long record (items of more than 16 templates)
+CASE_F1_MANY = dict(seed=34, n=1000, T=130, m=_m(1000, 3, 1001), bins=[0], grid=1024, zeros=True, one_each=True, scaled=True)
+CASE_F1_TCC = dict(seed=39, n=1000, T=7, m=_m(1000, 3, 1001), bins=[0], grid=1024, scaled=True)  # (TemplateCrossCorrelator)
+CASE_F1_DIRECT = dict(seed=35, n=64, T=2, m=20000, bins=[1], grid=64, zeros=True, sub=True)
+# the chained, folded (an odd number of valid delays in the last block) and partitioned roles
+CASES_F1_LONG = {
+    "n14018_chained_f1": dict(seed=36, n=14018, T=3, m=14018 + 40000, bins=[2], grid=16384, sub=True),
+    "n20000_folded_f1": dict(seed=37, n=20000, T=3, m=_m(20000, 1, 4321, 65536), freqs=[0.013], zeros=True),
+    "n40000_parts2_f1": dict(seed=38, n=40000, T=2, m=_m(40000, 1, 7233, 65536), bins=[-1], grid=16384),
+}
+# No-surface items of production size (tests/test_gpu_f64_modes.py): 3 blocks + a ragged one of 1001 delays
+CASES_NOSURF = {
+    "f128_items_of_64": dict(seed=41, n=1000, T=2, m=_m(1000, 3, 1001), bins=np.arange(-64, 64), grid=1024, zeros=True, sub=True),
+    "f201_uneven_51_48": dict(seed=42, n=4098, T=2, m=_m(4098, 3, 1001), bins=np.arange(-100, 101), grid=8192, sub=True),
+    "f256_one_item": dict(seed=43, n=1000, T=1, m=_m(1000, 3, 1001), bins=np.arange(-128, 128), grid=1024),
 }
 
 
@@ -332,6 +409,10 @@ _EQ_CAF = [
     ("folded65536", CASES_LONG["n32768_folded"], "persistent", {}),
     ("partitioned65536", dict(CASES_LONG["n40000_parts2_explicit_hdr"], hdr=False), "persistent", dict(cqf=True)),
     ("direct", CASES_DIRECT["n500_3x16_direct"], "direct", {}),
+    # no frequency scan: the FFT items write the finished rows and the peak records (16384), transpose_wave_f1<1> and <2>
+    ("persistent16_f1", CASES_F1["n1000_t5_table"], "persistent", dict(cqf=True, surface_t=True)),
+    ("chained32768_f1", CASES_F1_LONG["n14018_chained_f1"], "persistent", dict(cqf=True)),
+    ("folded65536_f1", CASES_F1_LONG["n20000_folded_f1"], "persistent", {}),
 ]
 
 

@@ -132,6 +132,73 @@ def test_amp_bound_widens_with_the_transform_span():
     assert np.all(bp > 2.0 ** -24 * 16 * np.sqrt(3 * 65536 / n2 * 0.8))
 
 
+def _modes_cases():
+    """(name, case arguments or case, block, partition length, constant) of every float64 case of tests/test_gpu_f64_modes.py."""
+    import test_gpu_f64_reference as G
+
+    out = [(k, v, 16384, None, G.C_OS) for k, v in G.CASES_F1.items()]
+    out += [("f1_many", G.CASE_F1_MANY, 16384, None, G.C_OS), ("f1_tcc", G.CASE_F1_TCC, 16384, None, G.C_OS),
+            ("f1_direct", G.CASE_F1_DIRECT, 64, None, G.C_DIRECT)]
+    for k, v in G.CASES_F1_LONG.items():
+        out.append((k, v, 32768 if v["n"] <= 16384 else 65536, 32768 if v["n"] > 32768 else None, G.C_OS))
+    out += [(k, k, 16384, None, G.C_OS) for k in G.CASES_NOSURF]
+    return out
+
+
+@pytest.mark.parametrize("name,args,B,part,c", _modes_cases(), ids=[m[0] for m in _modes_cases()])
+def test_modes_cases_satisfy_the_conditions_of_their_checks(name, args, B, part, c):
+    """The float64 reference of each case of tests/test_gpu_f64_modes.py alone: at least 95 % of the live rows clear of their
+    runner-up by 2 c bound and every planted peak clear (what _check_caf asserts before it looks at a GPU value), the
+    zero-energy windows and the sub-range inside a tile where the case is meant to have them, the winners of the one item
+    of 256 hypotheses where they were planted."""
+    import test_gpu_f64_modes as M
+    import test_gpu_f64_reference as G
+
+    case = M._nosurf_case(args) if isinstance(args, str) else G._caf_case(**args)
+    spec = G.CASES_NOSURF[args] if isinstance(args, str) else args
+    shifts = case["lo"] + np.arange(case["cnt"])
+    ref = caf64(case["tm"], case["rx"], case["nu"], shifts, case["gs"], case["gl"])
+    bound = amp_bound(case["rx"], case["n"], shifts, B, part, case["gs"], case["gl"], transform_energy=B != 64)
+    rmax, live, clear, ref_arg, flat, pk = G._ref_conditions(name, ref, bound, c)
+    if spec.get("zeros"):
+        assert (~live).any() and (~live).sum() < 0.01 * live.size
+    if spec.get("sub"):
+        step = G.os_step(case["n"], B) if B != 64 else 64
+        assert case["lo"] % 64 and (case["cnt"] % step) % 64
+    if spec.get("one_each"):
+        assert len(set(pk.tolist())) == case["tm"].shape[0] and 0 in pk and case["cnt"] - 1 in pk
+    for d, j in case.get("win", []):
+        assert clear[0, d] and ref_arg[0, d] == j
+
+
+def test_modes_windowed_and_tied_references():
+    """The windows of the widened case (176 blocks, as on 256 CUs): each at least 2000 delays across a block boundary, the last
+    one over the ragged last block, every planted copy inside one and the maximum of its window; 95 % of the rows clear.  The
+    tied table: the float64 columns of a pair agree to rounding and hold the planted peaks."""
+    import test_gpu_f64_modes as M
+    import test_gpu_f64_reference as G
+
+    w = M.widening_case(176)
+    step, S = w["step"], w["S"]
+    for lo, cnt in w["wins"]:
+        assert cnt >= 2000 and lo // step != (lo + cnt - 1) // step
+    assert w["wins"][-1][0] + w["wins"][-1][1] == S and S % step
+    for k, (lo, ref, bound) in enumerate(M.widening_refs(w)):
+        G._ref_conditions("window %d" % k, ref, bound, G.C_OS, peaks=False)
+        for i, (d, j) in w["truth"].items():
+            if lo <= d < lo + ref.shape[1]:
+                t = w["sel"].index(i)
+                assert np.unravel_index(np.argmax(ref[t]), ref[t].shape) == (d - lo, j)
+    assert all(any(lo <= d < lo + cnt for lo, cnt in w["wins"]) for d, _ in w["truth"].values())
+    c = M.ties_case()
+    ref = caf64(c["tm"], c["rx"], c["nu"], np.arange(c["cnt"]))
+    for j1, j2 in c["pairs"]:
+        assert c["nu"][j1] == c["nu"][j2] and j1 < j2 and (j1 // 64 == j2 // 64) == (j1 == 5)
+        np.testing.assert_allclose(ref[:, :, j1], ref[:, :, j2], rtol=1e-9)
+    for t, (d, j) in enumerate(c["planted"]):
+        assert np.argmax(ref[t].max(axis=1)) == d and np.argmax(ref[t, d]) == j
+
+
 # ------------------------------------------------------------------------------------------------------------------------------
 # the front end: FIR, upfirdn, WOLA
 
