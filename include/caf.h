@@ -622,6 +622,35 @@ CAF_EXPORT int32_t caf_viterbi_demod(const caf_viterbi_desc* desc, void* stream)
 /* the limits and the traceback chunk (the size at which the kernel changes path) */
 CAF_EXPORT int32_t caf_viterbi_geometry(int32_t* max_states, int32_t* max_pulselen, int32_t* decision_chunk);
 
+/* ---- Signal propagation and tones (signalCreationRoutines.py: propagateSignal :296-328, propagateSignalExact :331-353,
+ * freqshiftSignal :398-418, cupyAddTonePhase :454-487, cupyGenTonesDirect / cupyGenTonesScaling :500-560).  Added after ABI 1.10
+ * without a version bump, detected by symbol.  Signals and results are complex64; every phase is formed and reduced to a
+ * fraction of a turn in float64 (csrc/caf_propagate.hip).  k' is the signed bin of makeFreq: k for 2 k < len, k - len otherwise,
+ * so for even len bin len / 2 is -fs / 2. */
+/* propagateSignal: d_out (num_delays, len) = IFFT( FFT(d_sig row r, or the one row when rows_sig == 1) exp(-j 2 pi f_k t_r) ),
+ * f_k = k' fs / len, d_time (num_delays) float64 seconds, times d_tone (len complex64) when that is not NULL.  Any len. */
+CAF_EXPORT int32_t caf_propagate(const float* d_sig, int32_t rows_sig, int64_t len, const double* d_time, int32_t num_delays,
+                                 double fs, const float* d_tone, float* d_out, void* stream);
+/* propagateSignalExact for one signal row d_sig (len) and `rows` rows of delays d_tau (rows, len) float64 seconds:
+ * d_out[r][n] = exp(-j 2 pi f_c tau[r][n]) (1 / len) sum_k X[k] exp(j 2 pi (n / fs - tau[r][n]) f_k), X = FFT(d_sig).
+ * len^2 terms per row; 1 <= len <= 2^20, anything else is refused with CAF_ERR_INVALID before a launch.  Deterministic, and a
+ * row's result does not depend on the other rows. */
+CAF_EXPORT int32_t caf_propagate_exact(const float* d_sig, const double* d_tau, int32_t rows, int32_t len, double fs, double f_c,
+                                       float* d_out, void* stream);
+/* the limits and tile sizes of caf_propagate_exact (the sizes at which the kernel changes path, and the rotor's re-seed
+ * interval, on which its error bound depends) */
+CAF_EXPORT int32_t caf_propagate_geometry(int32_t* max_len, int32_t* reseed_interval, int32_t* outputs_per_workgroup,
+                                          int32_t* waves_per_workgroup);
+/* genTones{Direct,Scaling}_{64f,32f}: d_out (num_freqs, length) complex128 (c128 = 1) or complex64, row i =
+ * exp(j pi (2 (f0 + i fstep) n)), the phase in float64.  Every row is computed directly: the Scaling kernels' accumulated
+ * drift is not reproduced. */
+CAF_EXPORT int32_t caf_gen_tones(double f0, double fstep, int32_t num_freqs, int64_t length, int32_t c128, void* d_out,
+                                 void* stream);
+/* addPhase, in place: d_phase[i] = (float)fma(2 pi freq, fma(i, tstep, tstart), d_phase[i]), the arithmetic in float64 */
+CAF_EXPORT int32_t caf_add_tone_phase(float* d_phase, int64_t len, double freq, double tstart, double tstep, void* stream);
+/* d_out[r][i] = d_x[r][i] exp(j 2 pi fnorm i), fnorm in cycles per sample (freqshiftSignal with fnorm = freq / fs) */
+CAF_EXPORT int32_t caf_freq_shift(const float* d_x, int64_t rows, int64_t len, double fnorm, float* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

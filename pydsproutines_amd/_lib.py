@@ -291,6 +291,12 @@ _SIGNATURES = {
     "caf_viterbi_table": [_P, _P, _I32, _I32, _I32, _I32, _P, _P],
     "caf_viterbi_demod": [ct.POINTER(CafViterbiDesc), _P],
     "caf_viterbi_geometry": [ct.POINTER(_I32), ct.POINTER(_I32), ct.POINTER(_I32)],
+    "caf_propagate": [_P, _I32, _I64, _P, _I32, ct.c_double, _P, _P, _P],
+    "caf_propagate_exact": [_P, _P, _I32, _I32, ct.c_double, ct.c_double, _P, _P],
+    "caf_propagate_geometry": [ct.POINTER(_I32), ct.POINTER(_I32), ct.POINTER(_I32), ct.POINTER(_I32)],
+    "caf_gen_tones": [ct.c_double, ct.c_double, _I32, _I64, _I32, _P, _P],
+    "caf_add_tone_phase": [_P, _I64, ct.c_double, ct.c_double, ct.c_double, _P],
+    "caf_freq_shift": [_P, _I64, _I64, ct.c_double, _P, _P],
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
