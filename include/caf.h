@@ -651,6 +651,38 @@ CAF_EXPORT int32_t caf_add_tone_phase(float* d_phase, int64_t len, double freq, 
 /* d_out[r][i] = d_x[r][i] exp(j 2 pi fnorm i), fnorm in cycles per sample (freqshiftSignal with fnorm = freq / fs) */
 CAF_EXPORT int32_t caf_freq_shift(const float* d_x, int64_t rows, int64_t len, double fnorm, float* d_out, void* stream);
 
+/* ---- Subspace spectra (musicRoutines.py: MUSIC, CAPON, ESPRIT, musicAlg; xcorrRoutines.py: musicXcorr :378-410).  Added after
+ * ABI 1.10 without a version bump, detected by symbol.  All arithmetic is float64, nothing is atomic, and entry b of a batch is
+ * bitwise what the same problem gives alone (csrc/caf_music.hip).  Matrices are row-major complex128 (re, im pairs). */
+/* the limits: rows of a covariance, the sweep limit of the eigensolver, the covariance tile (the size at which the kernel takes
+ * another workgroup) and the largest batch of one call */
+CAF_EXPORT int32_t caf_music_geometry(int32_t* min_rows, int32_t* max_rows, int32_t* max_sweeps, int32_t* cov_tile, int32_t* max_batch);
+/* Snapshot covariances: d_rx (batch, rows, rows), Rx[i][j] = h_scale[b] sum_segments sum_c x[c jump + i] conj(x[c jump + j]).
+ * d_x: x_len elements, complex128 (x_c128 = 1) or complex64.  h_segs: (batch, nseg, 3) int64 (offset, element stride, length) in
+ * elements of d_x; a segment gives (length - rows) / jump + 1 snapshots (snapshotJump = None of the reference is jump = rows) and
+ * must lie inside d_x with length >= rows.  fwd_bwd: 0.5 (Rx + J Rx^T J); toeplitz: every diagonal replaced by its mean, after
+ * that. */
+CAF_EXPORT int32_t caf_music_cov(const void* d_x, int32_t x_c128, int64_t x_len, const int64_t* h_segs, int32_t nseg, int32_t batch,
+                                 int32_t rows, int64_t jump, const double* h_scale, int32_t fwd_bwd, int32_t toeplitz, double* d_rx,
+                                 void* stream);
+/* Hermitian eigendecompositions of d_rx (batch, rows, rows) by one-sided Jacobi: d_s (batch, rows) descending, d_u (batch, rows,
+ * rows) the unit eigenvectors as columns in that order (the phase of a column is unspecified), d_vh = u^H (or NULL).
+ * d_status (batch) int32: the sweeps used, or -1 where the sweep limit ran out (the outputs of that entry are then not to be
+ * used; the call itself still returns CAF_OK). */
+CAF_EXPORT int32_t caf_music_eig(const double* d_rx, int32_t batch, int32_t rows, double* d_s, double* d_u, double* d_vh,
+                                 int32_t* d_status, void* stream);
+/* Pseudo-spectra: with g_k(f) = |sum_m exp(-j 2 pi f m) u[m][k]|^2, denom_p = sum_{k >= p} g_k and num_p = sum_{k < p} g_k / s_k:
+ * mode 0: d_f = 1 / denom_p; mode 1: num_p / denom_p (the signal subspace as numerator); mode 2 (Capon, np = 1, h_plist ignored):
+ * 1 / sum_k g_k / s_k.  d_freqs (nfreq) float64 cycles per sample; h_plist (np) int32, 0 <= p < rows; d_f (batch, np, nfreq)
+ * float64; d_denom / d_num: the same shape, or NULL. */
+CAF_EXPORT int32_t caf_music_spectrum(const double* d_u, const double* d_s, int32_t batch, int32_t rows, const double* d_freqs,
+                                      int32_t nfreq, const int32_t* h_plist, int32_t np, int32_t mode, double* d_f, double* d_denom,
+                                      double* d_num, void* stream);
+/* The filtered products of musicXcorr: d_out (batch, len) complex128, row b = lfilter(taps, 1, rx[s_b : s_b + len] conj(cutout)),
+ * direct form.  d_rx (rx_len), d_cutout (len), d_taps (ntaps) complex128; h_shifts (batch) int64, 0 <= s_b <= rx_len - len. */
+CAF_EXPORT int32_t caf_music_xcorr_front(const double* d_rx, int64_t rx_len, const double* d_cutout, int64_t len, const double* d_taps,
+                                         int32_t ntaps, const int64_t* h_shifts, int32_t batch, double* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -297,6 +297,11 @@ _SIGNATURES = {
     "caf_gen_tones": [ct.c_double, ct.c_double, _I32, _I64, _I32, _P, _P],
     "caf_add_tone_phase": [_P, _I64, ct.c_double, ct.c_double, ct.c_double, _P],
     "caf_freq_shift": [_P, _I64, _I64, ct.c_double, _P, _P],
+    "caf_music_geometry": [ct.POINTER(_I32), ct.POINTER(_I32), ct.POINTER(_I32), ct.POINTER(_I32), ct.POINTER(_I32)],
+    "caf_music_cov": [_P, _I32, _I64, _P, _I32, _I32, _I32, _I64, _P, _I32, _I32, _P, _P],
+    "caf_music_eig": [_P, _I32, _I32, _P, _P, _P, _P, _P],
+    "caf_music_spectrum": [_P, _P, _I32, _I32, _P, _I32, _P, _I32, _I32, _P, _P, _P, _P],
+    "caf_music_xcorr_front": [_P, _I64, _P, _I64, _P, _I32, _P, _I32, _P, _P],
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

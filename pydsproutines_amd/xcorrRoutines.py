@@ -286,6 +286,64 @@ def fastXcorr(cutout, rx, freqsearch=False, outputCAF=False, shifts=None, absRes
 _CZTXCORR_FORCE_ROWS = None  # tests: True / False pins cztXcorr's path
 
 
+_MUSICXCORR_SCRATCH_BYTES = 1 << 30  # device memory one chunk of musicXcorr's shifts may take
+
+
+def _c128_device(a):
+    if isinstance(a, DeviceArray):
+        if a.dtype == np.dtype(np.complex128):
+            return a.reshape(-1)
+        a = a.get()
+    return asarray(np.ascontiguousarray(np.asarray(a).reshape(-1), dtype=np.complex128))
+
+
+def musicXcorr(cutout, rx, f_search, ftap, fs, dsr, plist, musicrows=130, shifts=None):
+    """ref: xcorrRoutines.py:378-410: the CAF whose frequency axis is a MUSIC pseudo-spectrum.  Per shift the product
+    rx[s : s + N] conj(cutout) is filtered with ftap (lfilter), its dsr polyphase slices from len(ftap) // 2 on are the
+    segments of one forward-backward covariance of musicrows rows (snapshotJump = 1), and the pseudo-spectrum has the signal
+    subspace as numerator.  Returns {p: (len(shifts), len(f_search)) float64}.  All shifts go through the four kernels of
+    csrc/caf_music.hip as one batch (float64 throughout), cut into chunks only by scratch size; cutout and rx may be host or
+    device arrays."""
+    from . import musicRoutines as M
+
+    n, rx_len = int(cutout.size), int(rx.size)
+    rows = M._check_rows(musicrows)
+    plist = list(plist)
+    pl, _ = M._check_plist(plist, rows)
+    if int(dsr) != dsr or dsr < 1:
+        raise ValueError("dsr must be a positive integer.")
+    dsr = int(dsr)
+    freqs = M._check_freqlist(np.asarray(f_search, dtype=np.float64) / (fs / dsr))
+    taps = np.asarray(ftap).reshape(-1)
+    if taps.size < 1 or n < 1 or n > rx_len:
+        raise ValueError("ftap and cutout must not be empty, and cutout must not be longer than rx.")
+    shifts = np.arange(rx_len - n + 1) if shifts is None else np.asarray(shifts).reshape(-1)
+    if shifts.size and (shifts.min() < 0 or shifts.max() + n > rx_len):
+        raise ValueError("A shift reaches outside rx.")
+    start = taps.size // 2
+    lengths = [len(range(start + k, n, dsr)) for k in range(dsr)]
+    jump, scale, _ = M.planSnapshots(lengths, rows, 1)
+    results = {p: np.zeros((shifts.size, freqs.size)) for p in plist}
+    if not shifts.size:
+        return results
+    _lib.require_device()
+    d_cut, d_rx = _c128_device(cutout), _c128_device(rx)
+    per_shift = 16 * n + 16 * 6 * rows * rows + 8 * pl.size * freqs.size
+    chunk = int(max(1, min(M.MUSIC_MAX_BATCH, _MUSICXCORR_SCRATCH_BYTES // per_shift)))
+    for b0 in range(0, shifts.size, chunk):
+        sh = shifts[b0 : b0 + chunk]
+        d_front = M.xcorrFront(d_rx, d_cut, taps, sh)
+        segs = np.zeros((sh.size, dsr, 3), np.int64)
+        segs[:, :, 0] = np.arange(sh.size)[:, None] * n + start + np.arange(dsr)[None, :]
+        segs[:, :, 1] = dsr
+        segs[:, :, 2] = lengths
+        d_cov = M.snapshotCovariance(d_front.reshape(-1), segs, rows, jump, scale, fwdBwd=True)
+        f = M._spectra(d_cov, rows, freqs, pl, True, vectors=False)[0]
+        for k, p in enumerate(plist):
+            results[p][b0 : b0 + sh.size] = f[:, k]
+    return results
+
+
 _CZT_OBJECTS = {}  # the last few CZT objects of cztXcorr's per-delay form (chirps + transform plans: milliseconds to build)
 
 
