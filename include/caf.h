@@ -683,6 +683,61 @@ CAF_EXPORT int32_t caf_music_spectrum(const double* d_u, const double* d_s, int3
 CAF_EXPORT int32_t caf_music_xcorr_front(const double* d_rx, int64_t rx_len, const double* d_cutout, int64_t len, const double* d_taps,
                                          int32_t ntaps, const int64_t* h_shifts, int32_t batch, double* d_out, void* stream);
 
+/* ---- Moving-platform scenarios (trajectoryRoutines.py: Trajectory.to / frm; cython_ext/PySampledLinearInterpolator: the
+ * ConstAmpSigLerp family).  Added after ABI 1.10 without a version bump, detected by symbol.  All arithmetic is float64, nothing
+ * is atomic, one thread per (row, sample): a row is bitwise the same whatever the number of rows (csrc/caf_scene.hip).
+ * The small tables are host arrays (h_), read and checked before a launch; the long ones are device arrays (d_). */
+#define CAF_TRAJ_STATIONARY 0
+#define CAF_TRAJ_CONSTANT_VELOCITY 1
+#define CAF_TRAJ_INTERPOLATED 2
+typedef struct caf_traj_table {
+    int32_t count;             /* trajectories */
+    int32_t reserved;
+    const int32_t* h_kind;     /* (count) CAF_TRAJ_* */
+    const double* h_x0v;       /* (count, 6) x0 and v, metres and metres per second; z = 0 for a 2-D trajectory.  An interpolated
+                                * trajectory's row is not read. */
+    const int64_t* h_knot_off; /* (count + 1) trajectory i owns knots h_knot_off[i] .. h_knot_off[i + 1] of d_tp / d_xp: at least
+                                * 2 for an interpolated one, none otherwise */
+    const double* d_tp;        /* (h_knot_off[count]) knot times, strictly increasing within a trajectory; NULL without knots */
+    const double* d_xp;        /* (h_knot_off[count], 3) knot positions; piecewise linear, held at the end knots outside tp */
+} caf_traj_table;
+typedef struct caf_burst_table {
+    int32_t count;              /* emitters (signals) */
+    int32_t reserved;
+    const int32_t* h_burst_off; /* (count + 1) emitter e owns bursts h_burst_off[e] .. h_burst_off[e + 1], at least one */
+    const double* h_burst;      /* (bursts, 7): timevec[0], timevec[-1] - timevec[0], T, amp, fc, phi, tJump.  Within an emitter
+                                 * the emission windows are in ascending order and disjoint as float64 computes them:
+                                 * (timevec[0] + tJump) + span of a burst <= timevec[0] + tJump of the next. */
+    const int64_t* h_phase_off; /* (bursts + 1) burst b owns d_phase[h_phase_off[b] .. h_phase_off[b + 1]], at least 2 knots, and
+                                 * span <= (knots - 1 + 1e-3) T (the last segment serves what lies past the last knot) */
+    const double* d_phase;      /* the phase tables, radians, knot k at timevec[0] + k T */
+} caf_burst_table;
+/* the limits: emitters, receivers (rows of caf_traj_tau and of caf_scene_propagate), bursts per emitter, knots of all trajectories
+ * of a table together, and the threads (= outputs) per workgroup */
+CAF_EXPORT int32_t caf_scene_geometry(int32_t* max_emitters, int32_t* max_receivers, int32_t* max_bursts, int64_t* max_knots,
+                                      int32_t* threads_per_workgroup, int32_t* outputs_per_workgroup);
+/* Light times.  d_tau (others->count, n) float64: row r is self.to(other_r, d_t) (direction 0: the photon leaves self at t) or
+ * self.frm(other_r, d_t) (direction 1: it arrives at self at t), the solution of c tau = |p_self(t) - p_other(t +- tau)|.
+ * self holds one trajectory.  A stationary other: distance / c.  A constant-velocity other with method 0 and a self that is
+ * not interpolated: the quadratic in closed form.  Anything else (method 1, an interpolated side): 5 fixed-point steps from 0.
+ * A constant-velocity speed of 1e-4 c or more is refused; the segments of an interpolated trajectory must be slower than that too
+ * (not checked here: the knots are on the device), or the 5 steps do not reach float64. */
+CAF_EXPORT int32_t caf_traj_tau(const caf_traj_table* self, const caf_traj_table* others, const double* d_t, int64_t n,
+                                int32_t direction, int32_t method, double* d_tau, void* stream);
+/* d_out[n] = sum_e sum_b amp exp(j (lerp(phase_b)(u) - 2 pi fc (tau[n] + tJump) + phi)), u = t[n] - tau[n] - tJump - timevec[0],
+ * a term present iff 0 <= u < span; n < start_idx gives 0.  d_t, d_tau (n) float64; d_out (n) complex128 (c128 = 1) or
+ * complex64.  The emitters are summed in order in float64 and rounded once. */
+CAF_EXPORT int32_t caf_lerp_propagate(const caf_burst_table* bursts, const double* d_t, const double* d_tau, int64_t n,
+                                      int64_t start_idx, int32_t c128, void* d_out, void* stream);
+/* The same sum with t[n] = t0 + n dt and, for emitter e and receiver r, tau = receivers[r].frm(emitters[e], t[n]) solved in the
+ * kernel (method 0): d_out (receivers->count, n).  emitters->count == bursts->count.  dt > 0.
+ * Precondition, not checked here for knot tables (they are on the device): every segment of an interpolated emitter or receiver
+ * is slower than 1e-4 c, and dt is many ulps of t0 + n dt, so that the emission time t - tau increases with n.  A workgroup
+ * brackets the bursts of its first and last sample and looks no further; where the precondition fails, terms can be missing from
+ * the result (no access leaves the tables).  The Python layer checks the speeds. */
+CAF_EXPORT int32_t caf_scene_propagate(const caf_traj_table* emitters, const caf_traj_table* receivers, const caf_burst_table* bursts,
+                                       double t0, double dt, int64_t n, int32_t c128, void* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

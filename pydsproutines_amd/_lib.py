@@ -185,6 +185,33 @@ class CafViterbiDesc(ct.Structure):
     ]
 
 
+class CafTrajTable(ct.Structure):
+    _fields_ = [
+        ("count", ct.c_int32),
+        ("reserved", ct.c_int32),
+        ("h_kind", ct.c_void_p),
+        ("h_x0v", ct.c_void_p),
+        ("h_knot_off", ct.c_void_p),
+        ("d_tp", ct.c_void_p),
+        ("d_xp", ct.c_void_p),
+    ]
+
+
+class CafBurstTable(ct.Structure):
+    _fields_ = [
+        ("count", ct.c_int32),
+        ("reserved", ct.c_int32),
+        ("h_burst_off", ct.c_void_p),
+        ("h_burst", ct.c_void_p),
+        ("h_phase_off", ct.c_void_p),
+        ("d_phase", ct.c_void_p),
+    ]
+
+
+CAF_TRAJ_STATIONARY = 0
+CAF_TRAJ_CONSTANT_VELOCITY = 1
+CAF_TRAJ_INTERPOLATED = 2
+
 CAF_LOCATE_POINTS = 0
 CAF_LOCATE_MESH = 1
 CAF_LOCATE_MESH_XY = 2
@@ -302,6 +329,11 @@ _SIGNATURES = {
     "caf_music_eig": [_P, _I32, _I32, _P, _P, _P, _P, _P],
     "caf_music_spectrum": [_P, _P, _I32, _I32, _P, _I32, _P, _I32, _I32, _P, _P, _P, _P],
     "caf_music_xcorr_front": [_P, _I64, _P, _I64, _P, _I32, _P, _I32, _P, _P],
+    "caf_scene_geometry": [ct.POINTER(_I32), ct.POINTER(_I32), ct.POINTER(_I32), ct.POINTER(_I64), ct.POINTER(_I32), ct.POINTER(_I32)],
+    "caf_traj_tau": [ct.POINTER(CafTrajTable), ct.POINTER(CafTrajTable), _P, _I64, _I32, _I32, _P, _P],
+    "caf_lerp_propagate": [ct.POINTER(CafBurstTable), _P, _P, _I64, _I64, _I32, _P, _P],
+    "caf_scene_propagate": [ct.POINTER(CafTrajTable), ct.POINTER(CafTrajTable), ct.POINTER(CafBurstTable), ct.c_double, ct.c_double,
+                            _I64, _I32, _P, _P],
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -29,6 +29,7 @@
 #include <cstdint>
 
 #include "caf_internal.h"
+#include "caf_phase.h"  // mul_split, frac_turn
 
 #pragma clang fp contract(off)
 
@@ -42,17 +43,6 @@ constexpr int PX_THREADS = PX_WAVE * PX_WAVES;
 constexpr int PX_L = 32;                         // pairs per rotor seed (the bound of tests/propagate_ref.py grows with it)
 constexpr int PX_MAXN = 1 << 20;
 constexpr int EW_THREADS = 256;
-
-// a b = whole + rest exactly up to the last rounding of rest: whole the nearest integer of the rounded product, |rest| <= 1/2 + ulp
-__device__ __forceinline__ void mul_split(double a, double b, double* whole, double* rest) {
-    const double p = a * b;
-    const double e = fma(a, b, -p);
-    const double w = rint(p);
-    *whole = w;
-    *rest = (p - w) + e;
-}
-
-__device__ __forceinline__ double frac_turn(double t) { return t - rint(t); }
 
 // exp(j 2 pi t), |t| <= 1/2 turn (+ an ulp): quarter turns in float64, sine and cosine of the rest (<= 1/8 turn) in float32
 __device__ __forceinline__ float2 unit_f32(double t) {

@@ -114,7 +114,7 @@ def makePulsedCPFSKsyms(bits, baud, g=np.ones(8) / 16, m=2, h=0.5, up=8, phase=0
 # freqshiftSignal :398-418, cupyAddTonePhase :454-487, cupyGenTonesDirect / cupyGenTonesScaling :500-560.  Same signatures.
 # A DeviceArray in gives a DeviceArray out; an ndarray in gives an ndarray out, computed on the device in complex64 (upstream
 # computes in complex128 on the host).  Every argument is checked before the library is touched; without a device the calls
-# raise, there is no host path.  Not provided: padZeros_fftfactors (sympy) and the trajectory classes.
+# raise, there is no host path.  Not provided: padZeros_fftfactors (sympy).  (The trajectory classes: trajectoryRoutines.py.)
 
 PROPAGATE_EXACT_MAX_LEN = 1 << 20  # caf_propagate_exact: N^2 terms per row
 
