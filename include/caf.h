@@ -738,6 +738,38 @@ CAF_EXPORT int32_t caf_lerp_propagate(const caf_burst_table* bursts, const doubl
 CAF_EXPORT int32_t caf_scene_propagate(const caf_traj_table* emitters, const caf_traj_table* receivers, const caf_burst_table* bursts,
                                        double t0, double dt, int64_t n, int32_t c128, void* d_out, void* stream);
 
+/* ---- Signal cancellation (cancellationRoutines.py: cancelSignalAtIdx :11-41, and the search over acceleration factors its
+ * __main__ names).  Added after ABI 1.10 without a version bump, detected by symbol (csrc/caf_cancel.hip).  For job b with the
+ * template s = d_sigs[b] (n_len complex64 samples), the start d_idx[b], a frequency nu (cycles per sample) and a rate alpha
+ * (cycles per sample^2):
+ *   m[n] = s[n] exp(+j 2 pi (nu n + alpha n^2 / 2)),  D = sum_n conj(m[n]) rx[idx + n],  Es = sum |s|^2,  Er = sum |rx[idx + n]|^2,
+ *   amp = D / Es,  QF^2 = |D|^2 / (Es Er),  resid = Er - |D|^2 / Es,  cancelled[idx + n] = rx[idx + n] - amp m[n].
+ * Phases are formed and reduced to a fraction of a turn in float64, products and rotors are float32, sums float64 in a fixed
+ * order: nothing is atomic, and a job's outputs are bitwise the same alone and in a batch.  A window that does not lie wholly
+ * inside rx (d_idx[b] < 0 or d_idx[b] + n_len > rx_len) is CAF_ERR_INVALID: the B indices are downloaded and checked before a
+ * launch, so every call below blocks until earlier work on `stream` that wrote d_idx has finished. */
+/* the limits (n_len, jobs, rates, frequencies of one call) and the sizes on which the error bound and the paths of the search
+ * depend: template samples per work item, samples per thread, rotor steps between two float64 seeds */
+CAF_EXPORT int32_t caf_cancel_geometry(int32_t* max_len, int32_t* chunk, int32_t* samples_per_thread, int32_t* reseed_interval,
+                                       int32_t* max_jobs, int32_t* max_rates, int32_t* max_freqs);
+/* D at the J rates d_rates[j] x the K frequencies nu0 + k dnu, for every job against the same d_rx, and the arg max of |D|^2
+ * over (j, k) (the lower flat index j K + k wins ties).  Outputs, each (B) unless noted and each optional (NULL): d_best_j,
+ * d_best_k int32; d_nu = nu0 + k dnu and d_rate = d_rates[j] of the winner; d_amp (B, 2) re, im; d_qf2, d_es, d_er, d_resid at
+ * the winner; d_surface (B, J, K) float32 QF^2. */
+CAF_EXPORT int32_t caf_cancel_search(const float* d_sigs, int32_t B, int32_t n_len, const float* d_rx, int64_t rx_len,
+                                     const int32_t* d_idx, double nu0, double dnu, int32_t K, const double* d_rates, int32_t J,
+                                     int32_t* d_best_j, int32_t* d_best_k, double* d_nu, double* d_rate, double* d_amp, double* d_qf2,
+                                     double* d_es, double* d_er, double* d_resid, float* d_surface, void* stream);
+/* the same estimate at one hypothesis per job: d_nu[b], d_rate[b] (the search's kernels with J = K = 1) */
+CAF_EXPORT int32_t caf_cancel_estimate(const float* d_sigs, int32_t B, int32_t n_len, const float* d_rx, int64_t rx_len,
+                                       const int32_t* d_idx, const double* d_nu, const double* d_rate, double* d_amp, double* d_qf2,
+                                       double* d_es, double* d_er, double* d_resid, void* stream);
+/* d_out[m] = d_rx[m] - sum_b d_amp[b] m_b[m - d_idx[b]] over the jobs whose window covers m, in increasing b, one float32
+ * complex multiply-add each; other samples are copied.  d_out (rx_len) may be d_rx. */
+CAF_EXPORT int32_t caf_cancel_subtract(const float* d_sigs, int32_t B, int32_t n_len, const float* d_rx, int64_t rx_len,
+                                       const int32_t* d_idx, const double* d_nu, const double* d_rate, const double* d_amp,
+                                       float* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -334,6 +334,11 @@ _SIGNATURES = {
     "caf_lerp_propagate": [ct.POINTER(CafBurstTable), _P, _P, _I64, _I64, _I32, _P, _P],
     "caf_scene_propagate": [ct.POINTER(CafTrajTable), ct.POINTER(CafTrajTable), ct.POINTER(CafBurstTable), ct.c_double, ct.c_double,
                             _I64, _I32, _P, _P],
+    "caf_cancel_geometry": [ct.POINTER(_I32)] * 7,
+    "caf_cancel_search": [_P, _I32, _I32, _P, _I64, _P, ct.c_double, ct.c_double, _I32, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                          _P, _P],
+    "caf_cancel_estimate": [_P, _I32, _I32, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "caf_cancel_subtract": [_P, _I32, _I32, _P, _I64, _P, _P, _P, _P, _P, _P],
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -29,7 +29,7 @@
 #include <cstdint>
 
 #include "caf_internal.h"
-#include "caf_phase.h"  // mul_split, frac_turn
+#include "caf_phase.h"  // mul_split, frac_turn, unit_f32, cmulf
 
 #pragma clang fp contract(off)
 
@@ -43,23 +43,6 @@ constexpr int PX_THREADS = PX_WAVE * PX_WAVES;
 constexpr int PX_L = 32;                         // pairs per rotor seed (the bound of tests/propagate_ref.py grows with it)
 constexpr int PX_MAXN = 1 << 20;
 constexpr int EW_THREADS = 256;
-
-// exp(j 2 pi t), |t| <= 1/2 turn (+ an ulp): quarter turns in float64, sine and cosine of the rest (<= 1/8 turn) in float32
-__device__ __forceinline__ float2 unit_f32(double t) {
-    const double q = rint(4.0 * t);
-    const float f = (float)(t - 0.25 * q);
-    float s, c;
-    sincospif(2.0f * f, &s, &c);
-    const int qi = (int)q & 3;
-    float2 r;
-    r.x = qi == 0 ? c : qi == 1 ? -s : qi == 2 ? -c : s;
-    r.y = qi == 0 ? s : qi == 1 ? c : qi == 2 ? -s : -c;
-    return r;
-}
-
-__device__ __forceinline__ float2 cmulf(float2 a, float2 b) {
-    return make_float2(fmaf(a.x, b.x, -(a.y * b.y)), fmaf(a.x, b.y, a.y * b.x));
-}
 
 // pairs[m] = (X[m] or 0, X[N - m] or 0), m < total (a multiple of PX_L, zero beyond N / 2)
 __global__ __launch_bounds__(EW_THREADS) void k_px_pairs(const float2* __restrict__ X, int32_t N, int32_t total, float4* __restrict__ pairs) {
