@@ -147,34 +147,10 @@ __global__ __launch_bounds__(256) void k_wm_count(const K* __restrict__ a, int64
             const bool zero = i < n && !((a[i] >> bit) & 1);
             c += __popcll(__ballot(zero));
         }
-        if (lane == 0) s_w[wave] = c;
-        __syncthreads();
-        if (threadIdx.x == 0) tile_cnt[t] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-        __syncthreads();
-    }
-}
-
-// in place exclusive scan, a[n] = the total.  One workgroup.
-__global__ __launch_bounds__(1024) void k_scan_i64(int64_t* __restrict__ a, int64_t n) {
-    __shared__ int64_t s_wave[16];
-    __shared__ int64_t s_base;
-    if (threadIdx.x == 0) s_base = 0;
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int64_t c0 = 0; c0 < n; c0 += 1024) {
-        const int64_t t = c0 + threadIdx.x;
-        const int64_t v = t < n ? a[t] : 0;
-        const int64_t incl = wave_scan_inclusive(v, lane);
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        int64_t off = s_base;
-        for (int w = 0; w < wave; ++w) off += s_wave[w];
-        if (t < n) a[t] = off + incl - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) s_base = off + incl;
+        const int64_t z = block_sum_totals(c, s_w);
+        if (threadIdx.x == 0) tile_cnt[t] = z;
         __syncthreads();
     }
-    if (threadIdx.x == 0) a[n] = s_base;
 }
 
 // the words of one level and (unless it is the last) the next level's order.  tile_off: scanned zero counts,
@@ -199,6 +175,8 @@ __global__ __launch_bounds__(256) void k_wm_level(const K* __restrict__ a, int64
             ones[ch] = __ballot(i >= n || ((v[ch] >> bit) & 1));
             c += 64 - __popcll(ones[ch]);
         }
+        // (the carry of block_exclusive of caf_wave.h, spelled out: through the helper the uint32 form takes 97 VGPRs for 82,
+        // one wave per SIMD fewer)
         if (lane == 0) s_w[wave] = c;
         __syncthreads();
         int64_t z = tile_off[t];
@@ -330,7 +308,7 @@ int medfilt_wavelet(const T* x, int64_t n, int64_t W, T* out, hipStream_t st) {
     for (int l = 0; l < BITS; ++l) {
         const int bit = BITS - 1 - l;
         hipLaunchKernelGGL(k_wm_count<K>, dim3(gt), dim3(256), 0, st, a, n, bit, ntiles, tiles);
-        hipLaunchKernelGGL(k_scan_i64, dim3(1), dim3(1024), 0, st, tiles, ntiles);
+        launch_scan_exclusive(tiles, ntiles, st);
         hipLaunchKernelGGL(k_wm_level<K>, dim3(gt), dim3(256), 0, st, a, n, bit, ntiles, tiles, words + (int64_t)l * nwl,
                            l + 1 < BITS ? b : nullptr, Zs + l);
         std::swap(a, b);
@@ -388,14 +366,8 @@ __global__ __launch_bounds__(GE_TILE) void k_ge_count(const int32_t* __restrict_
         const int32_t k = ge_stored(counts, r, emax);
         for (int32_t j = 0; j < k; ++j) c += edges[r * emax + j] != 0;
     }
-    c = wave_sum(c);
-    if (lane == 0) s_w[wave] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int64_t t = 0;
-        for (int w = 0; w < GE_TILE / 64; ++w) t += s_w[w];
-        tile_cnt[blockIdx.x] = t;
-    }
+    c = block_sum(c, s_w);
+    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = c;
 }
 
 __global__ __launch_bounds__(GE_TILE) void k_ge_compact(const int32_t* __restrict__ edges, const int32_t* __restrict__ counts,
@@ -411,10 +383,7 @@ __global__ __launch_bounds__(GE_TILE) void k_ge_compact(const int32_t* __restric
         for (int32_t j = 0; j < k; ++j) c += edges[r * emax + j] != 0;
     }
     const int64_t incl = wave_scan_inclusive(c, lane);
-    if (lane == 63) s_w[wave] = incl;
-    __syncthreads();
-    int64_t off = tile_off[blockIdx.x] + incl - c;
-    for (int w = 0; w < wave; ++w) off += s_w[w];
+    int64_t off = tile_off[blockIdx.x] + block_exclusive(incl, c, lane, wave, s_w);
     for (int32_t j = 0; j < k; ++j) {
         const int32_t v = edges[r * emax + j];
         if (v != 0) flat[off++] = v;
@@ -442,12 +411,10 @@ __global__ __launch_bounds__(1024) void k_ge_pair(const int32_t* __restrict__ fl
         const int64_t j = c0 + me;
         const int32_t e = j < T ? flat[j] : 0;
         int32_t seg = wave_scan_inclusive(e > 0 ? me + 1 : 0, lane, [](int32_t a, int32_t b) { return max(a, b); });
-        if (lane == 63) s_wave[wave] = seg;
         s_lval[me + 1] = e > 0 ? e : 0;
         s_first[me + 1] = 0x7fffffff;
         if (me == 0) s_lval[0] = s_state, s_first[0] = 0x7fffffff;
-        __syncthreads();
-        for (int w = 0; w < wave; ++w) seg = max(seg, s_wave[w]);
+        seg = block_carry(seg, seg, lane, wave, s_wave, [](int32_t a, int32_t b) { return max(a, b); });
         const int32_t L = s_lval[seg];
         const int64_t R = e < 0 ? -(int64_t)e : 0;
         const int64_t d = R - L;
@@ -456,19 +423,16 @@ __global__ __launch_bounds__(1024) void k_ge_pair(const int32_t* __restrict__ fl
         const int32_t f = s_first[seg];
         const bool emit = e < 0 && (me == f || (me > f && R >= mn && R <= mx));
         const uint64_t bal = __ballot(emit);
-        if (lane == 0) s_wave[wave] = __popcll(bal);
-        __syncthreads();
-        int64_t pos = s_out + __popcll(bal & lanemask_lt());
-        for (int w = 0; w < wave; ++w) pos += s_wave[w];
+        const int32_t cnt = __popcll(bal);
+        const int32_t before = block_exclusive(cnt, cnt, lane, wave, s_wave);  // emitted by the waves before this one
+        const int64_t pos = s_out + before + __popcll(bal & lanemask_lt());
         if (emit && pos < cap) {
             pairs[2 * pos] = me == f ? L : 0;
             pairs[2 * pos + 1] = (int32_t)R;
         }
         __syncthreads();
         if (me == 1023) {
-            int64_t tot = 0;
-            for (int w = 0; w < 16; ++w) tot += s_wave[w];
-            s_out += tot;
+            s_out += before + cnt;
             // the chunk's last segment hands its state on: 0 once it has paired, else its left value
             s_state = s_first[seg] != 0x7fffffff ? 0 : s_lval[seg];
         }
@@ -482,7 +446,7 @@ template <typename T, bool WRITE>
 __global__ __launch_bounds__(256) void k_above(const T* __restrict__ x, int64_t n, T thr, int64_t ntiles,
                                                int64_t* __restrict__ tile_a, int64_t* __restrict__ tile_s,
                                                int64_t* __restrict__ idx, int64_t* __restrict__ starts) {
-    __shared__ int64_t s_a[4], s_s[4];
+    __shared__ WaveSlots<4, int64_t, int64_t> s_as;  // (above, run starts)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
         const int64_t b0 = t * WM_TILE + (int64_t)wave * 1024;
@@ -499,16 +463,15 @@ __global__ __launch_bounds__(256) void k_above(const T* __restrict__ x, int64_t 
             ca += __popcll(ma[ch]);
             cs += __popcll(ms[ch]);
         }
-        if (lane == 0) s_a[wave] = ca, s_s[wave] = cs;
-        __syncthreads();
         if (!WRITE) {
-            if (threadIdx.x == 0) {
-                tile_a[t] = s_a[0] + s_a[1] + s_a[2] + s_a[3];
-                tile_s[t] = s_s[0] + s_s[1] + s_s[2] + s_s[3];
-            }
+            block_sum_totals(s_as, ca, cs);
+            if (threadIdx.x == 0) tile_a[t] = ca, tile_s[t] = cs;
         } else {
+            // (two carries from ONE store and barrier: block_exclusive of caf_wave.h, spelled out for the pair)
+            if (lane == 0) s_as.put(wave, ca, cs);
+            __syncthreads();
             int64_t oa = tile_a[t], os = tile_s[t];
-            for (int w = 0; w < wave; ++w) oa += s_a[w], os += s_s[w];
+            for (int w = 0; w < wave; ++w) oa += s_as.a[w], os += s_as.rest.a[w];
 #pragma unroll
             for (int ch = 0; ch < 16; ++ch) {
                 const int64_t i = b0 + ch * 64 + lane;
@@ -614,8 +577,8 @@ int above_threshold(const T* x, int64_t n, T thr, int64_t* idx, int64_t idx_cap,
     if ((rc = sc.get(&ta, ntiles + 1)) || (rc = sc.get(&ts, ntiles + 1))) return rc;
     const unsigned g = grid_for(ntiles, 1, 1 << 16);
     hipLaunchKernelGGL((k_above<T, false>), dim3(g), dim3(256), 0, st, x, n, thr, ntiles, ta, ts, nullptr, nullptr);
-    hipLaunchKernelGGL(k_scan_i64, dim3(1), dim3(1024), 0, st, ta, ntiles);
-    hipLaunchKernelGGL(k_scan_i64, dim3(1), dim3(1024), 0, st, ts, ntiles);
+    launch_scan_exclusive(ta, ntiles, st);
+    launch_scan_exclusive(ts, ntiles, st);
     int64_t tot[2] = {0, 0};
     CAF_HIP_TRY(hipMemcpyAsync(&tot[0], ta + ntiles, 8, hipMemcpyDeviceToHost, st));
     CAF_HIP_TRY(hipMemcpyAsync(&tot[1], ts + ntiles, 8, hipMemcpyDeviceToHost, st));
@@ -727,7 +690,7 @@ int32_t caf_gather_edges(const int32_t* d_edges, int64_t rows, int32_t edges_max
     int rc;
     if ((rc = sc.get(&tiles, ntiles + 1)) || (rc = sc.get(&np, 1))) return rc;
     hipLaunchKernelGGL(k_ge_count, dim3((unsigned)ntiles), dim3(GE_TILE), 0, st, d_edges, d_counts, rows, edges_max, tiles);
-    hipLaunchKernelGGL(k_scan_i64, dim3(1), dim3(1024), 0, st, tiles, ntiles);
+    launch_scan_exclusive(tiles, ntiles, st);
     int64_t T = 0;
     CAF_HIP_TRY(hipMemcpyAsync(&T, tiles + ntiles, 8, hipMemcpyDeviceToHost, st));
     CAF_HIP_TRY(hipStreamSynchronize(st));

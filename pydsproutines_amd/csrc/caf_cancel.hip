@@ -36,7 +36,7 @@
 
 #include "caf_internal.h"
 #include "caf_phase.h"  // mul_split, frac_turn, unit_f32, cmulf
-#include "caf_wave.h"   // wave_sum, wave_argmax
+#include "caf_wave.h"   // wave_sum, wave_argmax, block_sum, block_argmax
 
 #pragma clang fp contract(off)
 
@@ -72,7 +72,7 @@ __global__ __launch_bounds__(CS_THREADS) void k_cancel_search(const float2* __re
                                                             const double* __restrict__ job_rate, int32_t chunks, int32_t units_per_item,
                                                             double2* __restrict__ part, double2* __restrict__ energy) {
     __shared__ float2 s_acc[CS_KT][CS_THREADS];
-    __shared__ double2 s_e[CS_THREADS / 64];
+    __shared__ WaveSlots<CS_THREADS / 64, double, double> s_e;
     const int tid = threadIdx.x;
     const int32_t chunk = (int32_t)blockIdx.x, b = (int32_t)blockIdx.y;
     const int64_t start = idx[b];
@@ -100,19 +100,8 @@ __global__ __launch_bounds__(CS_THREADS) void k_cancel_search(const float2* __re
         sincospi(-2.0 * frac_turn(turn_of(dnu, (double)n)), &ws, &wc);
         w[i] = make_float2((float)wc, (float)ws);
     }
-    es = wave_sum(es);
-    er = wave_sum(er);
-    if ((tid & 63) == 0) s_e[tid >> 6] = make_double2(es, er);
-    __syncthreads();
-    if (tid == 0 && blockIdx.z == 0) {
-        double a = s_e[0].x, c = s_e[0].y;
-#pragma unroll
-        for (int v = 1; v < CS_THREADS / 64; v++) {
-            a += s_e[v].x;
-            c += s_e[v].y;
-        }
-        energy[(int64_t)b * chunks + chunk] = make_double2(a, c);
-    }
+    block_sum(s_e, es, er);
+    if (tid == 0 && blockIdx.z == 0) energy[(int64_t)b * chunks + chunk] = make_double2(es, er);
 
     // A unit is (rate j, block of CS_RESEED frequencies): it starts with a seed, so its values do not depend on which item runs it.
     const int kt = tid >> 4, sub = tid & 15;  // the tile fold: frequency kt of the tile, 16 values in turn from sub
@@ -167,7 +156,7 @@ struct CancelBest {
 __global__ __launch_bounds__(CS_THREADS) void k_cancel_fold(const double2* __restrict__ part, const double2* __restrict__ energy, int32_t chunks,
                                                           int32_t JK, int32_t tiles, float* __restrict__ surface, int32_t job0,
                                                           CancelBest* __restrict__ best) {
-    __shared__ CancelBest s_best[CS_THREADS / 64];
+    __shared__ WaveSlots<CS_THREADS / 64, double, int32_t, double, double> s_best;
     const int tid = threadIdx.x;
     const int32_t tile = (int32_t)blockIdx.x, b = (int32_t)blockIdx.y;
     const int32_t f = tile * CS_THREADS + tid;
@@ -190,18 +179,8 @@ __global__ __launch_bounds__(CS_THREADS) void k_cancel_fold(const double2* __res
     if (v != v) v = -1.0;  // (a NaN never wins)
     if (surface && f < JK) surface[(int64_t)(job0 + b) * JK + f] = (float)(v < 0.0 ? NAN : v / (es * er));
     int32_t fi = f;
-    wave_argmax(v, fi, dr, di);
-    if ((tid & 63) == 0) s_best[tid >> 6] = CancelBest{v, dr, di, fi, 0};
-    __syncthreads();
-    if (tid == 0) {
-        CancelBest r = s_best[0];
-#pragma unroll
-        for (int w = 1; w < CS_THREADS / 64; w++) {
-            const CancelBest o = s_best[w];
-            if (o.v > r.v || (o.v == r.v && o.f < r.f)) r = o;
-        }
-        best[(int64_t)b * tiles + tile] = r;
-    }
+    block_argmax(s_best, v, fi, dr, di);
+    if (tid == 0) best[(int64_t)b * tiles + tile] = CancelBest{v, dr, di, fi, 0};
 }
 
 __global__ __launch_bounds__(64) void k_cancel_pick(const CancelBest* __restrict__ best, const double2* __restrict__ energy, int32_t chunks,
@@ -267,6 +246,7 @@ __global__ __launch_bounds__(CS_THREADS) void k_cancel_subtract(const float2* __
         meets = a < m0 + CS_THREADS && a + N > m0;
     }
     const unsigned long long mask = __ballot(meets);
+    // (the carry AND the total from one store and barrier: block_exclusive and block_sum_totals of caf_wave.h would take two)
     if (lane == 0) s_count[wave] = __popcll(mask);
     __syncthreads();
     int32_t before = 0, count = 0;

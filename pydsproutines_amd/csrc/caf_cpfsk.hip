@@ -249,8 +249,7 @@ __global__ __launch_bounds__(COST_T) void k_cp2fsk_costs_tile(const double* __re
 __global__ __launch_bounds__(CT) void k_argmax_f64(const double* __restrict__ v, const int64_t* __restrict__ idx_in, int64_t n, int64_t rows,
                                                    int64_t chunk, double* __restrict__ pv, int64_t* __restrict__ pi,
                                                    int64_t* __restrict__ out_final, int64_t add, int64_t limit) {
-    __shared__ double s_v[CT / 64];
-    __shared__ long long s_i[CT / 64];
+    __shared__ WaveSlots<CT / 64, double, long long> s_best;
     const int64_t e0 = (int64_t)blockIdx.x * chunk, e1 = std::min(n, e0 + chunk);
     for (int64_t row = blockIdx.y; row < rows; row += gridDim.y) {
         double bv = -INFINITY;
@@ -258,29 +257,13 @@ __global__ __launch_bounds__(CT) void k_argmax_f64(const double* __restrict__ v,
         for (int64_t e = e0 + threadIdx.x; e < e1; e += CT) {
             const double val = v[row * n + e];
             const long long i = idx_in ? (long long)idx_in[row * n + e] : (long long)e;
-            if (val > bv || (val == bv && i < bi)) {
+            if (first_max(bv, bi, val, i)) {
                 bv = val;
                 bi = i;
             }
         }
-        wave_argmax(bv, bi);
-        const int w = threadIdx.x >> 6;
-        if ((threadIdx.x & 63) == 0) {
-            s_v[w] = bv;
-            s_i[w] = bi;
-        }
-        __syncthreads();
+        block_argmax(s_best, bv, bi);
         if (threadIdx.x == 0) {
-            bv = s_v[0];
-            bi = s_i[0];
-            for (int k = 1; k < CT / 64; k++) {
-                const double v2 = s_v[k];
-                const long long i2 = s_i[k];
-                if (v2 > bv || (v2 == bv && i2 < bi)) {
-                    bv = v2;
-                    bi = i2;
-                }
-            }
             const int64_t o = row * gridDim.x + blockIdx.x;
             if (pv) pv[o] = bv;
             if (pi) pi[o] = (int64_t)bi;

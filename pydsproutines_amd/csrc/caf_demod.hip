@@ -30,58 +30,12 @@ constexpr int DT = 256;                     // threads per row
 constexpr int DEMOD_LDS_SAMPLES = 16384;    // 128 KiB of complex64 per workgroup (+ 1 byte per symbol)
 constexpr int DEMOD_MAX_OSR = 32;
 
+// LDS of the workgroup folds of caf_wave.h: up to three sums through one barrier (a single sum uses the first field), and
+// the (count, flat index) records of the arg max
 struct Red {
-    float f[3][4];
-    uint32_t u[2][4];
+    WaveSlots<DT / 64, float, float, float> f3;
+    WaveSlots<DT / 64, uint32_t, uint32_t> u;
 };
-
-__device__ __forceinline__ void block_sum3(float& a, float& b, float& c, Red& red) {
-    a = wave_sum(a);
-    b = wave_sum(b);
-    c = wave_sum(c);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        red.f[0][w] = a;
-        red.f[1][w] = b;
-        red.f[2][w] = c;
-    }
-    __syncthreads();
-    a = ((red.f[0][0] + red.f[0][1]) + red.f[0][2]) + red.f[0][3];
-    b = ((red.f[1][0] + red.f[1][1]) + red.f[1][2]) + red.f[1][3];
-    c = ((red.f[2][0] + red.f[2][1]) + red.f[2][2]) + red.f[2][3];
-    __syncthreads();
-}
-
-__device__ __forceinline__ float block_sum(float a, Red& red) {
-    a = wave_sum(a);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) red.f[0][w] = a;
-    __syncthreads();
-    a = ((red.f[0][0] + red.f[0][1]) + red.f[0][2]) + red.f[0][3];
-    __syncthreads();
-    return a;
-}
-
-// the largest count wins, the lowest flat index among equals (the tie rule of caf_wave.h)
-__device__ __forceinline__ void block_argmax(uint32_t& cnt, uint32_t& idx, Red& red) {
-    wave_argmax(cnt, idx);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        red.u[0][w] = cnt;
-        red.u[1][w] = idx;
-    }
-    __syncthreads();
-    cnt = red.u[0][0];
-    idx = red.u[1][0];
-    for (int k = 1; k < 4; k++) {
-        const uint32_t c2 = red.u[0][k], i2 = red.u[1][k];
-        if (c2 > cnt || (c2 == cnt && i2 < idx)) {
-            cnt = c2;
-            idx = i2;
-        }
-    }
-    __syncthreads();
-}
 
 // numpy's complex absolute (the formula of k_abs_ampsq in caf_burst.hip): |x| formed here equals a precomputed abs_x bit for bit
 __device__ __forceinline__ float np_abs(float2 z) {
@@ -166,14 +120,14 @@ __device__ void compare_row(const uint8_t* syms, int64_t nsyms, const uint8_t* _
             }
             const uint32_t flat = (uint32_t)(p * SM + i);
             if (matches) matches[flat] = cnt;
-            if (cnt > bc || (cnt == bc && flat < bi)) {
+            if (first_max(bc, bi, cnt, flat)) {
                 bc = cnt;
                 bi = flat;
             }
         }
         off += len;
     }
-    block_argmax(bc, bi, red);
+    block_argmax_all(red.u, bc, bi);
     best_cnt = bc;
     best_idx = bi;
 }
@@ -227,7 +181,7 @@ __device__ void eye_row(const RowCtx& c, const float* __restrict__ absr, float* 
         } else {
             acc = s_acc[ph * DT + threadIdx.x];
         }
-        const float sum = block_sum(acc, red);
+        const float sum = block_sum_all(acc, red.f3.a);
         if (eo_metric && threadIdx.x == 0) eo_metric[ph] = sum;
         if (ph == 0 || sum > bs) {  // the first maximum wins
             bp = ph;
@@ -296,7 +250,7 @@ __device__ void demod_row(const DemodKernelArgs& a, int64_t row, int m, int64_t 
             s01 += p.x * p.y;
             s11 += p.y * p.y;
         }
-        block_sum3(s00, s01, s11, red);
+        block_sum_all(red.f3, s00, s01, s11);
         // S = [s00 s01; s01 s11]: l1,2 = T / 2 +- sqrt(h^2 + s01^2), h = (s00 - s11) / 2.  The leading eigenvector is
         // (l1 - s11, s01) = (h + r, s01); for h < 0 that difference cancels, so its parallel (s01, l1 - s00) = (s01, r - h) is used,
         // with the sign that keeps the first component >= 0 (the sign rule of the closed form).  s01 == 0 and l1 == s11: pi / 2
@@ -318,7 +272,7 @@ __device__ void demod_row(const DemodKernelArgs& a, int64_t row, int m, int64_t 
     } else if (d.lock == CAF_DEMOD_LOCK_NONE) {
         angle = 0.f;
     } else {
-        float sr = 0.f, si = 0.f, z = 0.f;
+        float sr = 0.f, si = 0.f, z = 0.f;  // (z: the record's third field, unused here)
         for (int64_t s = threadIdx.x; s < nsym; s += DT) {
             float2 p = csq(sample_of<LDS>(c, ph, s));
             if (m >= 4) p = csq(p);
@@ -326,7 +280,7 @@ __device__ void demod_row(const DemodKernelArgs& a, int64_t row, int m, int64_t 
             sr += p.x;
             si += p.y;
         }
-        block_sum3(sr, si, z, red);
+        block_sum_all(red.f3, sr, si, z);
         angle = atan2f(si, sr);
         s00 = sr;
         s01 = si;
@@ -485,12 +439,12 @@ __global__ __launch_bounds__(DT) void k_amble_search_bits(const uint8_t* __restr
                     rot = r;
                 }
             const uint32_t flat = (uint32_t)i * 4u + rot;  // (one candidate per search index: its best rotation)
-            if (best > bc || (best == bc && flat < bi)) {
+            if (first_max(bc, bi, best, flat)) {
                 bc = best;
                 bi = flat;
             }
         }
-        block_argmax(bc, bi, red);
+        block_argmax_all(red.u, bc, bi);
         const int idx = (int)(bi >> 2), rot = (int)(bi & 3u);
         if (threadIdx.x == 0) {
             best_matches[row] = (int32_t)bc;

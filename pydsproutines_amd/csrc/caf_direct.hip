@@ -36,7 +36,7 @@ __global__ __launch_bounds__(256) void k_direct_caf(const float2* __restrict__ r
     __shared__ float2 s_c[DIR_FPASS * 65];          // multipliers of the pass: [hypothesis][k] at pitch nk | 1, nk <= 64
     __shared__ float s_t[DIR_ROWS][DIR_TP];         // the pass' values, delay-major
     __shared__ int32_t s_pos[64];
-    __shared__ PeakRec s_w[4];
+    __shared__ WaveSlots<4, float, int32_t, int32_t> s_best;
     const int tid = threadIdx.x;
     const int cg = tid & 3, dp = tid >> 2;  // sub-chunk, delay pair
     const int cp = nk | 1;                  // (odd pitch: the four sub-chunks' reads fall on different banks)
@@ -128,15 +128,15 @@ __global__ __launch_bounds__(256) void k_direct_caf(const float2* __restrict__ r
             }
         }
         // the four sub-chunks of a delay sit in adjacent lanes: highest value, lowest hypothesis on ties (the tie rule of
-        // caf_wave.h, spelled out: the two delays' exchanges are interleaved, two wave_argmax calls compile differently)
+        // caf_wave.h, the exchange spelled out: the two delays' exchanges are interleaved, two wave_argmax calls compile differently)
 #pragma unroll
         for (int o = 1; o <= 2; o <<= 1) {
             float ov = __shfl_xor(bv0, o, 64);
             int32_t oi = __shfl_xor(bi0, o, 64);
-            if (ov > bv0 || (ov == bv0 && oi < bi0)) bv0 = ov, bi0 = oi;
+            if (first_max(bv0, bi0, ov, oi)) bv0 = ov, bi0 = oi;
             ov = __shfl_xor(bv1, o, 64);
             oi = __shfl_xor(bi1, o, 64);
-            if (ov > bv1 || (ov == bv1 && oi < bi1)) bv1 = ov, bi1 = oi;
+            if (first_max(bv1, bi1, ov, oi)) bv1 = ov, bi1 = oi;
         }
         if (cg == 0) {
             if (live0 && row_max) row_max[(int64_t)t * num_shifts + i0] = bv0 < 0.f ? __builtin_nanf("") : bv0;  // (zero-energy window)
@@ -155,17 +155,9 @@ __global__ __launch_bounds__(256) void k_direct_caf(const float2* __restrict__ r
                 b.delay = (int32_t)(shift_start + i1);
                 b.f = bi1;
             }
-            wave_argmax(b.v, b.delay, b.f);
-            __syncthreads();  // (s_w of the previous template has been read)
-            if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = b;
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                for (int wv = 1; wv < 4; ++wv) {
-                    const PeakRec r = s_w[wv];
-                    if (r.v > b.v || (r.v == b.v && r.delay < b.delay)) b = r;
-                }
-                partial[(int64_t)t * partial_per_tmpl + blockIdx.x] = b;
-            }
+            __syncthreads();  // (s_best of the previous template has been read)
+            block_argmax(s_best, b.v, b.delay, b.f);
+            if (threadIdx.x == 0) partial[(int64_t)t * partial_per_tmpl + blockIdx.x] = b;
         }
     }
 }

@@ -170,6 +170,9 @@ constexpr int PEAK_PARTS = 64;  // first-stage slices per template of the two-st
 void launch_peak_reduce(const PeakRec* partial, int64_t count, int64_t stride, int32_t ntmpl, PeakRec* scratch,
                         float* pv, int32_t* pd, int32_t* pf, hipStream_t st);
 void scan_tiles(double* tile_sums, int64_t ntiles, hipStream_t st);
+// in place exclusive scan of int32 or int64 counts by one workgroup, a[n] = the total (caf_rows.hip)
+template <typename T>
+void launch_scan_exclusive(T* a, int64_t n, hipStream_t st);
 
 // caf_rows.hip: the toolbox kernels that more than one translation unit launches
 inline unsigned cdiv(int64_t a, int64_t b) { return (unsigned)((a + b - 1) / b); }

@@ -44,10 +44,7 @@ __global__ __launch_bounds__(1024) void k_scan_tile_sums(double* __restrict__ ti
         }
         const double incl = wave_scan_inclusive(tot, lane);
         __syncthreads();  // (s_carry of the previous chunk is in place; s_wave is free)
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        double run = s_carry + (incl - tot);
-        for (int w = 0; w < wave; ++w) run += s_wave[w];
+        double run = block_carry(s_carry + (incl - tot), incl, lane, wave, s_wave, [](double a, double b) { return a + b; });  // (the carry first: this sum's bits)
 #pragma unroll
         for (int j = 0; j < MAXPER; ++j) {
             if (j < per && i0 + j < ntiles) tile_sums[i0 + j] = run;
@@ -297,7 +294,7 @@ __global__ __launch_bounds__(MUL_THREADS) void k_spectral_mul(const float2* __re
 // writes are MAG_F*4 B contiguous per delay row.
 // ----------------------------------------------------------------------------------------
 // (k_magsq_norm_argmax keeps its own spelling of the tie rule of caf_wave.h: at 256 VGPRs its register allocation
-// changes with every other form of this loop, wave_argmax included)
+// changes with every other form of this loop, wave_argmax and first_max as the predicate included)
 struct Best {
     float v;
     int32_t i;
@@ -460,7 +457,7 @@ __global__ __launch_bounds__(1024) void k_peak_reduce(const PeakRec* __restrict_
                                                       int64_t stride, PeakRec* __restrict__ scratch,
                                                       float* __restrict__ peak_val, int32_t* __restrict__ peak_delay,
                                                       int32_t* __restrict__ peak_freq) {
-    __shared__ PeakRec s_w[16];
+    __shared__ WaveSlots<16, float, int32_t, int32_t> s_best;
     const int t = blockIdx.x;
     const int64_t slice = (per_tmpl + gridDim.y - 1) / gridDim.y;
     const int64_t i0 = (int64_t)blockIdx.y * slice, i1 = min(per_tmpl, i0 + slice);
@@ -471,16 +468,10 @@ __global__ __launch_bounds__(1024) void k_peak_reduce(const PeakRec* __restrict_
     b.f = 0;
     for (int64_t i = i0 + threadIdx.x; i < i1; i += 1024) {
         const PeakRec r = p[i];
-        if (r.v > b.v || (r.v == b.v && r.delay < b.delay)) b = r;
+        if (first_max(b.v, b.delay, r.v, r.delay)) b = r;
     }
-    wave_argmax(b.v, b.delay, b.f);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = b;
-    __syncthreads();
+    block_argmax(s_best, b.v, b.delay, b.f);
     if (threadIdx.x == 0) {
-        for (int w = 1; w < 16; ++w) {
-            const PeakRec r = s_w[w];
-            if (r.v > b.v || (r.v == b.v && r.delay < b.delay)) b = r;
-        }
         if (scratch) {
             scratch[(int64_t)t * gridDim.y + blockIdx.y] = b;
         } else {
@@ -497,7 +488,7 @@ __global__ __launch_bounds__(1024) void k_peak_reduce(const PeakRec* __restrict_
 constexpr int RP_CHUNK = 16384;
 __global__ __launch_bounds__(256) void k_rows_peak(const float* __restrict__ rows, int64_t num_shifts, int64_t shift_start,
                                                    PeakRec* __restrict__ partial, int64_t partial_per_tmpl) {
-    __shared__ PeakRec s_w[4];
+    __shared__ WaveSlots<4, float, int32_t> s_best;
     const int t = blockIdx.y;
     const int64_t i0 = (int64_t)blockIdx.x * RP_CHUNK, i1 = min(num_shifts, i0 + RP_CHUNK);
     const float* r = rows + (int64_t)t * num_shifts;
@@ -512,26 +503,20 @@ __global__ __launch_bounds__(256) void k_rows_peak(const float* __restrict__ row
         const float x[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
         for (int k = 0; k < 4; ++k)
-            if (x[k] > b.v || (x[k] == b.v && (int32_t)(shift_start + i + k) < b.delay)) {
+            if (first_max(b.v, b.delay, x[k], (int32_t)(shift_start + i + k))) {
                 b.v = x[k];
                 b.delay = (int32_t)(shift_start + i + k);
             }
     }
     for (; i < i1; ++i) {  // (at most three values, of one thread)
         const float v = r[i];
-        if (v > b.v || (v == b.v && (int32_t)(shift_start + i) < b.delay)) {
+        if (first_max(b.v, b.delay, v, (int32_t)(shift_start + i))) {
             b.v = v;
             b.delay = (int32_t)(shift_start + i);
         }
     }
-    wave_argmax(b.v, b.delay);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = b;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w)
-            if (s_w[w].v > b.v || (s_w[w].v == b.v && s_w[w].delay < b.delay)) b = s_w[w];
-        partial[(int64_t)t * partial_per_tmpl + blockIdx.x] = b;
-    }
+    block_argmax(s_best, b.v, b.delay);
+    if (threadIdx.x == 0) partial[(int64_t)t * partial_per_tmpl + blockIdx.x] = b;
 }
 
 // ----------------------------------------------------------------------------------------

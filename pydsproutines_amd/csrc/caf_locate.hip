@@ -65,36 +65,12 @@ __device__ __forceinline__ double rsqrt_once(double x) {
     return fma(y0 * e, fma(e, 0.375, 0.5), y0);
 }
 
-__device__ __forceinline__ bool less_first(double v, long long i, double bv, long long bi) { return v < bv || (v == bv && i < bi); }
-
-// the workgroup's (minimum, index) from every thread's: left in thread 0
-__device__ __forceinline__ void group_argmin(double& bv, long long& bi, double* s_v, long long* s_i) {
-    double nv = -bv;
-    wave_argmax(nv, bi);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        s_v[w] = -nv;
-        s_i[w] = bi;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        bv = s_v[0];
-        bi = s_i[0];
-        for (int k = 1; k < LOC_T / 64; k++)
-            if (less_first(s_v[k], s_i[k], bv, bi)) {
-                bv = s_v[k];
-                bi = s_i[k];
-            }
-    }
-}
-
 template <bool TD, bool FD, int SRC>
 __global__ __launch_bounds__(LOC_T) void k_locate(const LocSrc src, int64_t N, const double* __restrict__ rec, int64_t K,
                                                   const int64_t* __restrict__ set_starts, void* __restrict__ cost, int cost_f32,
                                                   double* __restrict__ part_v, int64_t* __restrict__ part_i) {
     __shared__ double s_rec[LOC_C * LOC_REC];
-    __shared__ double s_v[LOC_T / 64];
-    __shared__ long long s_i[LOC_T / 64];
+    __shared__ WaveSlots<LOC_T / 64, double, long long> s_best;
     const int tid = threadIdx.x;
     const int64_t base = (int64_t)blockIdx.x * LOC_P;
     const int set = blockIdx.y;
@@ -204,12 +180,15 @@ __global__ __launch_bounds__(LOC_T) void k_locate(const LocSrc src, int64_t N, c
 #pragma unroll
         for (int j = 0; j < LOC_PPT; j++) {
             const int64_t at = base + tid + j * LOC_T;
-            if (at < N && less_first(acc[j], at, bv, bi)) {
+            if (at < N && first_min(bv, bi, acc[j], (long long)at)) {
                 bv = acc[j];
                 bi = at;
             }
         }
-        group_argmin(bv, bi, s_v, s_i);
+        // the arg min as the arg max of the negated values (first_min and first_max agree on them, signed zeros included)
+        bv = -bv;
+        block_argmax(s_best, bv, bi);
+        bv = -bv;
         if (tid == 0) {
             const int64_t o = (int64_t)set * gridDim.x + blockIdx.x;
             part_v[o] = bv;
@@ -221,20 +200,21 @@ __global__ __launch_bounds__(LOC_T) void k_locate(const LocSrc src, int64_t N, c
 // the partials of set blockIdx.x (in increasing order of index) -> min_val[set], min_idx[set]; nothing but NaN: (NaN, -1)
 __global__ __launch_bounds__(LOC_T) void k_locate_fold(const double* __restrict__ part_v, const int64_t* __restrict__ part_i, int64_t nparts,
                                                        double* __restrict__ min_val, int64_t* __restrict__ min_idx) {
-    __shared__ double s_v[LOC_T / 64];
-    __shared__ long long s_i[LOC_T / 64];
+    __shared__ WaveSlots<LOC_T / 64, double, long long> s_best;
     const int64_t o = (int64_t)blockIdx.x * nparts;
     double bv = INFINITY;
     long long bi = NO_INDEX;
     for (int64_t e = threadIdx.x; e < nparts; e += LOC_T) {
         const double v = part_v[o + e];
         const long long i = (long long)part_i[o + e];
-        if (less_first(v, i, bv, bi)) {
+        if (first_min(bv, bi, v, i)) {
             bv = v;
             bi = i;
         }
     }
-    group_argmin(bv, bi, s_v, s_i);
+    bv = -bv;  // (the arg min as the arg max of the negated values, as in k_locate)
+    block_argmax(s_best, bv, bi);
+    bv = -bv;
     if (threadIdx.x == 0) {
         const bool none = bi == NO_INDEX;
         if (min_val) min_val[blockIdx.x] = none ? (double)NAN : bv;

@@ -292,7 +292,7 @@ __global__ __launch_bounds__(EIG_THREADS) void k_music_eig(const double2* __rest
         for (int j = 0; j < n; j++) {
             const double o = s_norm2[j];
             const bool onan = o != o;
-            const bool ahead = mnan ? (!onan || j < tid) : (!onan && (o > mine || (o == mine && j < tid)));
+            const bool ahead = mnan ? (!onan || j < tid) : (!onan && first_max(mine, tid, o, j));
             rank += ahead ? 1 : 0;
         }
         s_col_of[rank] = tid;

@@ -17,8 +17,7 @@ namespace caf {
 // an all-zero item reports (0, 0, 0) like the reference's zero-initialised workspace.
 __global__ __launch_bounds__(256) void k_argmax3d_u32(const uint32_t* __restrict__ x, int32_t d1, int32_t d2, int32_t d3,
                                                       uint32_t* __restrict__ argmax, uint32_t* __restrict__ maxv) {
-    __shared__ uint32_t s_v[4];
-    __shared__ uint32_t s_i[4];
+    __shared__ WaveSlots<4, uint32_t, uint32_t> s_best;
     const int64_t n = (int64_t)d1 * d2 * d3;
     const uint32_t* xi = x + (int64_t)blockIdx.x * n;
     uint32_t bv = 0, bi = 0;
@@ -29,19 +28,8 @@ __global__ __launch_bounds__(256) void k_argmax3d_u32(const uint32_t* __restrict
             bi = (uint32_t)t;
         }
     }
-    wave_argmax(bv, bi);
-    if ((threadIdx.x & 63) == 0) {
-        s_v[threadIdx.x >> 6] = bv;
-        s_i[threadIdx.x >> 6] = bi;
-    }
-    __syncthreads();
+    block_argmax(s_best, bv, bi);
     if (threadIdx.x == 0) {
-#pragma unroll
-        for (int w = 1; w < 4; ++w)
-            if (s_v[w] > bv || (s_v[w] == bv && s_i[w] < bi)) {
-                bv = s_v[w];
-                bi = s_i[w];
-            }
         argmax[blockIdx.x * 3 + 0] = bi / (uint32_t)(d2 * d3);
         argmax[blockIdx.x * 3 + 1] = (bi / (uint32_t)d3) % (uint32_t)d2;
         argmax[blockIdx.x * 3 + 2] = bi % (uint32_t)d3;
@@ -90,10 +78,7 @@ __global__ __launch_bounds__(MA_THREADS) void k_moving_prefix_write(const float*
         if (base + j < n) tot += (double)x[base + j];
     }
     const double incl = wave_scan_inclusive(tot, lane);
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    double off = incl - tot;
-    for (int w = 0; w < wave; ++w) off += s_wave[w];
+    const double off = block_exclusive(incl, tot, lane, wave, s_wave);
 #pragma unroll
     for (int j = 0; j < MA_PER_THREAD; ++j)
         if (base + j <= n) local[base + j] = off + p[j];
@@ -157,11 +142,8 @@ __global__ __launch_bounds__(MAT_NT) void k_moving_tile(const float* __restrict_
 #pragma unroll
     for (int k = 0; k < MAT_PER; ++k) pl[k] = (tot += (double)v[k]);
     const double incl = wave_scan_inclusive(tot, lane);
-    if (lane == 63) s_wave[wave] = incl;
     if (threadIdx.x == 0) s_p[0] = 0.0;
-    __syncthreads();
-    double off = incl - tot;
-    for (int w = 0; w < wave; ++w) off += s_wave[w];
+    const double off = block_exclusive(incl, tot, lane, wave, s_wave);
 #pragma unroll
     for (int k = 0; k < MAT_PER; ++k) s_p[mat_slot(t0 + k + 1)] = off + pl[k];
     __syncthreads();

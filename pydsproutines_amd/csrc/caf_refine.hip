@@ -75,7 +75,7 @@ __global__ __launch_bounds__(256) void k_mul_conj(const float2* __restrict__ a, 
 
 __global__ __launch_bounds__(256) void k_steer_dot(const float2* __restrict__ vec, const double2* __restrict__ steer,
                                                    int64_t n, double scale, double2* __restrict__ out) {
-    __shared__ double s_re[4], s_im[4];
+    __shared__ WaveSlots<4, double, double> s_sum;
     const double2* row = steer + (int64_t)blockIdx.x * n;
     double re = 0.0, im = 0.0;
     for (int64_t k = threadIdx.x; k < n; k += 256) {
@@ -84,16 +84,8 @@ __global__ __launch_bounds__(256) void k_steer_dot(const float2* __restrict__ ve
         re += (double)v.x * s.x + (double)v.y * s.y;  // v * conj(s)
         im += (double)v.y * s.x - (double)v.x * s.y;
     }
-    re = wave_sum(re);
-    im = wave_sum(im);
-    if ((threadIdx.x & 63) == 0) {
-        s_re[threadIdx.x >> 6] = re;
-        s_im[threadIdx.x >> 6] = im;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0)
-        out[blockIdx.x] = make_double2(scale * (s_re[0] + s_re[1] + s_re[2] + s_re[3]),
-                                       scale * (s_im[0] + s_im[1] + s_im[2] + s_im[3]));
+    block_sum(s_sum, re, im);
+    if (threadIdx.x == 0) out[blockIdx.x] = make_double2(scale * re, scale * im);
 }
 
 // Tone-dot zoom (dotTonesScaling_32f, genTones.cu:165-283; cupyDotTonesScaling, spectralRoutines.py:580-630):

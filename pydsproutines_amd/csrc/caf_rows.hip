@@ -27,6 +27,7 @@ __global__ __launch_bounds__(256) void k_cutout_sumsq(const float2* __restrict__
     e = wave_sum(e);
     if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = e;
     __syncthreads();
+    // (PAIRWISE over the wave totals: block_sum of caf_wave.h adds them in sequence and would change the float64 bits)
     if (threadIdx.x == 0) parts[blockIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);
 }
 __global__ void k_cutout_final(double* __restrict__ parts) {  // parts[NORM_PARTS] = sqrt(sum of the partials), fixed order
@@ -128,8 +129,7 @@ __global__ __launch_bounds__(256) void k_sliding_multiply(const float2* __restri
 __global__ __launch_bounds__(256) void k_rows_argmax(const float2* __restrict__ z, int64_t len, int32_t use_normsq,
                                                      float scale, uint32_t* __restrict__ argmax,
                                                      float* __restrict__ maxv, float* __restrict__ plane, int32_t nan_empty) {
-    __shared__ float s_v[4];
-    __shared__ uint32_t s_i[4];
+    __shared__ WaveSlots<4, float, uint32_t> s_best;
     const int64_t row = blockIdx.x;
     const float2* zr = z + row * len;
     float bv = -1.f;
@@ -143,19 +143,8 @@ __global__ __launch_bounds__(256) void k_rows_argmax(const float2* __restrict__ 
             bi = (uint32_t)t;
         }
     }
-    wave_argmax(bv, bi);
-    if ((threadIdx.x & 63) == 0) {
-        s_v[threadIdx.x >> 6] = bv;
-        s_i[threadIdx.x >> 6] = bi;
-    }
-    __syncthreads();
+    block_argmax(s_best, bv, bi);
     if (threadIdx.x == 0) {
-#pragma unroll
-        for (int w = 1; w < 4; ++w)
-            if (s_v[w] > bv || (s_v[w] == bv && s_i[w] < bi)) {
-                bv = s_v[w];
-                bi = s_i[w];
-            }
         if (bv < 0.f) {  // empty or all-NaN row: the reference's zero-initialised workspace (argmax.cu:108-109)
             bv = (nan_empty && len > 0) ? __builtin_nanf("") : 0.f;
             bi = 0;
@@ -231,13 +220,8 @@ __global__ __launch_bounds__(256) void k_rows_argmax_part(const float2* __restri
         }
     }
     unsigned long long key = bv < 0.f ? 0ull : (((unsigned long long)__float_as_uint(bv)) << 32) | (0xFFFFFFFFu - bi);
-    key = wave_max(key);
-    if ((threadIdx.x & 63) == 0) s_k[threadIdx.x >> 6] = key;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w) key = s_k[w] > key ? s_k[w] : key;
-        part[row * gridDim.x + c] = key;
-    }
+    key = block_max(key, s_k);
+    if (threadIdx.x == 0) part[row * gridDim.x + c] = key;
 }
 __global__ __launch_bounds__(64) void k_rows_argmax_fin(const unsigned long long* __restrict__ part, int32_t chunks,
                                                         int64_t rows, int32_t use_normsq, uint32_t* __restrict__ argmax,
@@ -269,7 +253,7 @@ template <bool ALIGNED>
 __global__ __launch_bounds__(LM_NT) void k_local_max_flags(const float* __restrict__ x, int64_t n, float min_height,
                                                            uint16_t* __restrict__ masks, int32_t* __restrict__ tile_count) {
     __shared__ int32_t s_w[LM_NT / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
     const int64_t base = (int64_t)blockIdx.x * LM_TILE + (int64_t)threadIdx.x * LM_PER;
     float v[LM_PER];
     if (ALIGNED && base + LM_PER <= n) {
@@ -292,39 +276,37 @@ __global__ __launch_bounds__(LM_NT) void k_local_max_flags(const float* __restri
         if (base + j < n && v[j] > min_height && v[j] > l && v[j] > r) mask |= 1u << j;
     }
     masks[(int64_t)blockIdx.x * LM_NT + threadIdx.x] = (uint16_t)mask;
-    const int c = wave_sum(__popc(mask));
-    if (lane == 0) s_w[wave] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int t = 0;
-#pragma unroll
-        for (int w = 0; w < LM_NT / 64; ++w) t += s_w[w];
-        tile_count[blockIdx.x] = t;
-    }
+    const int t = block_sum((int32_t)__popc(mask), s_w);
+    if (threadIdx.x == 0) tile_count[blockIdx.x] = t;
 }
 
-// in place: tile_count[t] -> number of maxima before tile t; tile_count[ntiles] = the total (many tiles only)
-__global__ __launch_bounds__(1024) void k_local_max_scan(int32_t* __restrict__ tile_count, int64_t ntiles) {
-    __shared__ int32_t s_wave[16];
-    __shared__ int32_t s_base;
+// In place exclusive scan by one workgroup of 1024, a[n] = the total: the tile counts of the compactions (the local
+// maxima here, the edges, the wavelet-matrix levels and the runs of caf_burst.hip).
+template <typename T>
+__global__ __launch_bounds__(1024) void k_scan_exclusive(T* __restrict__ a, int64_t n) {
+    __shared__ T s_wave[16];
+    __shared__ T s_base;
     if (threadIdx.x == 0) s_base = 0;
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int64_t c0 = 0; c0 < ntiles; c0 += 1024) {
+    for (int64_t c0 = 0; c0 < n; c0 += 1024) {
         const int64_t t = c0 + threadIdx.x;
-        const int v = t < ntiles ? tile_count[t] : 0;
-        const int incl = wave_scan_inclusive(v, lane);
-        if (lane == 63) s_wave[wave] = incl;
+        const T v = t < n ? a[t] : 0;
+        const T incl = wave_scan_inclusive(v, lane);
+        const T off = s_base + block_exclusive(incl, v, lane, wave, s_wave);
+        if (t < n) a[t] = off;
         __syncthreads();
-        int off = s_base;
-        for (int w = 0; w < wave; ++w) off += s_wave[w];
-        if (t < ntiles) tile_count[t] = off + incl - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) s_base = off + incl;
+        if (threadIdx.x == 1023) s_base = off + v;
         __syncthreads();
     }
-    if (threadIdx.x == 0) tile_count[ntiles] = s_base;
+    if (threadIdx.x == 0) a[n] = s_base;
 }
+template <typename T>
+void launch_scan_exclusive(T* a, int64_t n, hipStream_t st) {
+    hipLaunchKernelGGL(k_scan_exclusive<T>, dim3(1), dim3(1024), 0, st, a, n);
+}
+template void launch_scan_exclusive<int32_t>(int32_t*, int64_t, hipStream_t);
+template void launch_scan_exclusive<int64_t>(int64_t*, int64_t, hipStream_t);
 
 __global__ __launch_bounds__(LM_NT) void k_local_max_write(const uint16_t* __restrict__ masks, const int32_t* __restrict__ tile_count,
                                                            int32_t scanned, int32_t max_out, int32_t* __restrict__ idx,
@@ -344,13 +326,8 @@ __global__ __launch_bounds__(LM_NT) void k_local_max_write(const uint16_t* __res
         if (mine == 0 && !last) return;  // (uniform)
         int c = 0;
         for (int t = threadIdx.x; t < (int)blockIdx.x; t += LM_NT) c += tile_count[t];
-        c = wave_sum(c);
-        if (lane == 0) s_w[wave] = c;
-        __syncthreads();
+        const int t = block_sum(c, s_w);
         if (threadIdx.x == 0) {
-            int t = 0;
-#pragma unroll
-            for (int w = 0; w < LM_NT / 64; ++w) t += s_w[w];
             s_before = t;
             if (last) *count = t + mine;
         }
@@ -362,10 +339,7 @@ __global__ __launch_bounds__(LM_NT) void k_local_max_write(const uint16_t* __res
     uint32_t mask = masks[(int64_t)blockIdx.x * LM_NT + threadIdx.x];
     const int c = __popc(mask);
     const int incl = wave_scan_inclusive(c, lane);
-    if (lane == 63) s_w[wave] = incl;
-    __syncthreads();
-    int off = before + (incl - c);
-    for (int w = 0; w < wave; ++w) off += s_w[w];
+    int off = before + block_exclusive(incl, c, lane, wave, s_w);
     const int64_t base = (int64_t)blockIdx.x * LM_TILE + (int64_t)threadIdx.x * LM_PER;
     while (mask) {
         const int j = __ffs(mask) - 1;
@@ -492,7 +466,7 @@ void launch_find_local_maxima(const float* x, int64_t n, float min_height, int32
         hipLaunchKernelGGL(k_local_max_flags<false>, dim3((unsigned)ntiles), dim3(LM_NT), 0, st, x, n, min_height, masks,
                            tile_scratch);
     const int scanned = ntiles > LM_DIRECT_TILES;
-    if (scanned) hipLaunchKernelGGL(k_local_max_scan, dim3(1), dim3(1024), 0, st, tile_scratch, ntiles);
+    if (scanned) launch_scan_exclusive(tile_scratch, ntiles, st);
     hipLaunchKernelGGL(k_local_max_write, dim3((unsigned)ntiles), dim3(LM_NT), 0, st, masks, tile_scratch, scanned, max_out, idx,
                        count);
 }

@@ -19,8 +19,7 @@ __global__ __launch_bounds__(1024) void k_zoom_topk(const float* __restrict__ tr
                                                     const int32_t* __restrict__ cand_count, int32_t max_cand, int32_t k,
                                                     float* __restrict__ vals, int32_t* __restrict__ sel,
                                                     int32_t* __restrict__ sel_count) {
-    __shared__ float s_v[16];
-    __shared__ int32_t s_i[16];
+    __shared__ WaveSlots<16, float, int32_t> s_best;
     __shared__ int32_t s_win;
     const int tid = threadIdx.x;
     const int cnt = min(*cand_count, max_cand);
@@ -37,18 +36,8 @@ __global__ __launch_bounds__(1024) void k_zoom_topk(const float* __restrict__ tr
                 bi = i;
             }
         }
-        wave_argmax(bv, bi);
-        if ((tid & 63) == 0) {
-            s_v[tid >> 6] = bv;
-            s_i[tid >> 6] = bi;
-        }
-        __syncthreads();
+        block_argmax(s_best, bv, bi);
         if (tid == 0) {
-            for (int w = 1; w < 16; ++w)
-                if (s_v[w] > bv || (s_v[w] == bv && s_i[w] < bi)) {
-                    bv = s_v[w];
-                    bi = s_i[w];
-                }
             s_win = (bi != 0x7fffffff && bv > -INFINITY) ? bi : -1;
             if (s_win >= 0) {
                 sel[r] = cand[s_win];
@@ -84,10 +73,7 @@ __global__ __launch_bounds__(256) void k_zoom_rows(const float2* __restrict__ rx
         const float2 a = w[t];
         e += (double)a.x * a.x + (double)a.y * a.y;
     }
-    e = wave_sum(e);
-    if ((threadIdx.x & 63) == 0) s_e[threadIdx.x >> 6] = e;
-    __syncthreads();
-    e = s_e[0] + s_e[1] + s_e[2] + s_e[3];
+    e = block_sum_all(e, s_e);
     // 1 / (||window|| ||u||): the normalisation of multiplySlidesNormalised (multiplySlices.cu:190-211)
     const float inv = (float)(sqrt((double)tscale_t[0]) / sqrt(e));
     const double f0 = nu[row_arg[rel]];
