@@ -53,7 +53,9 @@ CAF_EXPORT int32_t caf_device_info(int32_t device, char* name, int32_t name_len,
 /* caf_malloc / caf_free go through a caching allocator (the counterpart of cupy's default memory pool, which
  * every cp.empty / cp.zeros of the reference's wrappers hits): freed blocks are kept and reused in stream order;
  * CAF_POOL_MB bounds the cached bytes (default 8192, 0 = plain hipMalloc / hipFree).  caf_pool_trim returns the
- * cache to the driver (cp.get_default_memory_pool().free_all_blocks()). */
+ * cache to the driver (cp.get_default_memory_pool().free_all_blocks()).  CAF_POOL_POISON=<32-bit hex word> (diagnostic,
+ * read on every allocation; unset, empty or 0 = off) fills every block handed out, reused or fresh, with that word
+ * before the allocation returns: outputs and scratch then never start from what an earlier call left in the block. */
 CAF_EXPORT int32_t caf_malloc(void** d_ptr, int64_t bytes);
 CAF_EXPORT int32_t caf_free(void* d_ptr);
 CAF_EXPORT int32_t caf_pool_trim(void);

@@ -7,7 +7,12 @@
 // again by later work, so callers that stay on one stream (the host layer uses the null stream) need no
 // synchronisation; callers mixing streams synchronise before freeing, as with any stream-ordered pool.
 //
-//   CAF_POOL_MB   upper bound of cached (free) bytes per process, default 8192; 0 disables caching.
+//   CAF_POOL_MB       upper bound of cached (free) bytes per process, default 8192; 0 disables caching.
+//   CAF_POOL_POISON   diagnostic, read on every pool_alloc: a 32-bit word in hex (unset, empty or 0 = off).  When on, the
+//                     whole rounded block is filled with the word before pool_alloc returns, on a pool hit and on a fresh
+//                     hipMalloc alike, between two device synchronisations (so for users on any stream).  A kernel that
+//                     reads scratch before writing it, or leaves part of an output unwritten, then shows the word instead
+//                     of what the block's previous user left there (tests/test_gpu_pool_poison.py).
 #include <cstdlib>
 #include <map>
 #include <mutex>
@@ -51,6 +56,12 @@ int64_t round_size(int64_t bytes) {
         return r;
     }
     return (bytes + ((int64_t)1 << 20) - 1) & ~(((int64_t)1 << 20) - 1);
+}
+
+// CAF_POOL_POISON as a word; 0 = off
+uint32_t poison_word() {
+    const char* e = std::getenv("CAF_POOL_POISON");
+    return e && *e ? (uint32_t)std::strtoul(e, nullptr, 16) : 0u;
 }
 
 // caller holds g_mu; hipFree of every cached block of `dev` (or of all devices when dev < 0)
@@ -97,6 +108,11 @@ int pool_alloc(void** out, int64_t bytes) {
     g_live[p] = Live{r, dev};
     g_in_use += r;
     *out = p;
+    if (const uint32_t w = poison_word()) {  // (r is a multiple of 512)
+        CAF_HIP_TRY(hipDeviceSynchronize());  // the block's previous user may still run on another stream
+        CAF_HIP_TRY(hipMemsetD32((hipDeviceptr_t)p, (int)w, (size_t)(r / 4)));
+        CAF_HIP_TRY(hipDeviceSynchronize());
+    }
     return CAF_OK;
 }
 
