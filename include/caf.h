@@ -772,6 +772,43 @@ CAF_EXPORT int32_t caf_cancel_subtract(const float* d_sigs, int32_t B, int32_t n
                                        const int32_t* d_idx, const double* d_nu, const double* d_rate, const double* d_amp,
                                        float* d_out, void* stream);
 
+/* ---- The matrix profile of one record (matrixProfileRoutines.py: MatrixProfile, CupyMatrixProfile).  Added after ABI 1.10
+ * without a version bump, detected by symbol (csrc/caf_mprofile.hip).  d_x holds n complex64 samples, 2 <= n < 2^31; for the
+ * window w (1 <= w <= max_window, w < n) there are M = n - w + 1 window positions, and diagonal k (1 <= k <= M - 1) holds the
+ * M - k values
+ *   v(i, k) = |sum_{t < w} x[i + t] conj(x[i + k + t])|^2 / (E[i] E[i + k]),  E[i] = sum_{t < w} |x[i + t]|^2,  0 <= i < M - k.
+ * Products, their running prefix, the energies and the quotient are float64 in a fixed order, the value is rounded once to
+ * float32; a value is NaN where one of its two energies is zero.  Every call below computes the same bits for the same
+ * (x, w, i, k), whatever diagonals it is asked for, and repeats them on every run.  Anything outside the limits is
+ * CAF_ERR_INVALID; nothing is clamped. */
+/* segment: window positions per work item; chunk: diagonals per work item; max_window: the longest w.  With n, w (and the
+ * number of diagonals of a chains call) also the sizes that follow from them, 0 where n or w is out of range:
+ * products_per_thread (the run of products a thread adds up before the workgroup's scan), the bytes of pooled scratch a
+ * call takes (energies; energies + run counts + offsets of a chains call; energies + keys of a profile call) and the bytes
+ * of LDS of a work item.  Every output is optional (NULL). */
+CAF_EXPORT int32_t caf_mp_geometry(int64_t n, int32_t w, int64_t num_diagonals, int32_t* segment, int32_t* chunk,
+                                   int32_t* max_window, int32_t* products_per_thread, int64_t* energy_bytes,
+                                   int64_t* chains_bytes, int64_t* profile_bytes, int64_t* lds_bytes);
+/* The diagonals k0 <= k < k1 (1 <= k0 < k1 <= M), packed one after the other: value (i, k) at
+ * d_out[(k - k0) M - (k0 + k - 1) (k - k0) / 2 + i], an int64 offset; sum_{k0 <= k < k1} (M - k) floats in all. */
+CAF_EXPORT int32_t caf_mp_raw(const float* d_x, int64_t n, int32_t w, int32_t k0, int32_t k1, float* d_out, void* stream);
+/* The runs of v > min_threshold (compared as float32; NaN is never above) on the diagonals k0 <= k < k1, or, with d_diagonals
+ * != NULL, on its num_diagonals diagonals (int32, strictly increasing, each within 1 .. M - 1; k0 and k1 are then not read;
+ * the list is downloaded and checked first, so the call blocks until earlier work on `stream` that wrote it has finished).
+ * A run is (k, start, end), end exclusive, cut at the multiples of `segment`: runs that meet there (the same k, one's end
+ * the other's start) are one chain, and joining them is left to the caller.  *h_total (host memory) receives the number of
+ * runs, complete on return; the first min(*h_total, capacity) runs in (k, start) order are written to d_runs (capacity, 3)
+ * int32.  capacity == 0 counts only (d_runs may be NULL).  The list is the same on every run. */
+CAF_EXPORT int32_t caf_mp_chains(const float* d_x, int64_t n, int32_t w, int32_t k0, int32_t k1, const int32_t* d_diagonals,
+                                 int32_t num_diagonals, float min_threshold, int64_t capacity, int32_t* d_runs, int64_t* h_total,
+                                 void* stream);
+/* For every window position p < M the largest v over its partners q = p - k and q = p + k, kmin <= k <= kmax, 0 <= q < M
+ * (1 <= kmin, kmax <= M - 1; kmin > kmax is an empty range): d_value (M) float32 and d_index (M) int32 = q.  Of equal values
+ * the smallest k wins, and of equal k the left partner q = p - k.  NaN is never chosen; a position with no partner in range,
+ * or with NaN for every partner, gets value 0 and index -1.  No diagonal is written anywhere. */
+CAF_EXPORT int32_t caf_mp_profile(const float* d_x, int64_t n, int32_t w, int32_t kmin, int32_t kmax, float* d_value,
+                                  int32_t* d_index, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

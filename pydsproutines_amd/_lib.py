@@ -339,6 +339,10 @@ _SIGNATURES = {
                           _P, _P],
     "caf_cancel_estimate": [_P, _I32, _I32, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "caf_cancel_subtract": [_P, _I32, _I32, _P, _I64, _P, _P, _P, _P, _P, _P],
+    "caf_mp_geometry": [_I64, _I32, _I64] + [ct.POINTER(_I32)] * 4 + [ct.POINTER(_I64)] * 4,
+    "caf_mp_raw": [_P, _I64, _I32, _I32, _I32, _P, _P],
+    "caf_mp_chains": [_P, _I64, _I32, _I32, _I32, _P, _I32, ct.c_float, _I64, _P, ct.POINTER(_I64), _P],
+    "caf_mp_profile": [_P, _I64, _I32, _I32, _I32, _P, _P, _P],
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
