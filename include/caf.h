@@ -809,6 +809,34 @@ CAF_EXPORT int32_t caf_mp_chains(const float* d_x, int64_t n, int32_t w, int32_t
 CAF_EXPORT int32_t caf_mp_profile(const float* d_x, int64_t n, int32_t w, int32_t kmin, int32_t kmax, float* d_value,
                                   int32_t* d_index, void* stream);
 
+/* ---- cyclic-moment line search for batches of bursts (cyclostationaryRoutines.py: PSKOrderDetector, estimateOffsetViaCM,
+ *      estimateBaud; caf_cyclo.hip) -------------------------------------------------------------------------------------
+ * d_x: (rows, pitch) complex64.  d_lengths: int32 per row, or NULL (every row has `pitch` samples); row r uses its first
+ * L_r <= min(pitch, nfft) samples and the transform is zero-padded to nfft.  moments / band_lo / band_hi are HOST arrays of
+ * num_moments (1 .. 5) entries.  moments[k] selects the sequence that is transformed:
+ *   0: z = |x| - mean(|x|)     1: z = |x|^2 - mean(|x|^2)     2, 4, 8: z = x^m by repeated complex squaring,
+ * the mean over the row's own L_r samples (float64, in a fixed order), so that zero-padding does not spread a DC term.
+ * The band of moment k is the signed bins band_lo[k] .. band_hi[k], inclusive, -nfft/2 <= lo <= hi <= (nfft - 1)/2, i.e. the
+ * FFT-order indices b mod nfft.  Per (row, moment), at [row * num_moments + k]:
+ *   d_index (int32)       FFT-order index of the largest |Z|^2 in the band, the lower index of equal values
+ *   d_peak  (float64)     |Z[index]|
+ *   d_side  (2 float64)   |Z[index - 1]|, |Z[index + 1]|, circular, in the band or not
+ *   d_power (float64)     sum of |Z|^2 over the band
+ * d_peak, d_side and d_power may be NULL.  A row of L_r = 0, a row of zeros and a sequence z of zeros give index -1 and zeros.
+ * Every row is scaled by an exact power of two before it is raised (x^8 stays inside float32 at any level) and the outputs are
+ * scaled back in float64.  A non-finite sample makes its own row's results unspecified and nothing else.  A row's results are
+ * the same bits alone, in any batch and at any place in it.
+ * nfft a power of two within 64 .. 16384: one launch, the spectra never leave the LDS; no scratch, asynchronous on `stream`
+ * unless d_lengths is given (it is downloaded and checked first).  Any other nfft: elementwise kernel, rocFFT rows and a line
+ * kernel per moment over pooled scratch.  CAF_CYCLO_DEBUG=1 names the form on stderr (`cm_lds nfft=... rows/wg=...` or
+ * `cm_rocfft nfft=...`). */
+CAF_EXPORT int32_t caf_cm_lines(const float* d_x, int64_t rows, int64_t pitch, const int32_t* d_lengths, int64_t nfft,
+                                const int32_t* moments, int32_t num_moments, const int32_t* band_lo, const int32_t* band_hi,
+                                int32_t* d_index, double* d_peak, double* d_side, double* d_power, void* stream);
+/* form: 1 the in-LDS kernel, 2 the composed form, 0 nfft out of range; threads per workgroup, rows per workgroup and the
+ * bytes of dynamic LDS of a workgroup.  Every output is optional (NULL).  No device work. */
+CAF_EXPORT int32_t caf_cm_geometry(int64_t nfft, int32_t* form, int32_t* threads, int32_t* rows_per_wg, int64_t* lds_bytes);
+
 #ifdef __cplusplus
 }
 #endif

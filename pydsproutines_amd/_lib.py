@@ -343,6 +343,8 @@ _SIGNATURES = {
     "caf_mp_raw": [_P, _I64, _I32, _I32, _I32, _P, _P],
     "caf_mp_chains": [_P, _I64, _I32, _I32, _I32, _P, _I32, ct.c_float, _I64, _P, ct.POINTER(_I64), _P],
     "caf_mp_profile": [_P, _I64, _I32, _I32, _I32, _P, _P, _P],
+    "caf_cm_geometry": [_I64] + [ct.POINTER(_I32)] * 3 + [ct.POINTER(_I64)],
+    "caf_cm_lines": [_P, _I64, _I64, _P, _I64, ct.POINTER(_I32), _I32, ct.POINTER(_I32), ct.POINTER(_I32), _P, _P, _P, _P, _P],
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
