@@ -837,6 +837,62 @@ CAF_EXPORT int32_t caf_cm_lines(const float* d_x, int64_t rows, int64_t pitch, c
  * bytes of dynamic LDS of a workgroup.  Every output is optional (NULL).  No device work. */
 CAF_EXPORT int32_t caf_cm_geometry(int64_t nfft, int32_t* form, int32_t* threads, int32_t* rows_per_wg, int64_t* lds_bytes);
 
+/* ---- batched k-means and cluster scores (clusterRoutines.py: ClusterEngine, ClusterEngine2D, AngularClusterEngine;
+ *      caf_cluster.hip) ---------------------------------------------------------------------------------------------------
+ * Everything is float64.  d_x: (P, pitch, D) row-major, P problems of up to `pitch` points in D dimensions.  d_lengths:
+ * int32 per problem, or NULL (every problem has `pitch` points; a length is clamped to 0 .. pitch).  d_mask: uint8 (P, pitch)
+ * or NULL; a point is USED when it lies below its problem's length and its mask byte is not 0.  A JOB is one (problem, k)
+ * pair: job_problem and job_k are HOST arrays of J int32 (checked before anything touches a device: 0 <= problem < P,
+ * 1 <= k <= kmax), a restart is one more job.  Per-job arrays have a pitch of kmax: centres (J, kmax, D), counts (J, kmax).
+ * Limits: 1 <= D <= 4, 1 <= kmax <= 32, 1 <= pitch <= 2^17, 1 <= J < 2^22.  Every violation returns CAF_ERR_INVALID with a
+ * caf_last_error() text and no device work.  No atomics; every sum has a fixed order (the used points numbered in index
+ * order, a thread taking numbers t, t + 256, ... in increasing order, lanes by xor butterfly, waves, clusters and tiles in
+ * increasing order), and a job's outputs are a function of its own used points, k and centres (variates): not of J, its place
+ * among the jobs, the run, the pool, the pitch, or of whether unused points are masked or absent.
+ *
+ * caf_kmeans_seed: k-means++ (D^2 sampling, one trial per step) from the caller's variates d_u (J, kmax) in [0, 1).  The
+ * first centre is used point number floor(u_0 n_used) in index order.  For centre j >= 1: D2_i the squared distance of used
+ * point i to the nearest centre chosen so far, P_i its running sum in index order (a workgroup scan per tile of 256 on top of
+ * the tiles before), t = u_j P_last; chosen is the first used point with P_i > t and D2_i > 0 -- where rounding leaves none
+ * the last used point with D2_i > 0, and where every used point coincides with a centre the last used point.  Outputs:
+ * d_index (J, kmax) int32 point indices and d_centres (J, kmax, D), entries 0 .. k - 1 of a job.  A job with fewer used
+ * points than k gets indices -1 and no centres. */
+CAF_EXPORT int32_t caf_kmeans_seed(const double* d_x, int64_t P, int64_t pitch, int32_t D, const int32_t* d_lengths,
+                                   const uint8_t* d_mask, const int32_t* job_problem, const int32_t* job_k, int64_t J, int32_t kmax,
+                                   const double* d_u, int32_t* d_index, double* d_centres, void* stream);
+/* Lloyd's iteration from d_centres (in and out), one workgroup per job, wholly on the device.  Assignment: the centre with the
+ * smallest sum_d (x_d - c_d)^2, formed directly, the lower index of equal values.  Update: the mean of the members; an empty
+ * cluster keeps its centre.  The job ends when an assignment repeats the labels before it (converged), or with the
+ * assignment that follows update number max_iter (>= 1); either way the labels are the assignment to the centres returned.
+ * Outputs: d_labels (J, pitch) int32, -1 for points not used, nothing written from the problem's length on; d_counts
+ * (J, kmax) int32 and d_centres, entries 0 .. k - 1; d_inertia (J), the sum over used points of the squared distance to
+ * their centre; d_n_iter (J), the updates done; d_status (J):
+ *   0 converged   1 fewer used points than k: labels -1 and nothing else written   2 converged with an empty cluster
+ *   3 max_iter updates done and the labels still changed (takes precedence over 2)
+ * Form 1 keeps the problem's points in LDS (pitch * D * 8 <= 131072), form 2 reads them through L2 in every pass; the
+ * arithmetic and its order are the same.  A single job is one workgroup however many points it has. */
+CAF_EXPORT int32_t caf_kmeans_lloyd(const double* d_x, int64_t P, int64_t pitch, int32_t D, const int32_t* d_lengths,
+                                    const uint8_t* d_mask, const int32_t* job_problem, const int32_t* job_k, int64_t J, int32_t kmax,
+                                    int32_t max_iter, double* d_centres, int32_t* d_labels, int32_t* d_counts, double* d_inertia,
+                                    int32_t* d_n_iter, int32_t* d_status, void* stream);
+/* Scores of a labelling, from d_labels (label_rows, pitch) alone.  job_rows: HOST array of J int32, the row of d_labels that
+ * holds a job's labels (so that the winners among restarts are scored where they lie), or NULL: row = job, label_rows is
+ * ignored.  A point counts when it lies below its problem's length and its label
+ * is within 0 .. k - 1; centroids are the label means.  `which` is a mask: 1 the mean silhouette (Euclidean distances formed
+ * directly; a member of a singleton cluster scores 0), 2 Davies-Bouldin, 4 Calinski-Harabasz (1 when the within-cluster
+ * dispersion is 0); the outputs d_sil, d_db, d_ch are (J) and required when selected.  d_sil_points (J, pitch), optional with
+ * the silhouette: s(i) per counted point, NaN for the others below the length.  A job with fewer than 2 non-empty clusters,
+ * or with as many non-empty clusters as points, gets NaN. */
+CAF_EXPORT int32_t caf_cluster_scores(const double* d_x, int64_t P, int64_t pitch, int32_t D, const int32_t* d_lengths,
+                                      const int32_t* job_problem, const int32_t* job_k, int64_t J, int32_t kmax,
+                                      const int32_t* d_labels, const int32_t* job_rows, int64_t label_rows, uint32_t which,
+                                      double* d_sil, double* d_db, double* d_ch, double* d_sil_points, void* stream);
+/* form: 1 Lloyd with the points in LDS, 2 through L2, 0 arguments out of range; threads per workgroup; points per tile T of the
+ * seeding scans and the silhouette; dynamic LDS bytes of a Lloyd workgroup and of a silhouette workgroup; pooled scratch bytes
+ * per job.  Every output is optional (NULL).  No device work. */
+CAF_EXPORT int32_t caf_cluster_geometry(int64_t pitch, int32_t D, int32_t kmax, int32_t* form, int32_t* threads, int32_t* tile,
+                                        int64_t* lloyd_lds_bytes, int64_t* sil_lds_bytes, int64_t* scratch_bytes);
+
 #ifdef __cplusplus
 }
 #endif

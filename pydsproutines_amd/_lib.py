@@ -345,6 +345,10 @@ _SIGNATURES = {
     "caf_mp_profile": [_P, _I64, _I32, _I32, _I32, _P, _P, _P],
     "caf_cm_geometry": [_I64] + [ct.POINTER(_I32)] * 3 + [ct.POINTER(_I64)],
     "caf_cm_lines": [_P, _I64, _I64, _P, _I64, ct.POINTER(_I32), _I32, ct.POINTER(_I32), ct.POINTER(_I32), _P, _P, _P, _P, _P],
+    "caf_cluster_geometry": [_I64, _I32, _I32] + [ct.POINTER(_I32)] * 3 + [ct.POINTER(_I64)] * 3,
+    "caf_kmeans_seed": [_P, _I64, _I64, _I32, _P, _P, ct.POINTER(_I32), ct.POINTER(_I32), _I64, _I32, _P, _P, _P, _P],
+    "caf_kmeans_lloyd": [_P, _I64, _I64, _I32, _P, _P, ct.POINTER(_I32), ct.POINTER(_I32), _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P],
+    "caf_cluster_scores": [_P, _I64, _I64, _I32, _P, ct.POINTER(_I32), ct.POINTER(_I32), _I64, _I32, _P, ct.POINTER(_I32), _I64, ct.c_uint32, _P, _P, _P, _P, _P],
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
