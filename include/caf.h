@@ -18,6 +18,11 @@
  * pointers on the current HIP device.  `stream` is a hipStream_t passed as void*
  * (NULL = the default stream).  Calls with d_ pointers are asynchronous on `stream`
  * unless stated otherwise; *_host entry points are blocking.
+ *
+ * Placement: every pointer is aligned to its element type (4 bytes for float32 / int32, 8 for a complex64 or float64 element,
+ * 16 for complex128, 2 for int16, 1 for bytes) and nothing more is required unless the entry point says so; a view into a
+ * larger array is as good as an allocation of its own.  Results do not depend on where the arrays lie.  Nothing is written
+ * outside the outputs, and an argument is read-only unless its entry point says that it is written.
  */
 #ifndef CAF_H_
 #define CAF_H_
@@ -179,7 +184,7 @@ typedef struct caf_outputs {
                            /* fastXcorr(absResult=False) (:533-548)                                    */
 } caf_outputs;
 
-/* d_rx: device complex64 [rx_len].  Requires shift_start >= 0 and
+/* d_rx: device complex64 [rx_len], 8-byte aligned (a whole sample; CAF_ERR_INVALID otherwise).  Requires shift_start >= 0 and
  * shift_start + num_shifts - 1 + N <= rx_len <= max_rx_len.  Asynchronous on `stream`.
  * The plan belongs to the device that was current at caf_plan_create (the same must be current here) and owns
  * its workspace: executions of ONE plan must be ordered (same stream, or synchronised by the caller); different
@@ -292,7 +297,8 @@ CAF_EXPORT int32_t caf_complex_moving_sum(const float* d_x, int64_t n, int32_t s
 CAF_EXPORT int32_t caf_copy_slices_to_matrix(const float* d_x, int64_t xlen, const int32_t* d_starts,
                                              int32_t starts_stride, int64_t start0, int64_t increment, int32_t len,
                                              int64_t rows, float* d_out, void* stream);
-/* copy_groups_kernel32fc (cupyExtensions.py:17-38) */
+/* copy_groups_kernel32fc (cupyExtensions.py:17-38): d_y[d_y_starts[g] : + d_lengths[g]] = d_x[d_x_starts[g] : + d_lengths[g]] for
+ * every group g; d_y is written there and keeps what it held everywhere else */
 CAF_EXPORT int32_t caf_copy_groups(const float* d_x, float* d_y, const int32_t* d_x_starts, const int32_t* d_y_starts,
                                    const int32_t* d_lengths, int32_t num_groups, void* stream);
 /* findLocalMaxima (peakfinding.cu:14-58): indices in ASCENDING order (deterministic), *d_count = total found */
@@ -417,13 +423,15 @@ CAF_EXPORT int32_t caf_argmax3d_u32(const uint32_t* d_x, int64_t num_items, int3
                                     uint32_t* d_argmax, uint32_t* d_max, void* stream);
 /* IQ ingest: interleaved int16 I/Q -> complex64 * scale on the device, i.e. the
  * np.fromfile(int16).astype(float32).view(complex64) of usrpRoutines.simpleBinRead (usrpRoutines.py:51-67)
- * done after the (half-size) H2D copy as in benchmarks/benchmark_cupyCopyAndConvert.py:17-25 */
+ * done after the (half-size) H2D copy as in benchmarks/benchmark_cupyCopyAndConvert.py:17-25.
+ * d_iq must be 8-byte and d_out 16-byte aligned (two samples a load, two a store; CAF_ERR_INVALID otherwise). */
 CAF_EXPORT int32_t caf_iq16_to_c64(const int16_t* d_iq, int64_t num_samples, float scale, float* d_out, void* stream);
 /* Front-end filter/decimate fused into the rx load: one kernel that is
  *   caf_iq16_to_c64 -> filter_smtaps(dsr, dsPhase)   (usrpRoutines.py:51-67 + filter.cu:9-58, filterRoutines.py:417-501)
  * i.e. d_out[o] = lfilter(taps, 1, scale * iq)[ds_phase + o*dsr] as complex64, reading the raw int16 pairs (4 B per
  * input sample) and computing only the kept outputs.  d_delay = the delay_len int16 IQ pairs that precede d_iq
- * (streaming state: the tail of the previous chunk), NULL/0 for zeros.  num_taps <= 2048, dsr <= 16. */
+ * (streaming state: the tail of the previous chunk), NULL/0 for zeros.  num_taps <= 2048, dsr <= 16.
+ * d_iq and d_delay must be 4-byte aligned (a whole IQ pair; CAF_ERR_INVALID otherwise). */
 CAF_EXPORT int32_t caf_iq16_fir_decimate(const int16_t* d_iq, int64_t num_samples, float scale, const float* d_taps,
                                          int32_t num_taps, const int16_t* d_delay, int32_t delay_len, int32_t dsr,
                                          int32_t ds_phase, float* d_out, int64_t out_len, void* stream);
