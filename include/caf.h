@@ -594,6 +594,37 @@ CAF_EXPORT int32_t caf_locate_grid(const caf_locate_desc* desc, const double* d_
 /* the launch geometry: points per workgroup and records per staged chunk (the sizes at which the kernel changes path) */
 CAF_EXPORT int32_t caf_locate_geometry(int32_t* points_per_workgroup, int32_t* records_per_chunk);
 
+/* ---- CRB accuracy maps (crbRoutines.py: CRBMap).  Added after ABI 1.10 without a version bump, detected by symbol.  Everything
+ * is float64.  The Cramer-Rao bound of a position fix at every point of the grids that caf_locate_grid searches: a record
+ * (s1, s2, v1, v2, w, kind, 0, 0) adds w J J^T to the point's 3 x 3 Fisher matrix F, in the order of k, with a = p - s, rho = |a|,
+ * u = a / rho.  The library knows nothing of seconds, hertz or radians: w is the weight of J in the units of J. */
+#define CAF_CRB_RANGE 1       /* J = u1: a range from s1 (TOA)                                                     */
+#define CAF_CRB_RANGE_SUM 2   /* J = u1 + u2: a one-bounce round trip, transmitter s1, receiver s2                 */
+#define CAF_CRB_RANGE_DIFF 3  /* J = u2 - u1: a range difference (TDOA)                                            */
+#define CAF_CRB_RATE_DIFF 4   /* J = g2 - g1, g = (v - u (u.v)) / rho: a range-rate difference of a stationary emitter,
+                                 the gradient of the f term of the geolocation block above                         */
+#define CAF_CRB_AOA3D 5       /* two rows about s1, azimuth and elevation, weights w cos^2(elevation) and w; NaN straight
+                                 above or below the sensor                                                         */
+#define CAF_CRB_FREE 0        /* CRB = F^-1                                                                        */
+#define CAF_CRB_FIXED 1       /* the fix lies in the plane of normal n, `normal` for every point                   */
+#define CAF_CRB_RADIAL 2      /* n = p (a known length of the position vector)                                     */
+#define CAF_CRB_WGS84 3       /* n = (px / a^2, py / a^2, pz / b^2), the normal of the WGS84 ellipsoid through p   */
+/* desc: source, n and the tables as for caf_locate_grid (desc->mode is not read; desc->cost_f32 chooses the type of d_rms);
+ * d_records, K, d_set_starts, B as for caf_locate_grid: B maps over the same points in one launch.  A record of any other kind
+ * makes every point of its set NaN.  A point on a sensor is NaN (0 / 0).  `normal`: HOST, 3 doubles, read for CAF_CRB_FIXED only.
+ * Under a constraint, e = z^ x n (x^ where that vanishes), east = e / |e|, north = n^ x east, U = [east north],
+ * G = U^T F U, C2 = G^-1 and CRB = U C2 U^T.  A point is unobservable, and NaN in every output, when a pivot of the L D L^T of G
+ * (of F for CAF_CRB_FREE) is not above singular_threshold times its diagonal entry.
+ * Outputs, each optional: d_crb (B, N, 6) = xx xy xz yy yz zz; d_ellipse (B, N, 3) = sigma_major >= sigma_minor (the roots of the
+ * eigenvalues of C2) and the angle of the major axis from east toward north in (-pi/2, pi/2] (refused with CAF_CRB_FREE);
+ * d_rms (B, N) float64 or float32 = sqrt(trace CRB); d_min_val / d_min_idx and d_max_val / d_max_idx (B): the extremes of each
+ * set's rms and the FIRST index that has them (an index needs its value).  NaN never wins; nothing but NaN reports (NaN, -1). */
+CAF_EXPORT int32_t caf_crb_map(const caf_locate_desc* desc, const double* d_records, int64_t K, const int64_t* d_set_starts,
+                               int32_t B, int32_t constraint, const double* normal, double* d_crb, double* d_ellipse, void* d_rms,
+                               double* d_min_val, int64_t* d_min_idx, double* d_max_val, int64_t* d_max_idx, void* stream);
+/* the launch geometry (points per workgroup, records per staged chunk) and the threshold of an unobservable point */
+CAF_EXPORT int32_t caf_crb_map_geometry(int32_t* points_per_workgroup, int32_t* records_per_chunk, double* singular_threshold);
+
 /* ---- Viterbi sequence detection (viterbiDemodClasses.py: ViterbiDemodulator, BurstyViterbiDemodulator).  Added after ABI 1.10
  * without a version bump, detected by symbol.  Everything is float64.  With A states, T pretransitions per state, L sources:
  *   P_n[m] = sum_i exp(-j omegas[i] (n up + m)) pulses[i][m], m < pulselen, and the signal of a symbol sequence g is

@@ -218,6 +218,8 @@ CAF_LOCATE_MESH_XY = 2
 CAF_LOCATE_TD = 1
 CAF_LOCATE_FD = 2
 CAF_LOCATE_TDFD = 3
+CAF_CRB_RANGE, CAF_CRB_RANGE_SUM, CAF_CRB_RANGE_DIFF, CAF_CRB_RATE_DIFF, CAF_CRB_AOA3D = 1, 2, 3, 4, 5
+CAF_CRB_FREE, CAF_CRB_FIXED, CAF_CRB_RADIAL, CAF_CRB_WGS84 = 0, 1, 2, 3
 
 CAF_DEMOD_LOCK_EIG = 0
 CAF_DEMOD_LOCK_POWERSUM = 1
@@ -315,6 +317,8 @@ _SIGNATURES = {
     "caf_cp2fsk_bursty_demod": [_P, _I64, _I64, _I32, ct.c_double, _I32, _P, _I32, _I64, _I64, _P, _P, _P, _P],
     "caf_locate_grid": [ct.POINTER(CafLocateDesc), _P, _I64, _P, _I32, _P, _P, _P, _P],
     "caf_locate_geometry": [ct.POINTER(_I32), ct.POINTER(_I32)],
+    "caf_crb_map": [ct.POINTER(CafLocateDesc), _P, _I64, _P, _I32, _I32, ct.POINTER(ct.c_double), _P, _P, _P, _P, _P, _P, _P, _P],
+    "caf_crb_map_geometry": [ct.POINTER(_I32), ct.POINTER(_I32), ct.POINTER(ct.c_double)],
     "caf_viterbi_table": [_P, _P, _I32, _I32, _I32, _I32, _P, _P],
     "caf_viterbi_demod": [ct.POINTER(CafViterbiDesc), _P],
     "caf_viterbi_geometry": [ct.POINTER(_I32), ct.POINTER(_I32), ct.POINTER(_I32)],

@@ -14,7 +14,8 @@ float64 throughout, where the reference's flat functions and its CUDA kernel are
 
 Not provided: ``plot``, ``SatellitePairTDFDMixin`` (needs skyfield and sgp4), the RTT searches, the hyperbola helpers and the
 tangent-plane functions.  There is no CPU path: without a GPU every search raises RuntimeError (argument checks come first).
-The CRB functions are host NumPy, as in the reference.
+The CRB functions are host NumPy, as in the reference; ``crbMap`` of the two mixins evaluates them at every grid point on the
+device (crbRoutines.py).
 """
 
 import ctypes as ct
@@ -519,6 +520,18 @@ class TDMixin:
         gridmin = np.asarray(gridmin, dtype=np.float64)
         return calcCRB_TD(gridmin, S.T, np.asarray(td_sigma_list) * LIGHTSPD, cmat=gridmin.reshape(3, 1))[0]
 
+    def crbMap(self, s1x_list, s2x_list, td_sigma_list, outputs=("rms",), device=False, constraint="radial"):
+        """crb() at every grid point in one launch (crbRoutines.CRBMap): a CRBMapResult whose grids hold, at index i, what
+        crb(self.gridmat[i], ...) gives -- rms = sqrt(trace), ellipse, the six entries xx xy xz yy yz zz -- and the best and worst
+        point.  B measurement sets are given as in locate()."""
+        from .crbRoutines import CRBMap
+
+        batch = _is_batch(s1x_list)
+        m = CRBMap(constraint)
+        for n, a in enumerate(_per_set((s1x_list, s2x_list, td_sigma_list), batch)):
+            (m.newSet() if n else m).addTDOA(*a)
+        return m.run(self, outputs=outputs, device=device)
+
 
 class TDFDMixin:
     def run(self, s1x_list, s2x_list, tdoa_list, td_sigma_list, s1v_list, s2v_list, fdoa_list, fd_sigma_list, fc, device=False):
@@ -553,6 +566,19 @@ class TDFDMixin:
         cmat[3:6, 1:4] = np.eye(3)
         return calcCRB_TDFD(gridmin, S.T, np.asarray(td_sigma_list) * LIGHTSPD, np.zeros(3), Sdot.T,
                             np.asarray(fd_sigma_list) / fc * LIGHTSPD, cmat=cmat)
+
+    def crbMap(self, s1x_list, s2x_list, s1v_list, s2v_list, td_sigma_list, fd_sigma_list, fc, outputs=("rms",), device=False,
+               constraint="radial"):
+        """The position block of crb() at every grid point in one launch (crbRoutines.CRBMap), as TDMixin.crbMap; B measurement
+        sets as in locate() (fc may be one value for all sets).  Of each set the TD records come first, then the FD records."""
+        from .crbRoutines import CRBMap
+
+        batch = _is_batch(s1x_list)
+        m = CRBMap(constraint)
+        args = (s1x_list, s2x_list, s1v_list, s2v_list, td_sigma_list, fd_sigma_list, fc)
+        for n, (s1, s2, v1, v2, tds, fds, f) in enumerate(_per_set(args, batch, scalars=(6,))):
+            (m.newSet() if n else m).addTDOA(s1, s2, tds).addFDOA(s1, s2, v1, v2, fds, f)
+        return m.run(self, outputs=outputs, device=device)
 
 
 class LatLonGridLocalizerTD(TDMixin, LatLonGridLocalizer):
