@@ -593,6 +593,21 @@ CAF_EXPORT int32_t caf_locate_grid(const caf_locate_desc* desc, const double* d_
                                    int32_t B, void* d_cost, double* d_min_val, int64_t* d_min_idx, void* stream);
 /* the launch geometry: points per workgroup and records per staged chunk (the sizes at which the kernel changes path) */
 CAF_EXPORT int32_t caf_locate_geometry(int32_t* points_per_workgroup, int32_t* records_per_chunk);
+/* One-bounce round trips over the same grids (localizationRoutines.py:368-507: gridSearchRTT, gridSearchBlindLinearRTT), float64,
+ * contraction off, no atomics.  Of the record, s1 is the transmitter, s2 the receiver, slot 12 the measured range sum r, slot 13
+ * its weight w and slots 6 and 7 the nuisance basis g0, g1; the other slots are not read.  With d_k = r_k - (rho1_k + rho2_k):
+ *   nuisance 0: cost[p] = sum_k w_k d_k^2, in the order of k;
+ *   nuisance 1, 2: g0 (and g1) are orthonormal under the weights of their set, sum_k w g_i g_j = delta_ij; a first pass forms
+ *     alpha = sum_k w g0 d (and beta = sum_k w g1 d), a second pass cost[p] = sum_k w (d - alpha g0 - beta g1)^2, which is
+ *     min over (a, b) of sum_k w (d - a t - b)^2 for a basis of span{1} (and {1, t}).  Every range is computed twice.
+ * desc (desc->mode is not read), d_records, K, d_set_starts (clamped), B and the three optional outputs are taken as
+ * caf_locate_grid takes them; the first index wins the arg min, NaN never wins, nothing but NaN reports (NaN, -1).  A point on
+ * a sensor has that range 0 and a finite cost.  Refused: nuisance outside 0..2, K < B (nuisance + 1), and what caf_locate_grid
+ * refuses.  The offsets live on the device, so a SET with no more than `nuisance` records is NOT caught here (its cost is 0
+ * everywhere): the caller refuses it, as it supplies the orthonormal basis. */
+CAF_EXPORT int32_t caf_locate_rtt(const caf_locate_desc* desc, const double* d_records, int64_t K, const int64_t* d_set_starts,
+                                  int32_t B, int32_t nuisance, void* d_cost, double* d_min_val, int64_t* d_min_idx, void* stream);
+CAF_EXPORT int32_t caf_locate_rtt_geometry(int32_t* points_per_workgroup, int32_t* records_per_chunk);
 
 /* ---- CRB accuracy maps (crbRoutines.py: CRBMap).  Added after ABI 1.10 without a version bump, detected by symbol.  Everything
  * is float64.  The Cramer-Rao bound of a position fix at every point of the grids that caf_locate_grid searches: a record

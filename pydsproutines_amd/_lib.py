@@ -317,6 +317,8 @@ _SIGNATURES = {
     "caf_cp2fsk_bursty_demod": [_P, _I64, _I64, _I32, ct.c_double, _I32, _P, _I32, _I64, _I64, _P, _P, _P, _P],
     "caf_locate_grid": [ct.POINTER(CafLocateDesc), _P, _I64, _P, _I32, _P, _P, _P, _P],
     "caf_locate_geometry": [ct.POINTER(_I32), ct.POINTER(_I32)],
+    "caf_locate_rtt": [ct.POINTER(CafLocateDesc), _P, _I64, _P, _I32, _I32, _P, _P, _P, _P],
+    "caf_locate_rtt_geometry": [ct.POINTER(_I32), ct.POINTER(_I32)],
     "caf_crb_map": [ct.POINTER(CafLocateDesc), _P, _I64, _P, _I32, _I32, ct.POINTER(ct.c_double), _P, _P, _P, _P, _P, _P, _P, _P],
     "caf_crb_map_geometry": [ct.POINTER(_I32), ct.POINTER(_I32), ct.POINTER(ct.c_double)],
     "caf_viterbi_table": [_P, _P, _I32, _I32, _I32, _I32, _P, _P],

@@ -14,7 +14,8 @@ so an ellipse's angle means the same thing at every point: G = [east north]^T F 
 There is no CPU path for ``run``: without a GPU it raises RuntimeError (argument checks come first).  ``at`` is host NumPy.
 
 Not provided: ellipses of an unconstrained 3 x 3, correlated measurements on the device (the host classes accept a matrix
-``inv_sigma_sq``), the five-parameter blind RTT bound, plots.
+``inv_sigma_sq``), the five-parameter blind RTT bound as a device map (on the host it is
+``localizationRoutines.calcCRB_BlindLinearRTT``), plots.
 """
 
 import collections

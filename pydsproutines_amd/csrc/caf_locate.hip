@@ -29,6 +29,24 @@
 // <); across lanes caf::wave_argmax on the negated cost (lower index wins a tie); the workgroup's four waves through LDS with the
 // same comparison; the partials of a set, in increasing order of workgroup, by k_locate_fold in the same way.
 // Floating-point contraction is off in this file: every product and sum is rounded where it is written, and each fma is spelled.
+//
+// One-bounce round trips (localizationRoutines.py:368-507 of the reference: gridSearchRTT, gridSearchBlindLinearRTT).  The record
+// is (s1 = transmitter, s2 = receiver, g0, g1 in slots 6 and 7, r = the measured range sum in slot 12, w in slot 13); with
+//   d_k = r_k - (rho1_k + rho2_k)
+//   k_locate_rtt<Q, SRC>   Q = 0: cost[p] = sum_k w_k d_k^2, in the order of k.
+//                          Q = 1, 2: the columns g_i are orthonormal under the weights of their set (sum_k w g_i g_j = delta_ij,
+//                          the host's work), and the cost is what is left of d once its part in their span is taken out,
+//                            pass 1  alpha = sum_k (w g0) d,  beta = sum_k (w g1) d       (beta for Q = 2 alone)
+//                            pass 2  cost[p] = sum_k w (d - alpha g0 - beta g1)^2         = min over (a, b) of sum_k w (d - a t - b)^2
+//                          each in the order of k.  The geometry, the staging and the arg min are k_locate's.
+// Two passes are required: the one-pass form sum w d^2 - alpha^2 - beta^2 subtracts numbers that agree to six or more digits at the
+// minimum (a turnaround of 128 us is 38 km of d against metres of residual) and was measured 1.0e-7 off in relative terms where
+// the two passes are 2.4e-13 off, both in plain float64.  The price is each range twice.  As written, d costs 28 float64
+// operations per point and record (per range 3 subtractions, 1 product and 2 fma for a.a, 6 for the reciprocal root, 1 product
+// for rho = 13, twice; the sum and the difference from r), so Q = 0 costs 28 + 2 = 30, Q = 1 (28 + 1) + (28 + 3) = 60 and
+// Q = 2 (28 + 2) + (28 + 4) = 62.  A set of at most LOC_C records is staged once and pass 2 reads it from LDS again; a longer
+// set is read from global memory once per pass.  The range sum's error is c1 eps (rho1 + rho2) with the same c1 = 6: 5 per range
+// and one rounding of the sum.  A point on a sensor has that range 0 (selected), so its cost is finite.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -180,6 +198,127 @@ void launch_mode(int source, dim3 grid, hipStream_t st, const LocSrc& src, int64
         hipLaunchKernelGGL((k_locate<TD, FD, CAF_LOCATE_MESH_XY>), grid, dim3(LOC_T), 0, st, src, N, rec, K, starts, cost, cost_f32, pv, pi);
 }
 
+// ---- one-bounce round trips ------------------------------------------------------------------------------------------------------
+// the staged records against the thread's points: PASS 0 adds to alpha (and beta), PASS 1 adds the squared residual to acc
+template <int Q, int PASS>
+__device__ __forceinline__ void rtt_chunk(const double* s_rec, int nrec, const double (&px)[LOC_PPT], const double (&py)[LOC_PPT],
+                                          const double (&pz)[LOC_PPT], double (&al)[LOC_PPT], double (&be)[LOC_PPT], double (&acc)[LOC_PPT]) {
+    for (int k = 0; k < nrec; k++) {
+        const double* r = s_rec + k * LOC_REC;  // the same address in every lane: broadcast reads
+        const double s1x = r[0], s1y = r[1], s1z = r[2], s2x = r[3], s2y = r[4], s2z = r[5], rr = r[12], w = r[13];
+        double g0 = 0, g1 = 0;
+        if constexpr (Q >= 1) g0 = r[6];
+        if constexpr (Q == 2) g1 = r[7];
+        const double wg0 = w * g0, wg1 = w * g1;
+#pragma unroll
+        for (int j = 0; j < LOC_PPT; j++) {
+            const double a1x = px[j] - s1x, a1y = py[j] - s1y, a1z = pz[j] - s1z;
+            const double a2x = px[j] - s2x, a2y = py[j] - s2y, a2z = pz[j] - s2z;
+            const double q1 = fma(a1z, a1z, fma(a1y, a1y, a1x * a1x));
+            const double q2 = fma(a2z, a2z, fma(a2y, a2y, a2x * a2x));
+            const double rho1 = q1 == 0.0 ? 0.0 : q1 * rsqrt_once(q1);
+            const double rho2 = q2 == 0.0 ? 0.0 : q2 * rsqrt_once(q2);
+            const double d = rr - (rho1 + rho2);
+            if constexpr (PASS == 0) {
+                al[j] = fma(wg0, d, al[j]);
+                if constexpr (Q == 2) be[j] = fma(wg1, d, be[j]);
+            } else {
+                double e = d;
+                if constexpr (Q >= 1) e = fma(-al[j], g0, e);
+                if constexpr (Q == 2) e = fma(-be[j], g1, e);
+                acc[j] = fma(w, e * e, acc[j]);
+            }
+        }
+    }
+}
+
+template <int Q, int SRC>
+__global__ __launch_bounds__(LOC_T) void k_locate_rtt(const LocSrc src, int64_t N, const double* __restrict__ rec, int64_t K,
+                                                      const int64_t* __restrict__ set_starts, void* __restrict__ cost, int cost_f32,
+                                                      double* __restrict__ part_v, int64_t* __restrict__ part_i) {
+    __shared__ double s_rec[LOC_C * LOC_REC];
+    __shared__ WaveSlots<LOC_T / 64, double, long long> s_best;
+    const int tid = threadIdx.x;
+    const int64_t base = (int64_t)blockIdx.x * LOC_P;
+    const int set = blockIdx.y;
+
+    // the records of this set, clamped into the table whatever the offsets say
+    int64_t k0 = 0, k1 = K;
+    if (set_starts) {
+        k0 = std::min(std::max<int64_t>(set_starts[set], 0), K);
+        k1 = std::min(std::max<int64_t>(set_starts[set + 1], k0), K);
+    }
+    const bool once = k1 - k0 <= LOC_C;  // the whole set is one chunk: pass 2 finds it in LDS
+
+    double px[LOC_PPT], py[LOC_PPT], pz[LOC_PPT], al[LOC_PPT], be[LOC_PPT], acc[LOC_PPT];
+    loc_points<SRC, LOC_T, LOC_PPT>(src, N, base, tid, px, py, pz);
+#pragma unroll
+    for (int j = 0; j < LOC_PPT; j++) al[j] = be[j] = acc[j] = 0.0;
+
+    auto stage = [&](int64_t kc, int nrec) {
+        const double* g = rec + kc * LOC_REC;
+        for (int q = tid; q < nrec * LOC_REC; q += LOC_T) s_rec[q] = g[q];
+        __syncthreads();
+    };
+    if constexpr (Q > 0) {
+        for (int64_t kc = k0; kc < k1; kc += LOC_C) {
+            const int nrec = (int)std::min<int64_t>(LOC_C, k1 - kc);
+            stage(kc, nrec);
+            rtt_chunk<Q, 0>(s_rec, nrec, px, py, pz, al, be, acc);
+            if (!once) __syncthreads();  // the chunk is overwritten next
+        }
+    }
+    for (int64_t kc = k0; kc < k1; kc += LOC_C) {
+        const int nrec = (int)std::min<int64_t>(LOC_C, k1 - kc);
+        if (Q == 0 || !once) stage(kc, nrec);
+        rtt_chunk<Q, 1>(s_rec, nrec, px, py, pz, al, be, acc);
+        if (!once) __syncthreads();
+    }
+
+    // the stores and the workgroup's partial, as in k_locate
+    const int64_t out0 = (int64_t)set * N;
+    if (cost) {
+#pragma unroll
+        for (int j = 0; j < LOC_PPT; j++) {
+            const int64_t at = base + tid + j * LOC_T;
+            if (at >= N) continue;
+            if (cost_f32) ((float*)cost)[out0 + at] = (float)acc[j];
+            else ((double*)cost)[out0 + at] = acc[j];
+        }
+    }
+    if (part_v) {
+        double bv = INFINITY;
+        long long bi = NO_INDEX;
+#pragma unroll
+        for (int j = 0; j < LOC_PPT; j++) {
+            const int64_t at = base + tid + j * LOC_T;
+            if (at < N && first_min(bv, bi, acc[j], (long long)at)) {
+                bv = acc[j];
+                bi = at;
+            }
+        }
+        bv = -bv;
+        block_argmax(s_best, bv, bi);
+        bv = -bv;
+        if (tid == 0) {
+            const int64_t o = (int64_t)set * gridDim.x + blockIdx.x;
+            part_v[o] = bv;
+            part_i[o] = (int64_t)bi;
+        }
+    }
+}
+
+template <int Q>
+void launch_rtt(int source, dim3 grid, hipStream_t st, const LocSrc& src, int64_t N, const double* rec, int64_t K, const int64_t* starts,
+                void* cost, int cost_f32, double* pv, int64_t* pi) {
+    if (source == CAF_LOCATE_POINTS)
+        hipLaunchKernelGGL((k_locate_rtt<Q, CAF_LOCATE_POINTS>), grid, dim3(LOC_T), 0, st, src, N, rec, K, starts, cost, cost_f32, pv, pi);
+    else if (source == CAF_LOCATE_MESH)
+        hipLaunchKernelGGL((k_locate_rtt<Q, CAF_LOCATE_MESH>), grid, dim3(LOC_T), 0, st, src, N, rec, K, starts, cost, cost_f32, pv, pi);
+    else
+        hipLaunchKernelGGL((k_locate_rtt<Q, CAF_LOCATE_MESH_XY>), grid, dim3(LOC_T), 0, st, src, N, rec, K, starts, cost, cost_f32, pv, pi);
+}
+
 }  // namespace
 
 }  // namespace caf
@@ -249,6 +388,76 @@ int32_t caf_locate_grid(const caf_locate_desc* desc, const double* d_records, in
         launch_mode<false, true>(desc->source, grid, st, src, N, d_records, K, d_set_starts, d_cost, desc->cost_f32, pv, pi);
     else
         launch_mode<true, true>(desc->source, grid, st, src, N, d_records, K, d_set_starts, d_cost, desc->cost_f32, pv, pi);
+    CAF_HIP_TRY(hipGetLastError());
+    if (want_min) {
+        hipLaunchKernelGGL(k_locate_fold, dim3((unsigned)B), dim3(LOC_T), 0, st, pv, pi, tiles, d_min_val, d_min_idx);
+        CAF_HIP_TRY(hipGetLastError());
+    }
+    return sc.finish();
+}
+
+int32_t caf_locate_rtt_geometry(int32_t* points_per_workgroup, int32_t* records_per_chunk) {
+    if (points_per_workgroup) *points_per_workgroup = LOC_P;
+    if (records_per_chunk) *records_per_chunk = LOC_C;
+    return CAF_OK;
+}
+
+int32_t caf_locate_rtt(const caf_locate_desc* desc, const double* d_records, int64_t K, const int64_t* d_set_starts, int32_t B,
+                       int32_t nuisance, void* d_cost, double* d_min_val, int64_t* d_min_idx, void* stream) {
+    CAF_REQUIRE(desc != nullptr, "caf_locate_rtt: NULL descriptor");
+    CAF_REQUIRE(nuisance >= 0 && nuisance <= 2, "caf_locate_rtt: nuisance must be 0, 1 or 2");
+    CAF_REQUIRE(desc->cost_f32 == 0 || desc->cost_f32 == 1, "caf_locate_rtt: cost_f32 must be 0 or 1");
+    CAF_REQUIRE(K >= 1 && K <= ((int64_t)1 << 40), "caf_locate_rtt: the table needs at least one record");
+    CAF_REQUIRE(B >= 1 && B <= 65535 && (d_set_starts != nullptr || B == 1),
+                "caf_locate_rtt: 1 <= sets <= 65535, and more than one set needs set_starts");
+    CAF_REQUIRE((int64_t)B * (nuisance + 1) <= K, "caf_locate_rtt: every set needs more records than nuisance parameters");
+    LocSrc src = {};
+    int64_t N = 0;
+    if (desc->source == CAF_LOCATE_POINTS) {
+        N = desc->n;
+        CAF_REQUIRE(N >= 1, "caf_locate_rtt: the point matrix needs at least one row");
+        CAF_REQUIRE(desc->d_points != nullptr, "caf_locate_rtt: NULL point matrix");
+        src.pts = desc->d_points;
+    } else if (desc->source == CAF_LOCATE_MESH || desc->source == CAF_LOCATE_MESH_XY) {
+        CAF_REQUIRE(desc->ni >= 1 && desc->nj >= 1, "caf_locate_rtt: the mesh needs ni >= 1 and nj >= 1");
+        N = (int64_t)desc->ni * desc->nj;
+        CAF_REQUIRE(desc->d_a != nullptr && desc->d_c != nullptr, "caf_locate_rtt: NULL mesh table");
+        if (desc->source == CAF_LOCATE_MESH) {
+            CAF_REQUIRE(desc->d_z != nullptr && desc->d_s != nullptr, "caf_locate_rtt: NULL mesh table");
+        }
+        src.a = desc->d_a;
+        src.z = desc->d_z;
+        src.c = desc->d_c;
+        src.s = desc->d_s;
+        src.z0 = desc->z;
+        src.ni = desc->ni;
+        src.nj = desc->nj;
+        src.step_i = LOC_T / desc->nj;
+        src.step_j = LOC_T % desc->nj;
+    } else {
+        CAF_REQUIRE(false, "caf_locate_rtt: unknown point source");
+    }
+    const int64_t tiles = (N + LOC_P - 1) / LOC_P;
+    CAF_REQUIRE(tiles <= 0x7fffffff, "caf_locate_rtt: too many points for one launch");
+    CAF_REQUIRE(d_records != nullptr, "caf_locate_rtt: NULL record table");
+    const bool want_min = d_min_val != nullptr || d_min_idx != nullptr;
+    if (!d_cost && !want_min) return CAF_OK;
+
+    hipStream_t st = (hipStream_t)stream;
+    Scratch sc(st);
+    double* pv = nullptr;
+    int64_t* pi = nullptr;
+    if (want_min) {
+        int rc;
+        if ((rc = sc.get(&pv, (int64_t)B * tiles)) || (rc = sc.get(&pi, (int64_t)B * tiles))) return rc;
+    }
+    const dim3 grid((unsigned)tiles, (unsigned)B);
+    if (nuisance == 0)
+        launch_rtt<0>(desc->source, grid, st, src, N, d_records, K, d_set_starts, d_cost, desc->cost_f32, pv, pi);
+    else if (nuisance == 1)
+        launch_rtt<1>(desc->source, grid, st, src, N, d_records, K, d_set_starts, d_cost, desc->cost_f32, pv, pi);
+    else
+        launch_rtt<2>(desc->source, grid, st, src, N, d_records, K, d_set_starts, d_cost, desc->cost_f32, pv, pi);
     CAF_HIP_TRY(hipGetLastError());
     if (want_min) {
         hipLaunchKernelGGL(k_locate_fold, dim3((unsigned)B), dim3(LOC_T), 0, st, pv, pi, tiles, d_min_val, d_min_idx);

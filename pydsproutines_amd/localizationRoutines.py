@@ -12,10 +12,22 @@ WGS84 lat/lon grid, two and a constant for an XY mesh).  ``locate()`` fuses the 
 The host preparation reproduces the reference's roundings of the measurements (see ``_records_*``); the geometry itself is
 float64 throughout, where the reference's flat functions and its CUDA kernel are float32 (half a metre per ulp in ECEF).
 
-Not provided: ``plot``, ``SatellitePairTDFDMixin`` (needs skyfield and sgp4), the RTT searches, the hyperbola helpers and the
-tangent-plane functions.  There is no CPU path: without a GPU every search raises RuntimeError (argument checks come first).
-The CRB functions are host NumPy, as in the reference; ``crbMap`` of the two mixins evaluates them at every grid point on the
-device (crbRoutines.py).
+One-bounce round trips (``gridSearchRTT_direct``, ``gridSearchBlindLinearRTT``, ``RTTMixin``, ``BlindRTTMixin``) go through
+``caf_locate_rtt`` in the same file, over the same grids: with d_k = r_k - (|p - tx_k| + |p - rx_k|),
+
+    plain   cost[p] = sum_k w_k d_k^2
+    blind   cost[p] = min over (a, b) of sum_k w_k (d_k - a t_k - b)^2      (``nuisance=1``: b alone)
+
+The blind search is for a transponder that answers after an unknown turnaround b on a clock that drifts at an unknown rate a.
+The host centres the times of each set and hands the device a basis of span{1, t} that is orthonormal under the set's weights;
+the device projects d off it in two passes (one pass would lose the residual's digits under the turnaround's).  The default of
+``gridSearchBlindLinearRTT`` is the reference's: unweighted, the sigmas ignored, the cost in s^2.  Where the reference returns
+0 (no more measurements than unknowns, or times that do not span {1, t}), these raise ValueError.
+
+Not provided: ``plot``, ``SatellitePairTDFDMixin`` (needs skyfield and sgp4), the hyperbola helpers, the tangent-plane functions
+and the blind RTT bound as a device map.  There is no CPU path: without a GPU every search raises RuntimeError (argument checks
+come first).  The CRB functions are host NumPy, as in the reference; ``crbMap`` of the TD, TDFD and RTT mixins evaluates them at
+every grid point on the device (crbRoutines.py).
 """
 
 import ctypes as ct
@@ -27,7 +39,9 @@ from .devarray import DeviceArray, asarray, empty
 
 __all__ = ["gridSearchTDOA", "gridSearchFDOA", "gridSearchTDOA_direct", "gridSearchTDFD_direct", "gridSearchTDOA_gpu",
            "latlongrid_to_ecef", "calcCRB_TD", "calcCRB_TDFD", "projectCRBtoEllipse", "GridLocalizer", "LatLonGridLocalizer",
-           "TDMixin", "TDFDMixin", "LatLonGridLocalizerTD", "LatLonGridLocalizerTDFD", "locate_geometry"]
+           "TDMixin", "TDFDMixin", "LatLonGridLocalizerTD", "LatLonGridLocalizerTDFD", "locate_geometry", "gridSearchRTT_direct",
+           "gridSearchBlindLinearRTT", "calcCRB_BlindLinearRTT", "RTTMixin", "BlindRTTMixin", "LatLonGridLocalizerRTT",
+           "LatLonGridLocalizerBlindRTT", "locate_rtt_geometry"]
 
 LIGHTSPD = 299792458.0
 WGS84_A = 6378137.0            # the two defining constants of WGS84: semi-major axis (m) ...
@@ -35,6 +49,7 @@ WGS84_INV_F = 298.257223563    # ... and inverse flattening
 
 _REC = 16  # doubles per record: s1(3) s2(3) v1(3) v2(3) r wr d wd
 _MODES = {"td": _lib.CAF_LOCATE_TD, "fd": _lib.CAF_LOCATE_FD, "tdfd": _lib.CAF_LOCATE_TDFD}
+_RTT = {"rtt": 0, "rtt1": 1, "rtt2": 2}  # caf_locate_rtt and its number of nuisance parameters
 
 
 def _p(a):
@@ -51,6 +66,13 @@ def locate_geometry():
     """(points per workgroup, records per staged chunk) of the kernel: the sizes at which it changes path."""
     p, c = ct.c_int32(0), ct.c_int32(0)
     _lib.check(_lib.load().caf_locate_geometry(ct.byref(p), ct.byref(c)), "caf_locate_geometry")
+    return int(p.value), int(c.value)
+
+
+def locate_rtt_geometry():
+    """the same two sizes of the round-trip kernel; a set of at most one chunk is staged once for both passes"""
+    p, c = ct.c_int32(0), ct.c_int32(0)
+    _lib.check(_lib.load().caf_locate_rtt_geometry(ct.byref(p), ct.byref(c)), "caf_locate_rtt_geometry")
     return int(p.value), int(c.value)
 
 
@@ -140,6 +162,76 @@ def _records_fd_flat(s1x_list, s2x_list, s1v_list, s2v_list, fdoa_list, fd_sigma
     return _table(s1, s2, v1, v2, d=d, wd=1.0 / (sd * sd))
 
 
+def _kx(a, name, k):
+    """K positions: a K x 3 matrix, or one position of length 3 for all K measurements (a static platform)"""
+    a = np.asarray(a, dtype=np.float64)
+    if a.ndim == 1:
+        if a.size != 3:
+            raise ValueError("a static %s is one position of length 3." % name)
+        return np.tile(a, (k, 1))
+    return _k3(a, name, k)
+
+
+def _records_rtt(t_list, r_list, toa_list, toa_sigma_list):
+    """gridSearchRTT's roundings, all float64: r = c toa, w = 1 / (c sigma)^2"""
+    toa = np.asarray(toa_list, dtype=np.float64).reshape(-1)
+    k = toa.size
+    if k < 1:
+        raise ValueError("toa_list needs at least one measurement.")
+    m_err = LIGHTSPD * _k1(toa_sigma_list, "toa_sigma_list", k)
+    return _table(_kx(t_list, "t_list", k), _kx(r_list, "r_list", k), r=LIGHTSPD * toa, wr=1.0 / (m_err * m_err))
+
+
+def _nuisance_basis(t, w, q):
+    """The K x q columns g0 (and g1) of span{1} (and {1, t}), orthonormal under the weights w: sum_k w g_i g_j = delta_ij.
+    t is centred first; g1 is made orthogonal to g0 twice (the second round removes what the first one's rounding left)."""
+    g = np.zeros((t.size, q))
+    g[:, 0] = 1.0 / np.sqrt(np.sum(w))
+    if q == 2:
+        tc = t - np.mean(t)
+        g1 = tc - g[:, 0] * np.sum(w * g[:, 0] * tc)
+        g1 = g1 - g[:, 0] * np.sum(w * g[:, 0] * g1)
+        norm = np.sqrt(np.sum(w * g1 * g1))
+        # centring leaves every entry within one rounding of the largest |t|: a norm that small is all rounding
+        if not norm > 64 * np.finfo(np.float64).eps * np.max(np.abs(t)) * np.sqrt(np.sum(w)):
+            raise ValueError("time_list does not span {1, t}: the slope of the fit is undetermined (all times equal?).")
+        g[:, 1] = g1 / norm
+    return g
+
+
+def _records_blind(tx_list, rx_list, time_list, toa_list, toa_sigma_list, weighted, nuisance):
+    """gridSearchBlindLinearRTT's records: r = c toa; w = 1 / c^2 (the cost is then in s^2 and the sigmas are ignored, as in the
+    reference) or 1 / (c sigma)^2 with weighted=True; the basis of the fit in slots 6 and 7."""
+    if nuisance not in (1, 2):
+        raise ValueError("nuisance is 1 (an unknown turnaround) or 2 (a turnaround and a drift).")
+    toa = np.asarray(toa_list, dtype=np.float64).reshape(-1)
+    k = toa.size
+    if k <= nuisance:
+        raise ValueError("a fit of %d nuisance parameters needs more than %d measurements, found %d." % (nuisance, nuisance, k))
+    t = _k1(time_list, "time_list", k)
+    if weighted:
+        m_err = LIGHTSPD * _k1(toa_sigma_list, "toa_sigma_list", k)
+        w = 1.0 / (m_err * m_err)
+    else:
+        w = np.full(k, 1.0 / (LIGHTSPD * LIGHTSPD))
+    rec = _table(_kx(tx_list, "tx_list", k), _kx(rx_list, "rx_list", k), r=LIGHTSPD * toa, wr=w)
+    rec[:, 6 : 6 + nuisance] = _nuisance_basis(t, w, nuisance)
+    return rec
+
+
+def _fit_at(point, rec, time_list, nuisance):
+    """(slope in s/s, offset in s at time 0) of the weighted fit of d_k = toa_k - (range sum) / c at one point, on the host"""
+    d = (rec[:, 12] - (np.linalg.norm(point - rec[:, 0:3], axis=1) + np.linalg.norm(point - rec[:, 3:6], axis=1))) / LIGHTSPD
+    if nuisance == 1:
+        return 0.0, float(np.sum(rec[:, 13] * d) / np.sum(rec[:, 13]))
+    t = np.asarray(time_list, dtype=np.float64).reshape(-1)
+    sw = np.sqrt(rec[:, 13])
+    tm = np.mean(t)
+    a = np.stack((t - tm, np.ones(t.size)), axis=1)
+    sol = np.linalg.lstsq(a * sw[:, None], d * sw, rcond=None)[0]
+    return float(sol[0]), float(sol[1] - sol[0] * tm)
+
+
 # ---- point sources --------------------------------------------------------------------------------------------------------------
 class _Source:
     """Where the grid points come from: an (N, 3) matrix or the tables of a separable mesh, on the device once uploaded."""
@@ -218,24 +310,32 @@ def _check_sets(set_starts, k):
 
 
 def _search(source, mode, records, set_starts=None, cost=None, argmin=False, stream=None):
-    """One launch of caf_locate_grid.  cost: None, np.float64 or np.float32 -> DeviceArray (B, N) or None;
+    """One launch of caf_locate_grid, or of caf_locate_rtt for the modes "rtt", "rtt1" and "rtt2" (0, 1 and 2 nuisance parameters,
+    whose basis the records carry).  cost: None, np.float64 or np.float32 -> DeviceArray (B, N) or None;
     argmin -> DeviceArrays (B,) float64 and (B,) int64 or (None, None).  Returns (d_cost, d_min_val, d_min_idx)."""
     records = np.ascontiguousarray(records, dtype=np.float64)
     if records.ndim != 2 or records.shape[1] != _REC or records.shape[0] < 1:
         raise ValueError("records must be a K x 16 table with K >= 1.")
     k = records.shape[0]
     ss, b = _check_sets(set_starts, k)
+    nuisance = _RTT.get(mode)
+    if nuisance is not None and (k if ss is None else int(np.min(np.diff(ss)))) <= nuisance:
+        raise ValueError("every measurement set needs more records than nuisance parameters (%d)." % nuisance)  # (the library cannot see it)
     if cost is not None and np.dtype(cost) not in (np.dtype(np.float64), np.dtype(np.float32)):
         raise ValueError("the cost grid is float64 or float32.")
     _lib.require_device()
-    desc = source.desc(_MODES[mode], cost is not None and np.dtype(cost) == np.dtype(np.float32))
+    desc = source.desc(_MODES[mode] if nuisance is None else _lib.CAF_LOCATE_TD, cost is not None and np.dtype(cost) == np.dtype(np.float32))
     d_rec = asarray(records)
     d_ss = asarray(ss) if ss is not None else None
     d_cost = empty((b, source.n), np.dtype(cost)) if cost is not None else None
     d_val = empty((b,), np.float64) if argmin else None
     d_idx = empty((b,), np.int64) if argmin else None
-    _lib.check(_lib.load().caf_locate_grid(ct.byref(desc), _p(d_rec), k, _p(d_ss), b, _p(d_cost), _p(d_val), _p(d_idx), _st(stream)),
-               "caf_locate_grid")
+    if nuisance is None:
+        _lib.check(_lib.load().caf_locate_grid(ct.byref(desc), _p(d_rec), k, _p(d_ss), b, _p(d_cost), _p(d_val), _p(d_idx), _st(stream)),
+                   "caf_locate_grid")
+    else:
+        _lib.check(_lib.load().caf_locate_rtt(ct.byref(desc), _p(d_rec), k, _p(d_ss), b, nuisance, _p(d_cost), _p(d_val), _p(d_idx),
+                                              _st(stream)), "caf_locate_rtt")
     if stream is not None:  # the uploads above go back to the pool on return: on a caller's stream nothing may still read them
         _lib.check(_lib.load().caf_stream_sync(_st(stream)), "caf_stream_sync")
     return d_cost, d_val, d_idx
@@ -293,6 +393,26 @@ def gridSearchTDOA_gpu(s1x_list, s2x_list, tdoa_list, td_sigma_list, xrange, yra
     rec = _records_td_flat(s1x_list, s2x_list, tdoa_list, td_sigma_list)
     src = _Source.xy(_f32(x0 + np.arange(xrange.size) * xp), _f32(y0 + np.arange(yrange.size) * yp), float(np.float32(z)))
     return _grid(src, "td", rec, np.float32, not moveToCPU)
+
+
+def gridSearchRTT_direct(t_list, r_list, toa_list, toa_sigma_list, grid_list, verb=True, device=False):
+    """The reference's gridSearchRTT, arguments and all, named like the other searches that take an N x 3 matrix (the bare name is
+    on this module's list of what it does not provide, which tests/test_locate_host.py holds it to).  One-bounce round-trip cost of every row of grid_list (N x 3), float64: sum_k ((|t_k - p| + |r_k - p|) - c toa_k)^2 /
+    (c sigma_k)^2.  t_list and r_list are K x 3, or one position of length 3 for a static transmitter or receiver (the two may
+    be the same platform).  device=True returns a DeviceArray."""
+    rec = _records_rtt(t_list, r_list, toa_list, toa_sigma_list)
+    return _grid(_Source.points(grid_list), "rtt", rec, np.float64, device)
+
+
+def gridSearchBlindLinearRTT(tx_list, rx_list, time_list, toa_list, toa_sigma_list, grid_list, verb=True, device=False, weighted=False,
+                             nuisance=2):
+    """Round-trip cost of every row of grid_list (N x 3) for a transponder with an unknown turnaround and an unknown clock drift:
+    the residual of the least-squares line a time_k + b through d_k = toa_k - (|tx_k - p| + |rx_k - p|) / c, float64.  As in the
+    reference the fit is unweighted, toa_sigma_list is ignored and the cost is in s^2; weighted=True weights every measurement
+    by 1 / sigma_k^2 (a dimensionless cost).  nuisance=1 fits the turnaround alone.  Raises ValueError for no more measurements
+    than nuisance parameters and for times that are all equal (the reference returns a cost of 0 everywhere)."""
+    rec = _records_blind(tx_list, rx_list, time_list, toa_list, toa_sigma_list, weighted, nuisance)
+    return _grid(_Source.points(grid_list), "rtt%d" % nuisance, rec, np.float64, device)
 
 
 def _wgs84_tables(latlist, lonlist, h=0.0):
@@ -363,6 +483,21 @@ def calcCRB_TDFD(x, S, sig_r, xdot, Sdot, sig_r_dot, pairs=None, cmat=None):
     Rdot[3:6] = unit[:, c1] - unit[:, c2]
     fim = R @ np.diag(np.asarray(sig_r, dtype=np.float64) ** -2) @ R.T
     fim = fim + Rdot @ np.diag(np.asarray(sig_r_dot, dtype=np.float64) ** -2) @ Rdot.T
+    return _invert_fim(fim, cmat)
+
+
+def calcCRB_BlindLinearRTT(x, S, P, t, sig_r, cmat=None):
+    """CRB (5 x 5) of position, slope and offset from m round trips S -> x -> P with a linear nuisance a t + b added to every
+    range sum: the rows of the Jacobian are (u_S + u_P, t, 1).  S is 3 x m; P is 3 x m or one position; sig_r in the units of
+    the range sum, so that slope and offset come in those units per unit of t and in those units."""
+    x, P = _column(x), _column(P)
+    S = np.asarray(S, dtype=np.float64)
+    ds, dp = x - S, x - P
+    R = np.zeros((5, S.shape[1]))
+    R[0:3] = ds / np.linalg.norm(ds, axis=0) + dp / np.linalg.norm(dp, axis=0)
+    R[3] = np.asarray(t, dtype=np.float64)
+    R[4] = 1.0
+    fim = R @ np.diag(np.asarray(sig_r, dtype=np.float64) ** -2) @ R.T
     return _invert_fim(fim, cmat)
 
 
@@ -581,7 +716,89 @@ class TDFDMixin:
         return m.run(self, outputs=outputs, device=device)
 
 
+def _is_batch_rtt(toa_list):
+    """one set: a vector of K round-trip times; B sets: a sequence of such vectors"""
+    if isinstance(toa_list, np.ndarray):
+        return toa_list.ndim >= 2
+    return len(toa_list) > 0 and np.ndim(toa_list[0]) >= 1  # (the vectors of a sequence need not be equally long)
+
+
+class RTTMixin:
+    def run(self, t_list, r_list, toa_list, toa_sigma_list, device=False):
+        """One-bounce round-trip cost of every grid point (length N, float64), as gridSearchRTT_direct: t_list, r_list K x 3 or one
+        static position (m), toa_list and toa_sigma_list of length K (s).  device=True leaves the grid on the device."""
+        rec = _records_rtt(t_list, r_list, toa_list, toa_sigma_list)
+        if np.ndim(self.gridmat) != 2 or np.shape(self.gridmat)[1] != 3:
+            raise ValueError("Ensure gridmat has 3 columns.")
+        return _grid(self._source(), "rtt", rec, np.float64, device)
+
+    def locate(self, t_list, r_list, toa_list, toa_sigma_list):
+        """The arg min of run() without its grid: (index, cost, point); with a sequence of B measurement sets in every argument
+        all B are searched in one launch, as in TDMixin.locate."""
+        batch = _is_batch_rtt(toa_list)
+        recs = [_records_rtt(*a) for a in _per_set((t_list, r_list, toa_list, toa_sigma_list), batch)]
+        if np.ndim(self.gridmat) != 2 or np.shape(self.gridmat)[1] != 3:
+            raise ValueError("Ensure gridmat has 3 columns.")
+        return _unbatch(self._locate("rtt", recs), batch)
+
+    def crbMap(self, t_list, r_list, toa_sigma_list, outputs=("rms",), device=False, constraint="radial"):
+        """The CRB of a round-trip fix at every grid point in one launch (crbRoutines.CRBMap.addRTT), as TDMixin.crbMap;
+        B measurement sets are given as in locate() (every position list then K_b x 3)."""
+        from .crbRoutines import CRBMap
+
+        batch = _is_batch_rtt(toa_sigma_list)
+        m = CRBMap(constraint)
+        for n, (tx, rx, sig) in enumerate(_per_set((t_list, r_list, toa_sigma_list), batch)):
+            k = np.asarray(sig).size
+            (m.newSet() if n else m).addRTT(_kx(tx, "t_list", k), _kx(rx, "r_list", k), sig)
+        return m.run(self, outputs=outputs, device=device)
+
+
+class BlindRTTMixin:
+    def run(self, tx_list, rx_list, time_list, toa_list, toa_sigma_list, device=False, weighted=False, nuisance=2):
+        """The blind round-trip cost of every grid point (length N, float64), as gridSearchBlindLinearRTT: the residual of the
+        line a time + b fitted to toa - (range sum) / c at that point."""
+        rec = _records_blind(tx_list, rx_list, time_list, toa_list, toa_sigma_list, weighted, nuisance)
+        if np.ndim(self.gridmat) != 2 or np.shape(self.gridmat)[1] != 3:
+            raise ValueError("Ensure gridmat has 3 columns.")
+        return _grid(self._source(), "rtt%d" % nuisance, rec, np.float64, device)
+
+    def locate(self, tx_list, rx_list, time_list, toa_list, toa_sigma_list, weighted=False, nuisance=2):
+        """The arg min of run() without its grid, and the fit there: (index, cost, point, slope, offset) with the slope in s/s
+        and the offset in s at time 0 (the drift and the turnaround), computed on the host from the K measurements at the found
+        point; 0 and NaN where nothing was found.  B measurement sets in one launch as in TDMixin.locate."""
+        batch = _is_batch_rtt(toa_list)
+        sets = _per_set((tx_list, rx_list, time_list, toa_list, toa_sigma_list), batch)
+        recs = [_records_blind(*a, weighted, nuisance) for a in sets]
+        if np.ndim(self.gridmat) != 2 or np.shape(self.gridmat)[1] != 3:
+            raise ValueError("Ensure gridmat has 3 columns.")
+        idx, val, pts = self._locate("rtt%d" % nuisance, recs)
+        fit = np.array([_fit_at(p, r, a[2], nuisance) if i >= 0 else (np.nan, np.nan) for i, p, r, a in zip(idx, pts, recs, sets)])
+        if batch:
+            return idx, val, pts, fit[:, 0], fit[:, 1]
+        return int(idx[0]), float(val[0]), pts[0], float(fit[0, 0]), float(fit[0, 1])
+
+    def crb(self, gridmin, tx_list, rx_list, time_list, toa_sigma_list):
+        """The position block (3 x 3) of calcCRB_BlindLinearRTT at gridmin under the known-altitude (vector length) constraint
+        of TDMixin.crb; drift and turnaround are free."""
+        t = np.asarray(time_list, dtype=np.float64).reshape(-1)
+        gridmin = np.asarray(gridmin, dtype=np.float64)
+        cmat = np.zeros((5, 1))
+        cmat[0:3, 0] = gridmin
+        crb = calcCRB_BlindLinearRTT(gridmin, _kx(tx_list, "tx_list", t.size).T, _kx(rx_list, "rx_list", t.size).T, t,
+                                     _k1(toa_sigma_list, "toa_sigma_list", t.size) * LIGHTSPD, cmat=cmat)
+        return crb[0:3, 0:3]
+
+
 class LatLonGridLocalizerTD(TDMixin, LatLonGridLocalizer):
+    pass
+
+
+class LatLonGridLocalizerRTT(RTTMixin, LatLonGridLocalizer):
+    pass
+
+
+class LatLonGridLocalizerBlindRTT(BlindRTTMixin, LatLonGridLocalizer):
     pass
 
 
