@@ -640,6 +640,50 @@ CAF_EXPORT int32_t caf_crb_map(const caf_locate_desc* desc, const double* d_reco
 /* the launch geometry (points per workgroup, records per staged chunk) and the threshold of an unobservable point */
 CAF_EXPORT int32_t caf_crb_map_geometry(int32_t* points_per_workgroup, int32_t* records_per_chunk, double* singular_threshold);
 
+/* ---- Lines of position on an oblate spheroid (hyperboloidRoutines.py: Hyperboloid.intersectOblateSpheroid; sphereRoutines.py:
+ * Sphere.intersectOblateSpheroid).  Added after ABI 1.10 without a version bump, detected by symbol.  Everything is float64,
+ * contraction off, no atomics.  A job is 16 doubles, mu(3) e0(3) e1(3) e2(3) a c p_min p_max, and describes the family of circles
+ *   q(phi) = C(p) + A(p) cos phi + B(p) sin phi,
+ *   CAF_LOP_HYPERBOLOID: C = mu - c cosh p e2, A = a sinh p e0, B = a sinh p e1   (the sheet of range difference 2 c, p = v >= 0)
+ *   CAF_LOP_SPHERE:      C = mu + c cos p e2,  A = a sin p e0,  B = a sin p e1    (a = c = r, p = theta in [0, pi])
+ * cut with E(q) = (qx^2 + qy^2) / omega^2 + qz^2 / lambda^2 - 1 = 0.  With C^ = (Cx / omega, Cy / omega, Cz / lambda) (A^, B^ alike),
+ *   g(phi) = E(q(phi)) = k0 + k1 cos phi + k2 sin phi + k3 cos 2 phi + k4 sin 2 phi,
+ *   k0 = C^.C^ + (A^.A^ + B^.B^) / 2 - 1, k1 = 2 C^.A^, k2 = 2 C^.B^, k3 = (A^.A^ - B^.B^) / 2, k4 = A^.B^,
+ * which has at most four zeros in (-pi, pi].  A job with A = B = 0 at p, or with anything that is not finite, has no zero at p.
+ * Every loop of both kernels has a trip count fixed at compile time. */
+#define CAF_LOP_HYPERBOLOID 0
+#define CAF_LOP_SPHERE 1
+#define CAF_LOP_LIST 0        /* sample j of every job takes d_p[j]                                                      */
+#define CAF_LOP_LINSPACE 1    /* lo + j ((hi - lo) / (P - 1)); the last sample is hi itself; P = 1: lo                    */
+#define CAF_LOP_CHEBYSHEV 2   /* lo + (hi - lo) (1 - cos(pi (j + 1/2) / P)) / 2: dense towards both ends                  */
+#define CAF_LOP_FOUND 0       /* d_status of caf_lop_range: some parameter of the search has a zero                       */
+#define CAF_LOP_NO_CURVE 1    /* none has: the range is (NaN, NaN)                                                        */
+typedef struct {
+    int32_t kind;           /* CAF_LOP_HYPERBOLOID or CAF_LOP_SPHERE                                                  */
+    int32_t spacing;        /* CAF_LOP_LIST, CAF_LOP_LINSPACE or CAF_LOP_CHEBYSHEV (caf_lop_range does not read it)   */
+    int32_t P;              /* samples per job (caf_lop_range does not read it)                                       */
+    int32_t reserved;
+    double omega, lambda;   /* the semi-axes of the spheroid: x and y, and z                                          */
+    const double* d_p;      /* CAF_LOP_LIST: [P], shared by every job                                                 */
+} caf_lop_desc;
+/* d_jobs (B, 16).  d_range (B, 2) = (lo, hi) of each job, read for CAF_LOP_LINSPACE and CAF_LOP_CHEBYSHEV.  Outputs, each optional,
+ * one entry per (job, sample): d_count (B, P) int32, the number of zeros, 0..4; d_phi (B, P, 4), the zeros ascending in
+ * (-pi, pi], then NaN; d_xyz (B, P, 4, 3) = q(phi); d_latlon (B, P, 4, 2), geodetic degrees of a point of the surface,
+ * latitude = atan2(z / lambda^2, hypot(x, y) / omega^2), longitude = atan2(y, x); d_p_out (B, P), the parameter of the sample.
+ * One thread per (job, sample).  Refused: NULL desc or jobs, unknown kind or spacing, semi-axes not finite and positive, B < 1,
+ * P < 1, B P beyond one launch, CAF_LOP_LIST without d_p, the other spacings without d_range. */
+CAF_EXPORT int32_t caf_lop_points(const caf_lop_desc* desc, const double* d_jobs, int64_t B, const double* d_range, int32_t* d_count,
+                                  double* d_phi, double* d_xyz, double* d_latlon, double* d_p_out, void* stream);
+/* The interval of [p_min, p_max] of each job on which g has a zero, one wave per job: round 0 tries `width` parameters
+ * p_min + i (p_max - p_min) / (width - 1); every later round tries `width` parameters strictly inside the bracket (a, b) between the
+ * first (last) parameter with a zero and its neighbour without, a + (i + 1) (b - a) / (width + 1).  d_range (B, 2): the smallest and
+ * the largest parameter found to have a zero, each a parameter at which caf_lop_points finds one too (the same device function);
+ * d_status (B) int32.  Both optional.  Refused: as above, without P, spacing and d_p. */
+CAF_EXPORT int32_t caf_lop_range(const caf_lop_desc* desc, const double* d_jobs, int64_t B, double* d_range, int32_t* d_status,
+                                 void* stream);
+/* samples per workgroup of caf_lop_points, jobs per workgroup of caf_lop_range, and the number and width of its search rounds */
+CAF_EXPORT int32_t caf_lop_geometry(int32_t* samples_per_workgroup, int32_t* jobs_per_workgroup, int32_t* rounds, int32_t* width);
+
 /* ---- Viterbi sequence detection (viterbiDemodClasses.py: ViterbiDemodulator, BurstyViterbiDemodulator).  Added after ABI 1.10
  * without a version bump, detected by symbol.  Everything is float64.  With A states, T pretransitions per state, L sources:
  *   P_n[m] = sum_i exp(-j omegas[i] (n up + m)) pulses[i][m], m < pulselen, and the signal of a symbol sequence g is

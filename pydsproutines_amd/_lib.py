@@ -159,6 +159,18 @@ class CafLocateDesc(ct.Structure):
     ]
 
 
+class CafLopDesc(ct.Structure):
+    _fields_ = [
+        ("kind", ct.c_int32),
+        ("spacing", ct.c_int32),
+        ("P", ct.c_int32),
+        ("reserved", ct.c_int32),
+        ("omega", ct.c_double),
+        ("lambda_", ct.c_double),
+        ("d_p", ct.c_void_p),
+    ]
+
+
 class CafViterbiDesc(ct.Structure):
     _fields_ = [
         ("num_states", ct.c_int32),
@@ -220,6 +232,9 @@ CAF_LOCATE_FD = 2
 CAF_LOCATE_TDFD = 3
 CAF_CRB_RANGE, CAF_CRB_RANGE_SUM, CAF_CRB_RANGE_DIFF, CAF_CRB_RATE_DIFF, CAF_CRB_AOA3D = 1, 2, 3, 4, 5
 CAF_CRB_FREE, CAF_CRB_FIXED, CAF_CRB_RADIAL, CAF_CRB_WGS84 = 0, 1, 2, 3
+CAF_LOP_HYPERBOLOID, CAF_LOP_SPHERE = 0, 1
+CAF_LOP_LIST, CAF_LOP_LINSPACE, CAF_LOP_CHEBYSHEV = 0, 1, 2
+CAF_LOP_FOUND, CAF_LOP_NO_CURVE = 0, 1
 
 CAF_DEMOD_LOCK_EIG = 0
 CAF_DEMOD_LOCK_POWERSUM = 1
@@ -321,6 +336,9 @@ _SIGNATURES = {
     "caf_locate_rtt_geometry": [ct.POINTER(_I32), ct.POINTER(_I32)],
     "caf_crb_map": [ct.POINTER(CafLocateDesc), _P, _I64, _P, _I32, _I32, ct.POINTER(ct.c_double), _P, _P, _P, _P, _P, _P, _P, _P],
     "caf_crb_map_geometry": [ct.POINTER(_I32), ct.POINTER(_I32), ct.POINTER(ct.c_double)],
+    "caf_lop_points": [ct.POINTER(CafLopDesc), _P, _I64, _P, _P, _P, _P, _P, _P, _P],
+    "caf_lop_range": [ct.POINTER(CafLopDesc), _P, _I64, _P, _P, _P],
+    "caf_lop_geometry": [ct.POINTER(_I32)] * 4,
     "caf_viterbi_table": [_P, _P, _I32, _I32, _I32, _I32, _P, _P],
     "caf_viterbi_demod": [ct.POINTER(CafViterbiDesc), _P],
     "caf_viterbi_geometry": [ct.POINTER(_I32), ct.POINTER(_I32), ct.POINTER(_I32)],

@@ -24,24 +24,36 @@ the device projects d off it in two passes (one pass would lose the residual's d
 ``gridSearchBlindLinearRTT`` is the reference's: unweighted, the sigmas ignored, the cost in s^2.  Where the reference returns
 0 (no more measurements than unknowns, or times that do not span {1, t}), these raise ValueError.
 
-Not provided: ``plot``, ``SatellitePairTDFDMixin`` (needs skyfield and sgp4), the hyperbola helpers, the tangent-plane functions
+Lines of position (``linesOfPosition``, ``rangeCircles``): the curve on the WGS84 ellipsoid where ONE measured range difference,
+or one measured range, is satisfied, for B rows of a peak table at once.  ``caf_lop_range`` (csrc/caf_lop.hip) finds the interval
+of the sheet's (or the sphere's) parameter on which the curve exists, ``caf_lop_points`` samples it, densely towards both tangent
+ends by default, and the host stitches the ordered polyline.  The small range, Doppler, gradient and tangent-plane helpers of the
+reference are host NumPy, as there.
+
+Not provided: ``plot``, ``SatellitePairTDFDMixin`` (needs an orbit propagator: skyfield and sgp4), ``hyperbolaGradDesc`` and
+``generateHyperbolaXY`` (they step along the curve with scipy.optimize; the closed form of hyperboloidRoutines.py supersedes them),
 and the blind RTT bound as a device map.  There is no CPU path: without a GPU every search raises RuntimeError (argument checks
 come first).  The CRB functions are host NumPy, as in the reference; ``crbMap`` of the TD, TDFD and RTT mixins evaluates them at
 every grid point on the device (crbRoutines.py).
 """
 
 import ctypes as ct
+from enum import Enum
 
 import numpy as np
 
 from . import _lib
+from . import hyperboloidRoutines as _H
 from .devarray import DeviceArray, asarray, empty
 
 __all__ = ["gridSearchTDOA", "gridSearchFDOA", "gridSearchTDOA_direct", "gridSearchTDFD_direct", "gridSearchTDOA_gpu",
            "latlongrid_to_ecef", "calcCRB_TD", "calcCRB_TDFD", "projectCRBtoEllipse", "GridLocalizer", "LatLonGridLocalizer",
            "TDMixin", "TDFDMixin", "LatLonGridLocalizerTD", "LatLonGridLocalizerTDFD", "locate_geometry", "gridSearchRTT_direct",
            "gridSearchBlindLinearRTT", "calcCRB_BlindLinearRTT", "RTTMixin", "BlindRTTMixin", "LatLonGridLocalizerRTT",
-           "LatLonGridLocalizerBlindRTT", "locate_rtt_geometry"]
+           "LatLonGridLocalizerBlindRTT", "locate_rtt_geometry", "WGS84Coefficients", "get_wgs84_tangent_plane_normal",
+           "get_wgs84_tangent_plane_north_east", "calculateRangeRate", "calculateDoppler", "rangeOfArrival", "rangeDifferenceOfArrival",
+           "rangeOfArrivalGradient", "hyperboloidGradient", "hyperbolaTangentXY", "removeDownlinkRangeDiff", "removeDownlinkDopplerDiff",
+           "linesOfPosition", "rangeCircles", "LinesOfPosition"]
 
 LIGHTSPD = 299792458.0
 WGS84_A = 6378137.0            # the two defining constants of WGS84: semi-major axis (m) ...
@@ -804,3 +816,148 @@ class LatLonGridLocalizerBlindRTT(BlindRTTMixin, LatLonGridLocalizer):
 
 class LatLonGridLocalizerTDFD(TDFDMixin, LatLonGridLocalizer):
     pass
+
+
+# ---- the reference's small helpers (host NumPy) ------------------------------------------------------------------------------------
+class WGS84Coefficients(Enum):
+    a = 6378137.0
+    b = 6356752.314245
+
+
+def get_wgs84_tangent_plane_normal(ecef_pos):
+    """The gradient of the WGS84 ellipsoid's function at an ECEF position (length 3): the normal of its tangent plane there.  The
+    reference squares the Enum members themselves and raises TypeError; the members' values are used here."""
+    if not isinstance(ecef_pos, np.ndarray):
+        raise TypeError("Must be numpy array.")
+    a, b = WGS84Coefficients.a.value, WGS84Coefficients.b.value
+    return np.array([2 / a ** 2, 2 / a ** 2, 2 / b ** 2]) * ecef_pos
+
+
+def get_wgs84_tangent_plane_north_east(ecef_normal):
+    """unit vectors (north, east) of the tangent plane whose normal is ecef_normal: east = z x n, north = n x east"""
+    east = np.cross(np.array([0, 0, 1]), ecef_normal)
+    east = east / np.linalg.norm(east)
+    north = np.cross(ecef_normal, east)
+    return north / np.linalg.norm(north), east
+
+
+def calculateRangeRate(tx_x, rx_x, tx_xdot=np.zeros(3), rx_xdot=np.zeros(3)):
+    """The rate of the range from transmitter(s) to receiver(s): the receiver's speed along the wave's direction minus the
+    transmitter's.  Positions are one vector or N x 3; a velocity is one vector of length 3.  Returns N values."""
+    u = np.asarray(rx_x) - np.asarray(tx_x)
+    if u.ndim == 1:
+        u = u.reshape((1, 3))
+    elif u.shape[1] != 3:
+        raise ValueError("Direction vectors (rx_x - tx_x) must be a Nx3 array.")
+    u = u / np.linalg.norm(u, axis=1).reshape((-1, 1))
+    return np.dot(u, rx_xdot) - np.dot(u, tx_xdot)
+
+
+def calculateDoppler(f0, tx_x, rx_x, tx_xdot=np.zeros(3), rx_xdot=np.zeros(3), lightspd=LIGHTSPD):
+    """the Doppler shift of a carrier f0: a growing range lowers the frequency"""
+    return -calculateRangeRate(tx_x, rx_x, tx_xdot, rx_xdot) / lightspd * f0
+
+
+def rangeOfArrival(x, s_i):
+    """|x - s_i| over the last axis, for any two shapes that broadcast"""
+    return np.linalg.norm(x - s_i, axis=-1)
+
+
+def rangeDifferenceOfArrival(x, s1, s2):
+    return rangeOfArrival(x, s2) - rangeOfArrival(x, s1)
+
+
+def rangeOfArrivalGradient(x, s_i):
+    """the unit vector from s_i to x (one point)"""
+    return (x - s_i) / rangeOfArrival(x, s_i)
+
+
+def hyperboloidGradient(x, s1, s2, rangediff):
+    """the gradient at x of (|x - s2| - |x - s1| - rangediff)^2"""
+    miss = rangeOfArrival(x, s2) - rangeOfArrival(x, s1) - rangediff
+    return 2 * miss * (rangeOfArrivalGradient(x, s2) - rangeOfArrivalGradient(x, s1))
+
+
+def hyperbolaTangentXY(pt, s1, s2, rangediff):
+    """a unit vector in the plane z = const that is orthogonal to hyperboloidGradient at pt"""
+    g = hyperboloidGradient(pt, s1, s2, rangediff)
+    h = np.array([0.0, 1.0, 0.0]) if g[1] == 0.0 else np.array([1.0, -g[0] / g[1], 0.0])
+    return h / np.linalg.norm(h)
+
+
+def removeDownlinkRangeDiff(rx, s1x, s2x, rangediff):
+    """(rangediff without the downlink's share, the downlink's share): the receiver rx hears both satellites"""
+    down = rangeDifferenceOfArrival(rx, s1x, s2x)
+    return rangediff - down, down
+
+
+def removeDownlinkDopplerDiff(rx, s1x, s2x, s1v, s2v, fdoa, f0down, lightspd=LIGHTSPD):
+    """(fdoa without the downlink's share, the downlink's share) at the downlink carrier f0down"""
+    rdot1 = calculateRangeRate(s1x, rx, tx_xdot=s1v)
+    rdot2 = calculateRangeRate(s2x, rx, tx_xdot=s2v)
+    down = (rdot1 - rdot2) * f0down / lightspd
+    return fdoa - down, down
+
+
+# ---- lines of position on the WGS84 ellipsoid (csrc/caf_lop.hip) ----------------------------------------------------------------------
+LOP_OK, LOP_NO_CURVE, LOP_NO_SURFACE = 0, 1, 2
+
+
+class LinesOfPosition:
+    """What linesOfPosition and rangeCircles return.  xyz (B, 2 P, 3) ECEF and latlon (B, 2 P, 2) degrees: the ordered polyline of
+    every row, NaN where a sample has no point; status (B,): LOP_OK, LOP_NO_CURVE (the surface misses the ellipsoid) or
+    LOP_NO_SURFACE (|rangediff| >= the baseline, a radius that is not positive, or a row that is not finite); ranges (B, 2): the
+    interval of the parameter that was sampled; p (B, P): the parameters; count (B, P): the zeros of every sample.  With
+    device=True, ``points`` holds the kernel's own DeviceArrays (hyperboloidRoutines.LopPoints) and xyz, latlon are None."""
+
+    def __init__(self, xyz, latlon, status, ranges, p, count, points=None):
+        self.xyz, self.latlon, self.status, self.ranges, self.p, self.count, self.points = xyz, latlon, status, ranges, p, count, points
+
+
+def _lines(kind, jobs, ok, numPts, spacing, ranges, omega, lmbda, device):
+    numPts = int(numPts)
+    if numPts < 1:
+        raise ValueError("numPts must be at least 1.")
+    if spacing not in ("chebyshev", "linspace"):
+        raise ValueError("spacing must be 'chebyshev' or 'linspace'.")
+    b = jobs.shape[0]
+    if ranges is not None:
+        ranges = np.ascontiguousarray(ranges, dtype=np.float64)
+        if ranges.shape != (b, 2):
+            raise ValueError("ranges must be B x 2.")
+    _lib.require_device()
+    d_jobs = asarray(jobs)
+    if ranges is None:
+        d_range, d_status = _H.lop_range(kind, d_jobs, omega, lmbda)
+        status = d_status.get().astype(np.int64)
+    else:
+        d_range, status = asarray(ranges), np.zeros(b, np.int64)
+    status[~ok] = LOP_NO_SURFACE
+    pts = _H.lop_points(kind, d_jobs, omega, lmbda, ranges=d_range, num=numPts, spacing=spacing)
+    rng = d_range.get()
+    if device:
+        return LinesOfPosition(None, None, status, rng, None, None, pts)
+    out = pts.get()
+    if ranges is not None:
+        status[(status == LOP_OK) & ~np.any(out["count"] > 0, axis=1)] = LOP_NO_CURVE
+    return LinesOfPosition(_H.polyline(out["count"], out["xyz"]), _H.polyline(out["count"], out["latlon"]), status, rng, out["p"], out["count"])
+
+
+def linesOfPosition(s1, s2, rangediff, numPts=256, spacing="chebyshev", ranges=None, device=False, omega=WGS84_A,
+                    lmbda=WGS84Coefficients.b.value):
+    """The lines of position of B range differences |x - s2| - |x - s1| = rangediff (s1, s2: B x 3 ECEF; rangediff: B) on the
+    spheroid (WGS84 by default): a LinesOfPosition.  Every sheet is sampled at numPts values of its parameter v, spread over the
+    interval on which the curve exists (found on the device, or ``ranges`` (B, 2) if given); 'chebyshev' packs the samples
+    towards both tangent ends, 'linspace' spaces them evenly with one at each end.  Each v gives up to two points, one on
+    either side of the sheet's axis: the polyline has 2 numPts rows.  A row with |rangediff| >= |s2 - s1| has no surface: its
+    status says so and its curve is NaN; nothing is raised, one bad row does not lose a batch."""
+    jobs, ok = _H.hyperboloid_jobs(s1, s2, rangediff, omega)
+    return _lines("hyperboloid", jobs, ok, numPts, spacing, ranges, omega, lmbda, device)
+
+
+def rangeCircles(centres, radii, numPts=256, spacing="chebyshev", ranges=None, device=False, omega=WGS84_A,
+                 lmbda=WGS84Coefficients.b.value):
+    """The lines of position of B ranges |x - centre| = radius (centres: B x 3 ECEF; radii: B) on the spheroid, as
+    linesOfPosition returns them; the parameter is the sphere's polar angle from the z axis."""
+    jobs, ok = _H.sphere_jobs(centres, radii)
+    return _lines("sphere", jobs, ok, numPts, spacing, ranges, omega, lmbda, device)
