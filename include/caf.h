@@ -991,6 +991,49 @@ CAF_EXPORT int32_t caf_cluster_scores(const double* d_x, int64_t P, int64_t pitc
 CAF_EXPORT int32_t caf_cluster_geometry(int64_t pitch, int32_t D, int32_t kmax, int32_t* form, int32_t* threads, int32_t* tile,
                                         int64_t* lloyd_lds_bytes, int64_t* sil_lds_bytes, int64_t* scratch_bytes);
 
+/* ---- tone spectra, the dense DFT, integer-multiple FFTs and the burst FFT (spectralRoutines.py: toneSpectrum :663-679,
+ * toneSpec_kernel / toneSpecMulti_kernel :394-571, dft :637-659, IntegerMultipleFFT :128-232; burstyRoutines.py: burstFFT :14-36).
+ * Added after ABI 1.10 without a version bump, detected by symbol (csrc/caf_spectral.hip).  No atomics; every sum has a fixed
+ * order that depends on the row's own sizes alone, so a row of a batch holds the bits it has when run alone.  Every violation
+ * (NULL, sizes below 1 or above the stated limits, fs zero or not finite, a pointer not aligned to its element) returns
+ * CAF_ERR_INVALID with a caf_last_error() text before any launch.  Inputs and outputs must not overlap.  Scratch, where an
+ * entry point needs any (caf_dft_rows on a cut row, caf_integer_multiple_fft with reorder), comes from the pool's owner; the tone
+ * spectra and caf_burst_fft take none: they work in the caller's output.
+ *
+ * Tone spectra, float64 throughout: d_out (m, num_freqs) complex128,
+ *   out[i][k] = -j A_i (1 - exp(-j 2 pi (f_k - f0_i) N / fs)) / (2 pi (f_k - f0_i) / fs) exp(j phi_i)
+ * -- the reference's continuous-time formula, not the Dirichlet sum.  (f_k - f0_i) N / fs is reduced to a fraction of a turn before
+ * the sine and cosine.  Where f_k == f0_i exactly the limit A_i N exp(j phi_i) is returned (the reference: NaN).  d_f0, d_phi,
+ * d_A: m doubles each; m has no upper limit (the reference: 256).  caf_tone_spectrum_one takes the three as scalars (m = 1) and
+ * runs the same kernel: its output holds the bits of the multi form's row with the same values.  1 <= N <= 2^53. */
+CAF_EXPORT int32_t caf_tone_spectrum(const double* d_f0, const double* d_phi, const double* d_A, int64_t m, const double* d_freqs,
+                                     int64_t num_freqs, double fs, int64_t N, double* d_out, void* stream);
+CAF_EXPORT int32_t caf_tone_spectrum_one(double f0, double phi, double A, const double* d_freqs, int64_t num_freqs, double fs, int64_t N,
+                                         double* d_out, void* stream);
+/* out[r][k] = sum_n x[r][n] exp(-j 2 pi f_k n / fs): d_x (rows, len) complex64 (c128 = 0) or complex128 (c128 = 1), d_freqs
+ * num_freqs doubles in any order and of any size, d_out (rows, num_freqs) complex128; products and sums in float64.  Pooled
+ * scratch (the segments' partial sums) when len is cut: rows * segments * num_freqs complex128. */
+CAF_EXPORT int32_t caf_dft_rows(const void* d_x, int32_t c128, int64_t rows, int64_t len, const double* d_freqs, int64_t num_freqs,
+                                double fs, double* d_out, void* stream);
+/* frequencies per workgroup T; samples per LDS chunk C; samples per Horner block R, the interval at which the phase is seeded
+ * again from an exactly reduced product (the error bound grows with R, not with len); the largest len; the number of workgroups
+ * per row W the cut of len aims for: with tiles = ceil(num_freqs / T) and chunks = ceil(len / C), len is cut into
+ * ceil(chunks / ceil(chunks / min(chunks, ceil(W / tiles)))) segments of whole chunks, added in segment order by a second launch
+ * when there is more than one.  Every output is optional (NULL).  No device work. */
+CAF_EXPORT int32_t caf_dft_geometry(int32_t* freqs_per_workgroup, int32_t* samples_per_chunk, int32_t* reseed_interval, int64_t* max_len,
+                                    int32_t* split_workgroups);
+/* d_x (rows, len) complex64.  reorder = 0: d_out (rows, multiple, len), row i of a matrix the len-point transform of
+ * x[n] exp(-j 2 pi i n / (multiple len)); reorder != 0: d_out (rows, multiple len), the transform of x zero-padded to
+ * multiple len.  Three steps: the shifted copies (the phase formed from the integer i n, not by recurrence), the row transform in
+ * place (complex64, rocFFT under the plan cache), and for reorder the tiled transpose (multiple, len) -> (len, multiple), for which
+ * the first two steps work in pooled scratch of the output's size.  multiple * len < 2^31. */
+CAF_EXPORT int32_t caf_integer_multiple_fft(const float* d_x, int64_t rows, int64_t len, int32_t multiple, int32_t reorder, float* d_out,
+                                            void* stream);
+/* d_x (rows, len) complex64 -> d_out (rows, length) complex64: the row zero-padded to alpha * length, alpha = ceil(len / length),
+ * its alpha pieces of `length` samples added (float64, in order of the pieces, rounded once) and the sum transformed.  len < length
+ * is plain zero padding. */
+CAF_EXPORT int32_t caf_burst_fft(const float* d_x, int64_t rows, int64_t len, int64_t length, float* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -373,6 +373,12 @@ _SIGNATURES = {
     "caf_kmeans_seed": [_P, _I64, _I64, _I32, _P, _P, ct.POINTER(_I32), ct.POINTER(_I32), _I64, _I32, _P, _P, _P, _P],
     "caf_kmeans_lloyd": [_P, _I64, _I64, _I32, _P, _P, ct.POINTER(_I32), ct.POINTER(_I32), _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P],
     "caf_cluster_scores": [_P, _I64, _I64, _I32, _P, ct.POINTER(_I32), ct.POINTER(_I32), _I64, _I32, _P, ct.POINTER(_I32), _I64, ct.c_uint32, _P, _P, _P, _P, _P],
+    "caf_tone_spectrum": [_P, _P, _P, _I64, _P, _I64, ct.c_double, _I64, _P, _P],
+    "caf_tone_spectrum_one": [ct.c_double, ct.c_double, ct.c_double, _P, _I64, ct.c_double, _I64, _P, _P],
+    "caf_dft_rows": [_P, _I32, _I64, _I64, _P, _I64, ct.c_double, _P, _P],
+    "caf_dft_geometry": [ct.POINTER(_I32), ct.POINTER(_I32), ct.POINTER(_I32), ct.POINTER(_I64), ct.POINTER(_I32)],
+    "caf_integer_multiple_fft": [_P, _I64, _I64, _I32, _I32, _P, _P],
+    "caf_burst_fft": [_P, _I64, _I64, _I64, _P, _P],
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

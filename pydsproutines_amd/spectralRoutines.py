@@ -3,6 +3,10 @@ pybinds/ippCZT/CZT.cpp).  The cached Bluestein constants are computed once on th
 float64 and cast to complex64 exactly as the reference does (spectralRoutines.py:335-351,
 CZT.cpp:89-140); every transform runs on the GPU through ``caf_czt_run_many``
 (x*aa -> rocFFT -> *fv -> inverse rocFFT -> slice*ww).
+
+The other half of the reference's module follows them: the tone spectra (spectralRoutines.py:394-571, 663-679), the dense DFT at
+arbitrary frequencies (:637-659) and IntegerMultipleFFT (:128-232), all through csrc/caf_spectral.hip.  Not provided:
+``czt_scipy`` and the plots.
 """
 
 import ctypes as ct
@@ -10,7 +14,7 @@ import ctypes as ct
 import numpy as np
 
 from . import _lib
-from .devarray import DeviceArray, asarray, empty, requireDeviceArray, requireDtype
+from .devarray import DeviceArray, asarray, empty, requireDeviceArray, requireDtype, zeros
 
 
 def _smooth(n, max_prime):
@@ -166,5 +170,192 @@ def cupyDotTonesScaling(f0, fstep, numFreqs, src):
     return out
 
 
+# ---- tone spectra (ref: spectralRoutines.py:394-571, 663-679; csrc/caf_spectral.hip: k_tone_spectrum) ------------------------
+
+def _p(a):
+    return ct.c_void_p(a.ptr)
+
+
+def _download(out, stream):
+    """the host copy of a result queued on ``stream``: the stream is drained first (the download runs on the null stream, which a
+    caller's stream is not ordered with), while the caller still holds the uploaded input"""
+    if stream is not None:
+        _lib.check(_lib.load().caf_stream_sync(stream), "caf_stream_sync")
+    return out.get()
+
+
+def _f64_vector(name, a):
+    requireDeviceArray(a)
+    requireDtype(np.float64, a)
+    if a.ndim != 1:
+        raise ValueError("%s must be 1-dim" % name)
+    return a
+
+
+def toneSpectrum_gpu(f0, d_freqs, fs, N, phi=0.0, A=1.0, stream=None):
+    """ref: spectralRoutines.py:438-452 (`toneSpec_kernel`).  The spectrum of a tone of frequency f0, phase phi and amplitude A
+    over N samples at the float64 frequencies ``d_freqs``: device array in, complex128 device array out,
+
+        -j A (1 - exp(-j 2 pi (f - f0) N / fs)) / (2 pi (f - f0) / fs) exp(j phi)
+
+    in float64, the phase reduced to a fraction of a turn before the sine and cosine.  Where f == f0 exactly the limit
+    A N exp(j phi) is returned (upstream: NaN)."""
+    _f64_vector("d_freqs", d_freqs)
+    out = empty(d_freqs.shape, np.complex128)
+    if out.size:
+        _lib.check(_lib.load().caf_tone_spectrum_one(float(f0), float(phi), float(A), _p(d_freqs), d_freqs.size, float(fs), int(N),
+                                                     _p(out), stream), "caf_tone_spectrum_one")
+    return out
+
+
+def toneSpectrumMulti_gpu(d_f0List, d_freqs, fs, N, d_phiList, d_AList, stream=None):
+    """ref: spectralRoutines.py:541-571 (`toneSpecMulti_kernel`).  (len(d_f0List), len(d_freqs)) complex128: row i is
+    ``toneSpectrum_gpu(f0[i], d_freqs, fs, N, phi[i], A[i])`` bit for bit.  Any number of parameter sets (upstream: at most 256)."""
+    _f64_vector("d_freqs", d_freqs)
+    for name, a in (("d_f0List", d_f0List), ("d_phiList", d_phiList), ("d_AList", d_AList)):
+        _f64_vector(name, a)
+        if a.size != d_f0List.size:
+            raise ValueError("d_f0List, d_phiList and d_AList must have one length")
+    out = empty((d_f0List.size, d_freqs.size), np.complex128)
+    if out.size:
+        _lib.check(_lib.load().caf_tone_spectrum(_p(d_f0List), _p(d_phiList), _p(d_AList), d_f0List.size, _p(d_freqs), d_freqs.size,
+                                                 float(fs), int(N), _p(out), stream), "caf_tone_spectrum")
+    return out
+
+
+def toneSpectrum(f0, freqs, fs, N, phi=0, A=1.0):
+    """ref: spectralRoutines.py:663-679.  Host arrays in, host complex128 out, computed on the GPU (``toneSpectrum_gpu``).  f0, phi
+    and A are scalars as upstream's, or arrays of one length m: then the result is (m, len(freqs))."""
+    freqs = np.asarray(freqs, np.float64)
+    d_freqs = asarray(np.ascontiguousarray(freqs.reshape(-1)))
+    if np.ndim(f0) == 0 and np.ndim(phi) == 0 and np.ndim(A) == 0:
+        return toneSpectrum_gpu(f0, d_freqs, fs, N, phi, A).get().reshape(freqs.shape)
+    f0l, phil, Al = (np.ascontiguousarray(a) for a in np.broadcast_arrays(*(np.atleast_1d(np.asarray(v, np.float64)) for v in (f0, phi, A))))
+    if f0l.ndim != 1:
+        raise ValueError("f0, phi and A must be scalars or 1-dim")
+    return toneSpectrumMulti_gpu(asarray(f0l), d_freqs, fs, N, asarray(phil), asarray(Al)).get().reshape((f0l.size,) + freqs.shape)
+
+
+# ---- the dense DFT at arbitrary frequencies (ref: spectralRoutines.py:637-659; csrc/caf_spectral.hip: k_dft, k_dft_fold) ---------
+
+def dft_geometry():
+    """(T, C, R, max_len, W) of ``caf_dft_geometry``: frequencies per workgroup, samples per LDS chunk, the re-seed interval of the
+    phase, the largest row length, and the workgroups per row that the cut of a long row aims for."""
+    t, c, r, w = ct.c_int32(), ct.c_int32(), ct.c_int32(), ct.c_int32()
+    mx = ct.c_int64()
+    _lib.check(_lib.load().caf_dft_geometry(ct.byref(t), ct.byref(c), ct.byref(r), ct.byref(mx), ct.byref(w)), "caf_dft_geometry")
+    return t.value, c.value, r.value, mx.value, w.value
+
+
+def dftRows(d_x, d_freqs, fs, stream=None):
+    """out[r][k] = sum_n x[r][n] exp(-j 2 pi freqs[k] n / fs): the device, batched form of ``dft``.  ``d_x``: complex64 or complex128
+    device array, (rows, len) or (len,); ``d_freqs``: float64 device array, in any order, repeated, outside +-fs/2 or not.  Returns a
+    complex128 device array (rows, num_freqs), or (num_freqs,) for 1-dim input; products and sums are float64."""
+    requireDeviceArray(d_x)
+    requireDtype((np.complex64, np.complex128), d_x)
+    _f64_vector("d_freqs", d_freqs)
+    if d_x.ndim not in (1, 2):
+        raise ValueError("d_x must be 1-dim or 2-dim")
+    rows, length = (1, d_x.shape[0]) if d_x.ndim == 1 else d_x.shape
+    shape = (d_freqs.size,) if d_x.ndim == 1 else (rows, d_freqs.size)
+    if rows * length == 0:
+        return zeros(shape, np.complex128)
+    out = empty(shape, np.complex128)
+    if out.size:
+        _lib.check(_lib.load().caf_dft_rows(_p(d_x), int(d_x.dtype == np.complex128), rows, length, _p(d_freqs), d_freqs.size, float(fs),
+                                            _p(out), stream), "caf_dft_rows")
+    return out
+
+
+def dft(x, freqs, fs):
+    """ref: spectralRoutines.py:637-659.  Host arrays in upstream's signature, host complex128 out; the sums run on the GPU in
+    float64 (``dftRows``).  A complex64 ``x`` is uploaded as it is, anything else as complex128."""
+    x = np.asarray(x)
+    if x.ndim != 1:
+        raise ValueError("x must be 1-dim")
+    x = np.ascontiguousarray(x, np.complex64 if x.dtype == np.complex64 else np.complex128)
+    freqs = np.ascontiguousarray(np.asarray(freqs, np.float64).reshape(-1))
+    return dftRows(asarray(x), asarray(freqs), fs).get()
+
+
+# ---- IntegerMultipleFFT (ref: spectralRoutines.py:128-232; csrc/caf_spectral.hip: k_imfft_shift, k_imfft_transpose) --------------
+
+class IntegerMultipleFFT:
+    """ref: spectralRoutines.py:128-232.  FFTs of ``multiple`` times the input length without the padded transform: the input is
+    shifted by i / multiple of a bin for i = 0 .. multiple - 1 and each copy transformed at its own length.
+
+    The transform runs on the GPU in complex64 through the row-FFT machinery (as ``CZTCached`` does) and the result is complex64,
+    whatever ``dtype`` is: ``dtype`` governs ``getTones()`` only, the (multiple, N) table computed on the host in float64 exactly as
+    upstream computes it.  The device forms its phases itself, from the integer i n."""
+
+    def __init__(self, dtype=np.complex128, multiple: int = None, unpadLength: int = None):
+        self.dtype = dtype
+        self._M = None
+        self._tones = None
+        self.setMultiple(multiple)
+        self.setUnpadLength(unpadLength)
+        if self._multiple is not None and self._N is not None:
+            self.computeInternals()
+
+    def computeInternals(self):
+        self._M = self._multiple * self._N
+        self._tones = np.array(
+            [np.exp(-1j * 2 * np.pi * i / self._multiple * np.arange(self._N) / self._N) for i in np.arange(self._multiple)]
+        ).astype(self.dtype)
+
+    def _run(self, d_x, rows, reorder, stream):
+        multiple, n = self._tones.shape
+        shape = (rows, multiple * n) if reorder else (rows, multiple, n)
+        out = empty(shape, np.complex64)
+        if out.size:
+            _lib.check(_lib.load().caf_integer_multiple_fft(_p(d_x), rows, n, multiple, int(bool(reorder)), _p(out), stream),
+                       "caf_integer_multiple_fft")
+        return out
+
+    def _check(self, x, ndim):
+        if not isinstance(x, DeviceArray):
+            x = np.asarray(x)
+        if x.ndim != ndim:
+            raise Exception("Requires %d-dim array." % ndim)
+        if x.shape[-1] != self._N:
+            raise Exception("Input length does not correspond to internal value. Please call setUnpadLength().")
+        if self._tones is None:  # (upstream multiplies by its missing table here: numpy's TypeError, with its text)
+            raise TypeError("unsupported operand type(s) for *: 'complex' and 'NoneType'")
+        if self._tones.shape != (self._multiple, self._N):
+            raise Exception("Internal values have changed. Please call computeInternals().")
+        if isinstance(x, DeviceArray):
+            requireDtype(np.complex64, x)
+            return x, True
+        return asarray(np.ascontiguousarray(x, np.complex64)), False
+
+    def fft(self, x, reorder: bool = False, stream=None):
+        """The (multiple, N) matrix of transforms of x[n] exp(-j 2 pi i n / (multiple N)), or with ``reorder`` the length multiple N
+        array equal to ``np.fft.fft(x, n=multiple * N)``; complex64.  A host array gives a host result, a complex64 ``DeviceArray``
+        a device result.  With a host array and a ``stream`` the call drains the stream before it downloads and returns."""
+        d_x, dev = self._check(x, 1)
+        out = self._run(d_x, 1, reorder, stream)
+        out = out.reshape(out.shape[1:])
+        return out if dev else _download(out, stream)
+
+    def fftMany(self, xmany, reorder: bool = False, stream=None):
+        """``fft`` of every row of a (rows, N) array: (rows, multiple, N), or (rows, multiple N) with ``reorder``."""
+        d_x, dev = self._check(xmany, 2)
+        out = self._run(d_x, d_x.shape[0], reorder, stream)
+        return out if dev else _download(out, stream)
+
+    def setMultiple(self, multiple: int):
+        self._multiple = multiple
+
+    def setUnpadLength(self, unpadLength: int):
+        self._N = unpadLength
+
+    def getPaddedLength(self):
+        return self._M
+
+    def getTones(self):
+        return self._tones
+
+
 __all__ = ["next_fast_len", "prev_fast_len", "CZTCachedGPU", "CZTCached", "pbIppCZT32fc", "czt", "cupyDotTonesScaling",
+           "toneSpectrum", "toneSpectrum_gpu", "toneSpectrumMulti_gpu", "dft", "dftRows", "dft_geometry", "IntegerMultipleFFT",
            "DeviceArray"]
