@@ -20,9 +20,10 @@
 //                    (blockIdx.y); records staged in LDS CRB_C = 64 at a time and read back as broadcasts; the kind of a record
 //                    is one value for the whole wave (v_readfirstlane), so the switch on it is a scalar branch and a table of
 //                    range differences never reads a velocity.  After the records every thread finishes its own points.
-//   k_crb_fold       the workgroups' (min, index) and (max, index) partials of each set -> one pair each per set.
-// Arg min and arg max of rms as in caf_locate.hip: first of equal values, NaN never wins, through caf_wave.h on the value and on
-// the negated value, partials in pooled scratch, folded in increasing order of workgroup; no atomics.
+//   k_grid_fold<true>  (caf_grid.h) the workgroups' (min, index) and (max, index) partials of each set -> one pair each per set.
+// The point source, the sets, the stores and the extremes are the frame of caf_grid.h, shared with caf_locate.hip.
+// Arg min and arg max of rms as in caf_locate.hip: first of equal values, NaN never wins, through block_argmax and block_argmin of
+// caf_wave.h, partials in pooled scratch, folded in increasing order of workgroup; no atomics.
 //
 // The error count, in units of eps = 2^-53 (tests/crb_ref.py repeats it and forms the bound from it):
 //   u = a y, y = 1 / sqrt(a.a) by rsqrt_once: a is off by 1 per component relative to rho; y by 4 relative (1 from a, 1.5 from the
@@ -49,7 +50,7 @@
 #include <cstdint>
 
 #include "caf_internal.h"
-#include "caf_locate_dev.h"
+#include "caf_grid.h"
 #include "caf_wave.h"
 
 #pragma clang fp contract(off)
@@ -64,20 +65,11 @@ constexpr int CRB_P = CRB_T * CRB_PPT;  // points per workgroup
 constexpr int CRB_C = 64;               // records per LDS chunk (8 KiB)
 constexpr int CRB_REC = 16;             // doubles per record: s1(3) s2(3) v1(3) v2(3) w kind 0 0
 constexpr double CRB_SINGULAR = 0x1p-40;
-constexpr long long NO_INDEX = INT64_MAX;
 constexpr double WGS84_A = 6378137.0, WGS84_INV_F = 298.257223563;
 
 struct CrbNormal {
     double nx, ny, nz;  // CAF_CRB_FIXED
     double a2, b2;      // CAF_CRB_WGS84: the squared semi-axes
-};
-
-// where the partials of the two reductions go (all four or none)
-struct CrbParts {
-    double* min_v;
-    int64_t* min_i;
-    double* max_v;
-    int64_t* max_i;
 };
 
 // F += w J J^T
@@ -103,19 +95,15 @@ template <int SRC>
 __global__ __launch_bounds__(CRB_T) void k_crb_map(const LocSrc src, int64_t N, const double* __restrict__ rec, int64_t K,
                                                    const int64_t* __restrict__ set_starts, int constraint, const CrbNormal nrm,
                                                    double* __restrict__ crb, double* __restrict__ ell, void* __restrict__ rms,
-                                                   int rms_f32, const CrbParts parts) {
+                                                   int rms_f32, const GridParts parts) {  // (all four partials or none)
     __shared__ double s_rec[CRB_C * CRB_REC];
     __shared__ WaveSlots<CRB_T / 64, double, long long> s_lo, s_hi;
     const int tid = threadIdx.x;
     const int64_t base = (int64_t)blockIdx.x * CRB_P;
     const int set = blockIdx.y;
 
-    // the records of this set, clamped into the table whatever the offsets say
-    int64_t k0 = 0, k1 = K;
-    if (set_starts) {
-        k0 = std::min(std::max<int64_t>(set_starts[set], 0), K);
-        k1 = std::min(std::max<int64_t>(set_starts[set + 1], k0), K);
-    }
+    int64_t k0, k1;
+    set_records(set_starts, set, K, k0, k1);
 
     double px[CRB_PPT], py[CRB_PPT], pz[CRB_PPT], f[CRB_PPT][6];
     loc_points<SRC, CRB_T, CRB_PPT>(src, N, base, tid, px, py, pz);
@@ -284,59 +272,22 @@ __global__ __launch_bounds__(CRB_T) void k_crb_map(const LocSrc src, int64_t N, 
 #pragma unroll
                 for (int q = 0; q < 3; q++) ell[3 * o + q] = ok ? e3[q] : qnan;
             }
-            if (rms) {
-                if (rms_f32) ((float*)rms)[o] = (float)v;
-                else ((double*)rms)[o] = v;
-            }
+            if (rms) store_value(rms, rms_f32, o, v);
         }
     }
 
     if (parts.min_v) {
-        double lo = INFINITY, hi = -INFINITY;
-        long long li = NO_INDEX, hi_i = NO_INDEX;
-#pragma unroll
-        for (int j = 0; j < CRB_PPT; j++) {
-            const int64_t at = base + tid + j * CRB_T;
-            if (at < N && first_min(lo, li, val[j], (long long)at)) lo = val[j], li = at;
-            if (at < N && first_max(hi, hi_i, val[j], (long long)at)) hi = val[j], hi_i = at;
-        }
-        // the arg min as the arg max of the negated values (first_min and first_max agree on them)
-        lo = -lo;
-        block_argmax(s_lo, lo, li);
-        lo = -lo;
+        double lo, hi;
+        long long li, hi_i;
+        thread_first_min<CRB_T, CRB_PPT>(val, N, base, tid, lo, li);
+        thread_first_max<CRB_T, CRB_PPT>(val, N, base, tid, hi, hi_i);
+        block_argmin(s_lo, lo, li);
         block_argmax(s_hi, hi, hi_i);
         if (tid == 0) {
             const int64_t o = (int64_t)set * gridDim.x + blockIdx.x;
             parts.min_v[o] = lo, parts.min_i[o] = (int64_t)li;
             parts.max_v[o] = hi, parts.max_i[o] = (int64_t)hi_i;
         }
-    }
-}
-
-// the partials of set blockIdx.x (in increasing order of index) -> the set's extremes; nothing but NaN: (NaN, -1)
-__global__ __launch_bounds__(CRB_T) void k_crb_fold(const CrbParts parts, int64_t nparts, double* __restrict__ min_val,
-                                                    int64_t* __restrict__ min_idx, double* __restrict__ max_val,
-                                                    int64_t* __restrict__ max_idx) {
-    __shared__ WaveSlots<CRB_T / 64, double, long long> s_lo, s_hi;
-    const int64_t o = (int64_t)blockIdx.x * nparts;
-    double lo = INFINITY, hi = -INFINITY;
-    long long li = NO_INDEX, hi_i = NO_INDEX;
-    for (int64_t e = threadIdx.x; e < nparts; e += CRB_T) {
-        const double a = parts.min_v[o + e], b = parts.max_v[o + e];
-        const long long ai = (long long)parts.min_i[o + e], bi = (long long)parts.max_i[o + e];
-        if (first_min(lo, li, a, ai)) lo = a, li = ai;
-        if (first_max(hi, hi_i, b, bi)) hi = b, hi_i = bi;
-    }
-    lo = -lo;
-    block_argmax(s_lo, lo, li);
-    lo = -lo;
-    block_argmax(s_hi, hi, hi_i);
-    if (threadIdx.x == 0) {
-        const bool no_lo = li == NO_INDEX, no_hi = hi_i == NO_INDEX;
-        if (min_val) min_val[blockIdx.x] = no_lo ? (double)NAN : lo;
-        if (min_idx) min_idx[blockIdx.x] = no_lo ? (int64_t)-1 : (int64_t)li;
-        if (max_val) max_val[blockIdx.x] = no_hi ? (double)NAN : hi;
-        if (max_idx) max_idx[blockIdx.x] = no_hi ? (int64_t)-1 : (int64_t)hi_i;
     }
 }
 
@@ -356,12 +307,11 @@ int32_t caf_crb_map_geometry(int32_t* points_per_workgroup, int32_t* records_per
 int32_t caf_crb_map(const caf_locate_desc* desc, const double* d_records, int64_t K, const int64_t* d_set_starts, int32_t B,
                     int32_t constraint, const double* normal, double* d_crb, double* d_ellipse, void* d_rms, double* d_min_val,
                     int64_t* d_min_idx, double* d_max_val, int64_t* d_max_idx, void* stream) {
-    CAF_REQUIRE(desc != nullptr, "caf_crb_map: NULL descriptor");
-    CAF_REQUIRE(desc->cost_f32 == 0 || desc->cost_f32 == 1, "caf_crb_map: cost_f32 must be 0 or 1");
-    CAF_REQUIRE(K >= 1 && K <= ((int64_t)1 << 40), "caf_crb_map: the table needs at least one record");
-    CAF_REQUIRE(B >= 1 && B <= 65535 && (d_set_starts != nullptr || B == 1),
-                "caf_crb_map: 1 <= sets <= 65535, and more than one set needs set_starts");
-    CAF_REQUIRE((int64_t)B <= K, "caf_crb_map: every set needs at least one record");
+    LocSrc src;
+    int64_t N, tiles;
+    int rc;
+    if ((rc = grid_source("caf_crb_map", desc, CRB_T, CRB_P, &src, &N, &tiles))) return rc;
+    if ((rc = grid_sets_ok("caf_crb_map", desc, d_records, K, d_set_starts, B, 1))) return rc;
     CAF_REQUIRE(constraint == CAF_CRB_FREE || constraint == CAF_CRB_FIXED || constraint == CAF_CRB_RADIAL || constraint == CAF_CRB_WGS84,
                 "caf_crb_map: constraint must be CAF_CRB_FREE, CAF_CRB_FIXED, CAF_CRB_RADIAL or CAF_CRB_WGS84");
     CrbNormal nrm = {0.0, 0.0, 0.0, WGS84_A * WGS84_A, 0.0};
@@ -377,62 +327,27 @@ int32_t caf_crb_map(const caf_locate_desc* desc, const double* d_records, int64_
     CAF_REQUIRE(!(constraint == CAF_CRB_FREE && d_ellipse != nullptr), "caf_crb_map: no ellipse of an unconstrained 3 x 3 (CAF_CRB_FREE)");
     CAF_REQUIRE(d_min_idx == nullptr || d_min_val != nullptr, "caf_crb_map: d_min_idx needs d_min_val");
     CAF_REQUIRE(d_max_idx == nullptr || d_max_val != nullptr, "caf_crb_map: d_max_idx needs d_max_val");
-    LocSrc src = {};
-    int64_t N = 0;
-    if (desc->source == CAF_LOCATE_POINTS) {
-        N = desc->n;
-        CAF_REQUIRE(N >= 1, "caf_crb_map: the point matrix needs at least one row");
-        CAF_REQUIRE(desc->d_points != nullptr, "caf_crb_map: NULL point matrix");
-        src.pts = desc->d_points;
-    } else if (desc->source == CAF_LOCATE_MESH || desc->source == CAF_LOCATE_MESH_XY) {
-        CAF_REQUIRE(desc->ni >= 1 && desc->nj >= 1, "caf_crb_map: the mesh needs ni >= 1 and nj >= 1");
-        N = (int64_t)desc->ni * desc->nj;
-        CAF_REQUIRE(desc->d_a != nullptr && desc->d_c != nullptr, "caf_crb_map: NULL mesh table");
-        if (desc->source == CAF_LOCATE_MESH) {
-            CAF_REQUIRE(desc->d_z != nullptr && desc->d_s != nullptr, "caf_crb_map: NULL mesh table");
-        }
-        src.a = desc->d_a;
-        src.z = desc->d_z;
-        src.c = desc->d_c;
-        src.s = desc->d_s;
-        src.z0 = desc->z;
-        src.ni = desc->ni;
-        src.nj = desc->nj;
-        src.step_i = CRB_T / desc->nj;
-        src.step_j = CRB_T % desc->nj;
-    } else {
-        CAF_REQUIRE(false, "caf_crb_map: unknown point source");
-    }
-    const int64_t tiles = (N + CRB_P - 1) / CRB_P;
-    CAF_REQUIRE(tiles <= 0x7fffffff, "caf_crb_map: too many points for one launch");
-    CAF_REQUIRE(d_records != nullptr, "caf_crb_map: NULL record table");
     const bool want_fold = d_min_val != nullptr || d_max_val != nullptr;
     if (!d_crb && !d_ellipse && !d_rms && !want_fold) return CAF_OK;
 
     hipStream_t st = (hipStream_t)stream;
     Scratch sc(st);
-    CrbParts parts = {};
+    GridParts parts = {};
     if (want_fold) {
-        int rc;
         const int64_t np = (int64_t)B * tiles;
         if ((rc = sc.get(&parts.min_v, np)) || (rc = sc.get(&parts.min_i, np)) || (rc = sc.get(&parts.max_v, np)) ||
             (rc = sc.get(&parts.max_i, np)))
             return rc;
     }
     const dim3 grid((unsigned)tiles, (unsigned)B);
-    const int f32 = desc->cost_f32;
-    if (desc->source == CAF_LOCATE_POINTS)
-        hipLaunchKernelGGL((k_crb_map<CAF_LOCATE_POINTS>), grid, dim3(CRB_T), 0, st, src, N, d_records, K, d_set_starts, constraint, nrm,
-                           d_crb, d_ellipse, d_rms, f32, parts);
-    else if (desc->source == CAF_LOCATE_MESH)
-        hipLaunchKernelGGL((k_crb_map<CAF_LOCATE_MESH>), grid, dim3(CRB_T), 0, st, src, N, d_records, K, d_set_starts, constraint, nrm,
-                           d_crb, d_ellipse, d_rms, f32, parts);
-    else
-        hipLaunchKernelGGL((k_crb_map<CAF_LOCATE_MESH_XY>), grid, dim3(CRB_T), 0, st, src, N, d_records, K, d_set_starts, constraint, nrm,
-                           d_crb, d_ellipse, d_rms, f32, parts);
+    for_source(desc->source, [&](auto s) {
+        hipLaunchKernelGGL(k_crb_map<decltype(s)::value>, grid, dim3(CRB_T), 0, st, src, N, d_records, K, d_set_starts, constraint, nrm, d_crb,
+                           d_ellipse, d_rms, desc->cost_f32, parts);
+    });
     CAF_HIP_TRY(hipGetLastError());
     if (want_fold) {
-        hipLaunchKernelGGL(k_crb_fold, dim3((unsigned)B), dim3(CRB_T), 0, st, parts, tiles, d_min_val, d_min_idx, d_max_val, d_max_idx);
+        hipLaunchKernelGGL(k_grid_fold<true>, dim3((unsigned)B), dim3(GRID_FOLD_T), 0, st, parts, tiles, d_min_val, d_min_idx, d_max_val,
+                           d_max_idx);
         CAF_HIP_TRY(hipGetLastError());
     }
     return sc.finish();

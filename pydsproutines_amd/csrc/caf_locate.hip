@@ -10,7 +10,9 @@
 //                          back as broadcasts, one record for the thread's four points.  A TD instantiation never reads a velocity.
 //                          SRC: an (N, 3) matrix, or a separable mesh that is never materialised,
 //                          p(i, j) = (A[i] C[j], A[i] S[j], Z[i]) or (XY) p(i, j) = (X[j], Y[i], z), flat index i nj + j.
-//   k_locate_fold          the workgroups' (minimum, index) partials of each set -> one (value, index) per set.
+//   k_grid_fold<false>     (caf_grid.h) the workgroups' (minimum, index) partials of each set -> one (value, index) per set.
+// The point source, the sets, the stores and the arg min are the frame of caf_grid.h, shared with caf_crbmap.hip;
+// this file holds the two record loops and their choice of kernel.
 //
 // One range costs: a = p - s (3 subtractions), d2 = a.a (one product and two fma), y = 1 / sqrt(d2) from v_rsq_f64 and ONE
 // third-order correction y0 + y0 e (1/2 + 3/8 e), e = 1 - d2 y0^2 (the hardware estimate is good to about 2^-23, so the e^3 that is
@@ -26,8 +28,8 @@
 // its TD cost is finite and its FD cost NaN.  A NaN cost is stored as NaN and never wins the arg min.
 //
 // Arg min, in a fixed order and without atomics: a thread visits its points in increasing index and keeps the first minimum (strict
-// <); across lanes caf::wave_argmax on the negated cost (lower index wins a tie); the workgroup's four waves through LDS with the
-// same comparison; the partials of a set, in increasing order of workgroup, by k_locate_fold in the same way.
+// <); across lanes and the workgroup's four waves caf::block_argmin (the arg max of the negated cost: lower index wins a tie);
+// the partials of a set, in increasing order of workgroup, by k_grid_fold in the same way.
 // Floating-point contraction is off in this file: every product and sum is rounded where it is written, and each fma is spelled.
 //
 // One-bounce round trips (localizationRoutines.py:368-507 of the reference: gridSearchRTT, gridSearchBlindLinearRTT).  The record
@@ -52,7 +54,7 @@
 #include <cstdint>
 
 #include "caf_internal.h"
-#include "caf_locate_dev.h"
+#include "caf_grid.h"
 #include "caf_wave.h"
 
 #pragma clang fp contract(off)
@@ -66,7 +68,31 @@ constexpr int LOC_PPT = 4;              // points per thread
 constexpr int LOC_P = LOC_T * LOC_PPT;  // points per workgroup
 constexpr int LOC_C = 64;               // records per LDS chunk (8 KiB)
 constexpr int LOC_REC = 16;             // doubles per record: s1(3) s2(3) v1(3) v2(3) r wr d wd
-constexpr long long NO_INDEX = INT64_MAX;
+
+// what every search kernel ends with: the thread's costs stored, and the workgroup's first minimum into the partials
+__device__ __forceinline__ void put_costs(WaveSlots<LOC_T / 64, double, long long>& s_best, const double (&acc)[LOC_PPT], int64_t N,
+                                          int64_t base, int tid, int set, void* __restrict__ cost, int cost_f32,
+                                          double* __restrict__ part_v, int64_t* __restrict__ part_i) {
+    const int64_t out0 = (int64_t)set * N;
+    if (cost) {
+#pragma unroll
+        for (int j = 0; j < LOC_PPT; j++) {
+            const int64_t at = base + tid + j * LOC_T;
+            if (at < N) store_value(cost, cost_f32, out0 + at, acc[j]);
+        }
+    }
+    if (part_v) {
+        double bv;
+        long long bi;
+        thread_first_min<LOC_T, LOC_PPT>(acc, N, base, tid, bv, bi);
+        block_argmin(s_best, bv, bi);
+        if (tid == 0) {
+            const int64_t o = (int64_t)set * gridDim.x + blockIdx.x;
+            part_v[o] = bv;
+            part_i[o] = (int64_t)bi;
+        }
+    }
+}
 
 template <bool TD, bool FD, int SRC>
 __global__ __launch_bounds__(LOC_T) void k_locate(const LocSrc src, int64_t N, const double* __restrict__ rec, int64_t K,
@@ -78,14 +104,9 @@ __global__ __launch_bounds__(LOC_T) void k_locate(const LocSrc src, int64_t N, c
     const int64_t base = (int64_t)blockIdx.x * LOC_P;
     const int set = blockIdx.y;
 
-    // the records of this set, clamped into the table whatever the offsets say
-    int64_t k0 = 0, k1 = K;
-    if (set_starts) {
-        k0 = std::min(std::max<int64_t>(set_starts[set], 0), K);
-        k1 = std::min(std::max<int64_t>(set_starts[set + 1], k0), K);
-    }
+    int64_t k0, k1;
+    set_records(set_starts, set, K, k0, k1);
 
-    // the thread's points (caf_locate_dev.h)
     double px[LOC_PPT], py[LOC_PPT], pz[LOC_PPT], acc[LOC_PPT];
     loc_points<SRC, LOC_T, LOC_PPT>(src, N, base, tid, px, py, pz);
 #pragma unroll
@@ -128,74 +149,7 @@ __global__ __launch_bounds__(LOC_T) void k_locate(const LocSrc src, int64_t N, c
         }
         __syncthreads();  // the chunk is overwritten next
     }
-
-    const int64_t out0 = (int64_t)set * N;
-    if (cost) {
-#pragma unroll
-        for (int j = 0; j < LOC_PPT; j++) {
-            const int64_t at = base + tid + j * LOC_T;
-            if (at >= N) continue;
-            if (cost_f32) ((float*)cost)[out0 + at] = (float)acc[j];
-            else ((double*)cost)[out0 + at] = acc[j];
-        }
-    }
-    if (part_v) {
-        double bv = INFINITY;
-        long long bi = NO_INDEX;
-#pragma unroll
-        for (int j = 0; j < LOC_PPT; j++) {
-            const int64_t at = base + tid + j * LOC_T;
-            if (at < N && first_min(bv, bi, acc[j], (long long)at)) {
-                bv = acc[j];
-                bi = at;
-            }
-        }
-        // the arg min as the arg max of the negated values (first_min and first_max agree on them, signed zeros included)
-        bv = -bv;
-        block_argmax(s_best, bv, bi);
-        bv = -bv;
-        if (tid == 0) {
-            const int64_t o = (int64_t)set * gridDim.x + blockIdx.x;
-            part_v[o] = bv;
-            part_i[o] = (int64_t)bi;
-        }
-    }
-}
-
-// the partials of set blockIdx.x (in increasing order of index) -> min_val[set], min_idx[set]; nothing but NaN: (NaN, -1)
-__global__ __launch_bounds__(LOC_T) void k_locate_fold(const double* __restrict__ part_v, const int64_t* __restrict__ part_i, int64_t nparts,
-                                                       double* __restrict__ min_val, int64_t* __restrict__ min_idx) {
-    __shared__ WaveSlots<LOC_T / 64, double, long long> s_best;
-    const int64_t o = (int64_t)blockIdx.x * nparts;
-    double bv = INFINITY;
-    long long bi = NO_INDEX;
-    for (int64_t e = threadIdx.x; e < nparts; e += LOC_T) {
-        const double v = part_v[o + e];
-        const long long i = (long long)part_i[o + e];
-        if (first_min(bv, bi, v, i)) {
-            bv = v;
-            bi = i;
-        }
-    }
-    bv = -bv;  // (the arg min as the arg max of the negated values, as in k_locate)
-    block_argmax(s_best, bv, bi);
-    bv = -bv;
-    if (threadIdx.x == 0) {
-        const bool none = bi == NO_INDEX;
-        if (min_val) min_val[blockIdx.x] = none ? (double)NAN : bv;
-        if (min_idx) min_idx[blockIdx.x] = none ? (int64_t)-1 : (int64_t)bi;
-    }
-}
-
-template <bool TD, bool FD>
-void launch_mode(int source, dim3 grid, hipStream_t st, const LocSrc& src, int64_t N, const double* rec, int64_t K, const int64_t* starts,
-                 void* cost, int cost_f32, double* pv, int64_t* pi) {
-    if (source == CAF_LOCATE_POINTS)
-        hipLaunchKernelGGL((k_locate<TD, FD, CAF_LOCATE_POINTS>), grid, dim3(LOC_T), 0, st, src, N, rec, K, starts, cost, cost_f32, pv, pi);
-    else if (source == CAF_LOCATE_MESH)
-        hipLaunchKernelGGL((k_locate<TD, FD, CAF_LOCATE_MESH>), grid, dim3(LOC_T), 0, st, src, N, rec, K, starts, cost, cost_f32, pv, pi);
-    else
-        hipLaunchKernelGGL((k_locate<TD, FD, CAF_LOCATE_MESH_XY>), grid, dim3(LOC_T), 0, st, src, N, rec, K, starts, cost, cost_f32, pv, pi);
+    put_costs(s_best, acc, N, base, tid, set, cost, cost_f32, part_v, part_i);
 }
 
 // ---- one-bounce round trips ------------------------------------------------------------------------------------------------------
@@ -242,12 +196,8 @@ __global__ __launch_bounds__(LOC_T) void k_locate_rtt(const LocSrc src, int64_t 
     const int64_t base = (int64_t)blockIdx.x * LOC_P;
     const int set = blockIdx.y;
 
-    // the records of this set, clamped into the table whatever the offsets say
-    int64_t k0 = 0, k1 = K;
-    if (set_starts) {
-        k0 = std::min(std::max<int64_t>(set_starts[set], 0), K);
-        k1 = std::min(std::max<int64_t>(set_starts[set + 1], k0), K);
-    }
+    int64_t k0, k1;
+    set_records(set_starts, set, K, k0, k1);
     const bool once = k1 - k0 <= LOC_C;  // the whole set is one chunk: pass 2 finds it in LDS
 
     double px[LOC_PPT], py[LOC_PPT], pz[LOC_PPT], al[LOC_PPT], be[LOC_PPT], acc[LOC_PPT];
@@ -274,49 +224,43 @@ __global__ __launch_bounds__(LOC_T) void k_locate_rtt(const LocSrc src, int64_t 
         rtt_chunk<Q, 1>(s_rec, nrec, px, py, pz, al, be, acc);
         if (!once) __syncthreads();
     }
-
-    // the stores and the workgroup's partial, as in k_locate
-    const int64_t out0 = (int64_t)set * N;
-    if (cost) {
-#pragma unroll
-        for (int j = 0; j < LOC_PPT; j++) {
-            const int64_t at = base + tid + j * LOC_T;
-            if (at >= N) continue;
-            if (cost_f32) ((float*)cost)[out0 + at] = (float)acc[j];
-            else ((double*)cost)[out0 + at] = acc[j];
-        }
-    }
-    if (part_v) {
-        double bv = INFINITY;
-        long long bi = NO_INDEX;
-#pragma unroll
-        for (int j = 0; j < LOC_PPT; j++) {
-            const int64_t at = base + tid + j * LOC_T;
-            if (at < N && first_min(bv, bi, acc[j], (long long)at)) {
-                bv = acc[j];
-                bi = at;
-            }
-        }
-        bv = -bv;
-        block_argmax(s_best, bv, bi);
-        bv = -bv;
-        if (tid == 0) {
-            const int64_t o = (int64_t)set * gridDim.x + blockIdx.x;
-            part_v[o] = bv;
-            part_i[o] = (int64_t)bi;
-        }
-    }
+    put_costs(s_best, acc, N, base, tid, set, cost, cost_f32, part_v, part_i);
 }
 
-template <int Q>
-void launch_rtt(int source, dim3 grid, hipStream_t st, const LocSrc& src, int64_t N, const double* rec, int64_t K, const int64_t* starts,
-                void* cost, int cost_f32, double* pv, int64_t* pi) {
-    if (source == CAF_LOCATE_POINTS)
-        hipLaunchKernelGGL((k_locate_rtt<Q, CAF_LOCATE_POINTS>), grid, dim3(LOC_T), 0, st, src, N, rec, K, starts, cost, cost_f32, pv, pi);
-    else if (source == CAF_LOCATE_MESH)
-        hipLaunchKernelGGL((k_locate_rtt<Q, CAF_LOCATE_MESH>), grid, dim3(LOC_T), 0, st, src, N, rec, K, starts, cost, cost_f32, pv, pi);
-    else
-        hipLaunchKernelGGL((k_locate_rtt<Q, CAF_LOCATE_MESH_XY>), grid, dim3(LOC_T), 0, st, src, N, rec, K, starts, cost, cost_f32, pv, pi);
+// a search kernel, and what both entry points do once they have checked their own arguments: the shared checks, the launch of
+// pick(source as a constant) over (workgroups, sets), and the fold of the partials when a minimum is asked for
+using SearchKernel = void (*)(const LocSrc, int64_t, const double*, int64_t, const int64_t*, void*, int, double*, int64_t*);
+
+template <class Pick>
+int32_t grid_search(const char* entry, const caf_locate_desc* desc, const double* d_records, int64_t K, const int64_t* d_set_starts, int32_t B,
+                    int per_set, Pick pick, void* d_cost, double* d_min_val, int64_t* d_min_idx, void* stream) {
+    LocSrc src;
+    int64_t N, tiles;
+    int rc;
+    if ((rc = grid_source(entry, desc, LOC_T, LOC_P, &src, &N, &tiles))) return rc;
+    if ((rc = grid_sets_ok(entry, desc, d_records, K, d_set_starts, B, per_set))) return rc;
+    const bool want_min = d_min_val != nullptr || d_min_idx != nullptr;
+    if (!d_cost && !want_min) return CAF_OK;
+
+    hipStream_t st = (hipStream_t)stream;
+    Scratch sc(st);
+    double* pv = nullptr;
+    int64_t* pi = nullptr;
+    if (want_min) {
+        if ((rc = sc.get(&pv, (int64_t)B * tiles)) || (rc = sc.get(&pi, (int64_t)B * tiles))) return rc;
+    }
+    for_source(desc->source, [&](auto s) {
+        const SearchKernel k = pick(s);
+        hipLaunchKernelGGL(k, dim3((unsigned)tiles, (unsigned)B), dim3(LOC_T), 0, st, src, N, d_records, K, d_set_starts, d_cost,
+                           desc->cost_f32, pv, pi);
+    });
+    CAF_HIP_TRY(hipGetLastError());
+    if (want_min) {
+        hipLaunchKernelGGL(k_grid_fold<false>, dim3((unsigned)B), dim3(GRID_FOLD_T), 0, st, GridParts{pv, pi, nullptr, nullptr}, tiles,
+                           d_min_val, d_min_idx, (double*)nullptr, (int64_t*)nullptr);
+        CAF_HIP_TRY(hipGetLastError());
+    }
+    return sc.finish();
 }
 
 }  // namespace
@@ -336,132 +280,24 @@ int32_t caf_locate_grid(const caf_locate_desc* desc, const double* d_records, in
     CAF_REQUIRE(desc != nullptr, "caf_locate_grid: NULL descriptor");
     CAF_REQUIRE(desc->mode == CAF_LOCATE_TD || desc->mode == CAF_LOCATE_FD || desc->mode == CAF_LOCATE_TDFD,
                 "caf_locate_grid: mode must be CAF_LOCATE_TD, CAF_LOCATE_FD or CAF_LOCATE_TDFD");
-    CAF_REQUIRE(desc->cost_f32 == 0 || desc->cost_f32 == 1, "caf_locate_grid: cost_f32 must be 0 or 1");
-    CAF_REQUIRE(K >= 1 && K <= ((int64_t)1 << 40), "caf_locate_grid: the table needs at least one record");
-    CAF_REQUIRE(B >= 1 && B <= 65535 && (d_set_starts != nullptr || B == 1),
-                "caf_locate_grid: 1 <= sets <= 65535, and more than one set needs set_starts");
-    CAF_REQUIRE((int64_t)B <= K, "caf_locate_grid: every set needs at least one record");
-    LocSrc src = {};
-    int64_t N = 0;
-    if (desc->source == CAF_LOCATE_POINTS) {
-        N = desc->n;
-        CAF_REQUIRE(N >= 1, "caf_locate_grid: the point matrix needs at least one row");
-        CAF_REQUIRE(desc->d_points != nullptr, "caf_locate_grid: NULL point matrix");
-        src.pts = desc->d_points;
-    } else if (desc->source == CAF_LOCATE_MESH || desc->source == CAF_LOCATE_MESH_XY) {
-        CAF_REQUIRE(desc->ni >= 1 && desc->nj >= 1, "caf_locate_grid: the mesh needs ni >= 1 and nj >= 1");
-        N = (int64_t)desc->ni * desc->nj;
-        CAF_REQUIRE(desc->d_a != nullptr && desc->d_c != nullptr, "caf_locate_grid: NULL mesh table");
-        if (desc->source == CAF_LOCATE_MESH) {
-            CAF_REQUIRE(desc->d_z != nullptr && desc->d_s != nullptr, "caf_locate_grid: NULL mesh table");
-        }
-        src.a = desc->d_a;
-        src.z = desc->d_z;
-        src.c = desc->d_c;
-        src.s = desc->d_s;
-        src.z0 = desc->z;
-        src.ni = desc->ni;
-        src.nj = desc->nj;
-        src.step_i = LOC_T / desc->nj;
-        src.step_j = LOC_T % desc->nj;
-    } else {
-        CAF_REQUIRE(false, "caf_locate_grid: unknown point source");
-    }
-    const int64_t tiles = (N + LOC_P - 1) / LOC_P;
-    CAF_REQUIRE(tiles <= 0x7fffffff, "caf_locate_grid: too many points for one launch");
-    CAF_REQUIRE(d_records != nullptr, "caf_locate_grid: NULL record table");
-    const bool want_min = d_min_val != nullptr || d_min_idx != nullptr;
-    if (!d_cost && !want_min) return CAF_OK;
-
-    hipStream_t st = (hipStream_t)stream;
-    Scratch sc(st);
-    double* pv = nullptr;
-    int64_t* pi = nullptr;
-    if (want_min) {
-        int rc;
-        if ((rc = sc.get(&pv, (int64_t)B * tiles)) || (rc = sc.get(&pi, (int64_t)B * tiles))) return rc;
-    }
-    const dim3 grid((unsigned)tiles, (unsigned)B);
-    if (desc->mode == CAF_LOCATE_TD)
-        launch_mode<true, false>(desc->source, grid, st, src, N, d_records, K, d_set_starts, d_cost, desc->cost_f32, pv, pi);
-    else if (desc->mode == CAF_LOCATE_FD)
-        launch_mode<false, true>(desc->source, grid, st, src, N, d_records, K, d_set_starts, d_cost, desc->cost_f32, pv, pi);
-    else
-        launch_mode<true, true>(desc->source, grid, st, src, N, d_records, K, d_set_starts, d_cost, desc->cost_f32, pv, pi);
-    CAF_HIP_TRY(hipGetLastError());
-    if (want_min) {
-        hipLaunchKernelGGL(k_locate_fold, dim3((unsigned)B), dim3(LOC_T), 0, st, pv, pi, tiles, d_min_val, d_min_idx);
-        CAF_HIP_TRY(hipGetLastError());
-    }
-    return sc.finish();
+    const int mode = desc->mode;
+    const auto pick = [mode](auto s) -> SearchKernel {
+        constexpr int SRC = decltype(s)::value;
+        return mode == CAF_LOCATE_TD ? k_locate<true, false, SRC> : mode == CAF_LOCATE_FD ? k_locate<false, true, SRC> : k_locate<true, true, SRC>;
+    };
+    return grid_search("caf_locate_grid", desc, d_records, K, d_set_starts, B, 1, pick, d_cost, d_min_val, d_min_idx, stream);
 }
 
 int32_t caf_locate_rtt_geometry(int32_t* points_per_workgroup, int32_t* records_per_chunk) {
-    if (points_per_workgroup) *points_per_workgroup = LOC_P;
-    if (records_per_chunk) *records_per_chunk = LOC_C;
-    return CAF_OK;
+    return caf_locate_geometry(points_per_workgroup, records_per_chunk);  // (k_locate's frame)
 }
 
 int32_t caf_locate_rtt(const caf_locate_desc* desc, const double* d_records, int64_t K, const int64_t* d_set_starts, int32_t B,
                        int32_t nuisance, void* d_cost, double* d_min_val, int64_t* d_min_idx, void* stream) {
-    CAF_REQUIRE(desc != nullptr, "caf_locate_rtt: NULL descriptor");
     CAF_REQUIRE(nuisance >= 0 && nuisance <= 2, "caf_locate_rtt: nuisance must be 0, 1 or 2");
-    CAF_REQUIRE(desc->cost_f32 == 0 || desc->cost_f32 == 1, "caf_locate_rtt: cost_f32 must be 0 or 1");
-    CAF_REQUIRE(K >= 1 && K <= ((int64_t)1 << 40), "caf_locate_rtt: the table needs at least one record");
-    CAF_REQUIRE(B >= 1 && B <= 65535 && (d_set_starts != nullptr || B == 1),
-                "caf_locate_rtt: 1 <= sets <= 65535, and more than one set needs set_starts");
-    CAF_REQUIRE((int64_t)B * (nuisance + 1) <= K, "caf_locate_rtt: every set needs more records than nuisance parameters");
-    LocSrc src = {};
-    int64_t N = 0;
-    if (desc->source == CAF_LOCATE_POINTS) {
-        N = desc->n;
-        CAF_REQUIRE(N >= 1, "caf_locate_rtt: the point matrix needs at least one row");
-        CAF_REQUIRE(desc->d_points != nullptr, "caf_locate_rtt: NULL point matrix");
-        src.pts = desc->d_points;
-    } else if (desc->source == CAF_LOCATE_MESH || desc->source == CAF_LOCATE_MESH_XY) {
-        CAF_REQUIRE(desc->ni >= 1 && desc->nj >= 1, "caf_locate_rtt: the mesh needs ni >= 1 and nj >= 1");
-        N = (int64_t)desc->ni * desc->nj;
-        CAF_REQUIRE(desc->d_a != nullptr && desc->d_c != nullptr, "caf_locate_rtt: NULL mesh table");
-        if (desc->source == CAF_LOCATE_MESH) {
-            CAF_REQUIRE(desc->d_z != nullptr && desc->d_s != nullptr, "caf_locate_rtt: NULL mesh table");
-        }
-        src.a = desc->d_a;
-        src.z = desc->d_z;
-        src.c = desc->d_c;
-        src.s = desc->d_s;
-        src.z0 = desc->z;
-        src.ni = desc->ni;
-        src.nj = desc->nj;
-        src.step_i = LOC_T / desc->nj;
-        src.step_j = LOC_T % desc->nj;
-    } else {
-        CAF_REQUIRE(false, "caf_locate_rtt: unknown point source");
-    }
-    const int64_t tiles = (N + LOC_P - 1) / LOC_P;
-    CAF_REQUIRE(tiles <= 0x7fffffff, "caf_locate_rtt: too many points for one launch");
-    CAF_REQUIRE(d_records != nullptr, "caf_locate_rtt: NULL record table");
-    const bool want_min = d_min_val != nullptr || d_min_idx != nullptr;
-    if (!d_cost && !want_min) return CAF_OK;
-
-    hipStream_t st = (hipStream_t)stream;
-    Scratch sc(st);
-    double* pv = nullptr;
-    int64_t* pi = nullptr;
-    if (want_min) {
-        int rc;
-        if ((rc = sc.get(&pv, (int64_t)B * tiles)) || (rc = sc.get(&pi, (int64_t)B * tiles))) return rc;
-    }
-    const dim3 grid((unsigned)tiles, (unsigned)B);
-    if (nuisance == 0)
-        launch_rtt<0>(desc->source, grid, st, src, N, d_records, K, d_set_starts, d_cost, desc->cost_f32, pv, pi);
-    else if (nuisance == 1)
-        launch_rtt<1>(desc->source, grid, st, src, N, d_records, K, d_set_starts, d_cost, desc->cost_f32, pv, pi);
-    else
-        launch_rtt<2>(desc->source, grid, st, src, N, d_records, K, d_set_starts, d_cost, desc->cost_f32, pv, pi);
-    CAF_HIP_TRY(hipGetLastError());
-    if (want_min) {
-        hipLaunchKernelGGL(k_locate_fold, dim3((unsigned)B), dim3(LOC_T), 0, st, pv, pi, tiles, d_min_val, d_min_idx);
-        CAF_HIP_TRY(hipGetLastError());
-    }
-    return sc.finish();
+    const auto pick = [nuisance](auto s) -> SearchKernel {
+        constexpr int SRC = decltype(s)::value;
+        return nuisance == 0 ? k_locate_rtt<0, SRC> : nuisance == 1 ? k_locate_rtt<1, SRC> : k_locate_rtt<2, SRC>;
+    };
+    return grid_search("caf_locate_rtt", desc, d_records, K, d_set_starts, B, nuisance + 1, pick, d_cost, d_min_val, d_min_idx, stream);
 }

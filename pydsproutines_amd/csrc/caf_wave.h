@@ -12,9 +12,9 @@
 //    Changing an order here changes result bits everywhere.
 //
 // What lives here: first_max / first_min; wave_sum, wave_max, wave_scan_inclusive, wave_argmax; block_sum (one value
-// through an array, or several through a WaveSlots record and one barrier), block_sum_totals, block_max, block_argmax --
-// one barrier, the LDS in use until the caller's next one -- and the _all forms, whose trailing barrier frees the LDS;
-// block_exclusive, the carry of a workgroup scan of sums, over block_carry, which takes the operator (k_scan_exclusive
+// through an array, or several through a WaveSlots record and one barrier), block_sum_totals, block_max, block_argmax,
+// block_argmin -- one barrier, the LDS in use until the caller's next one -- and the _all forms, whose trailing barrier
+// frees the LDS; block_exclusive, the carry of a workgroup scan of sums, over block_carry, which takes the operator (k_scan_exclusive
 // of caf_rows.hip is the whole scan by one workgroup).  The block helpers take their LDS from the caller (a WaveSlots
 // or an array of WAVES entries), so a kernel's LDS is all declared in the kernel, and index lanes and waves by threadIdx.x.
 //
@@ -200,6 +200,14 @@ __device__ __forceinline__ void block_argmax_all(WaveSlots<WAVES, V, I, P...>& l
     for (int w = 1; w < WAVES; ++w)
         if (first_max(v, i, lds.a[w], lds.rest.a[w])) lds.get(w, v, i, payload...);
     __syncthreads();
+}
+// (value, index) arg min over the workgroup: the arg max of the negated values (first_min and first_max agree on them, signed
+// zeros included, and a NaN wins neither).  In place, the result in thread 0.
+template <int WAVES, typename V, typename I>
+__device__ __forceinline__ void block_argmin(WaveSlots<WAVES, V, I>& lds, V& v, I& i) {
+    v = -v;
+    block_argmax(lds, v, i);
+    v = -v;
 }
 
 // the carry of a workgroup scan under `op`: lane 63 leaves the wave's inclusive total `incl`, and after the barrier `first`

@@ -98,6 +98,49 @@ def cases():
         src = L._Source.xy(1000.0 * (np.arange(70) - 35) + 0.37, 800.0 * (np.arange(90) - 45) - 0.21, 50.0)
         return [o for o in L._search(src, "td", rec, argmin=True) if o is not None]
 
+    # K = 70 records (two chunks, 64 + 6, where they are one set) on the 70 x 90 shape of `locate`, as three sets and as one
+    GRID_SETS = (3, 62, 5)
+
+    def locate_rtt(q):
+        def run():
+            rng = np.random.default_rng(16 + q)
+            src = L._Source.xy(1000.0 * (np.arange(70) - 35) + 0.37, 800.0 * (np.arange(90) - 45) - 0.21, 50.0)
+            p0 = src.matrix()[3000]
+
+            def table(k):
+                tx, rx = (p0 + np.concatenate((rng.uniform(-6e4, 6e4, (k, 2)), rng.uniform(8e3, 12e3, (k, 1))), 1) for _ in range(2))
+                t, sigma = np.sort(rng.uniform(0.0, 240.0, k)), rng.uniform(5e-8, 2e-7, k)
+                toa = (np.linalg.norm(p0 - tx, axis=1) + np.linalg.norm(p0 - rx, axis=1)) / L.LIGHTSPD + sigma * rng.standard_normal(k)
+                toa = toa + (128e-6 if q else 0.0) + (2e-7 * t if q == 2 else 0.0)
+                return L._records_rtt(tx, rx, toa, sigma) if q == 0 else L._records_blind(tx, rx, t, toa, sigma, True, q)
+
+            mode = ("rtt", "rtt1", "rtt2")[q]
+            sets = L._search(src, mode, np.concatenate([table(k) for k in GRID_SETS]), set_starts=np.concatenate(([0], np.cumsum(GRID_SETS))),
+                             cost=np.float64, argmin=True)
+            return list(sets) + list(L._search(src, mode, table(sum(GRID_SETS)), cost=np.float64, argmin=True))
+
+        return run
+
+    def crb_map():
+        from pydsproutines_amd import crbRoutines as B
+
+        rng = np.random.default_rng(19)
+        src = L._Source.mesh(*L._wgs84_tables(1.3 + 0.01 * (np.arange(70) - 35), 103.8 + 0.01 * (np.arange(90) - 45)))
+        p0 = src.matrix()[3000]
+        k = sum(GRID_SETS)
+        d = p0 / np.linalg.norm(p0) + 0.35 * rng.standard_normal((2 * k, 3))
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+        rec = np.zeros((k, 16))
+        rec[:, 0:3], rec[:, 3:6] = (d * rng.uniform(6.9e6, 7.2e6, (2 * k, 1))).reshape(2, k, 3)
+        rec[:, 6:12] = 7.5e3 * np.cross(np.repeat(d[:k], 2, axis=0), rng.standard_normal((2 * k, 3))).reshape(k, 6)
+        rec[:, 13] = kind = np.array([(5, 3, 4, 1, 2)[i % 5] for i in range(k)])  # the five kinds in turn
+        rec[:, 12] = np.where(kind == 4, 1.0, np.where(kind == 5, 2e6, 30.0 ** -2))
+        out = []
+        for starts in (np.concatenate(([0], np.cumsum(GRID_SETS))), None):
+            r = B.CRBMap.fromRecords(rec, starts, "wgs84").run(src, outputs=("rms", "ellipse", "crb"))
+            out += [r.rms, r.ellipse, r.crb, np.asarray(r.best_idx), np.asarray(r.best_rms), np.asarray(r.worst_idx), np.asarray(r.worst_rms)]
+        return out
+
     def cancel():
         rng = np.random.default_rng(15)
         n, m, idx = 3000, 9000, 1234
@@ -128,7 +171,9 @@ def cases():
             ("rows_argmax_chunked", rows_argmax(2, 163841)), ("argmax3d", argmax3d), ("local_maxima_direct", local_maxima(64 * 4 * 129 + 1)),
             ("local_maxima_scanned", local_maxima(16384 * 4100 + 5)), ("threshold_and_gather_edges", edges), ("median", median),
             ("above_threshold_runs", above), ("moving_average", moving), ("psk_demod_batch", psk), ("cp2fsk_bursty_batch", cp2fsk),
-            ("locate_grid_argmin", locate), ("cancel_search_estimate_subtract", cancel), ("plan_peaks_and_zoom", plan_peaks_and_zoom)]
+            ("locate_grid_argmin", locate), ("locate_rtt_plain", locate_rtt(0)),
+            ("locate_rtt_turnaround", locate_rtt(1)), ("locate_rtt_linear", locate_rtt(2)), ("crb_map_wgs84_all_outputs", crb_map),
+            ("cancel_search_estimate_subtract", cancel), ("plan_peaks_and_zoom", plan_peaks_and_zoom)]
 
 
 def child():

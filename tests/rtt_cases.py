@@ -75,6 +75,31 @@ def sensor_case(q):
     return case(L._Source.points(pts), rec, q)
 
 
+TIE_FIRST = 70
+
+
+def tie_rows(p):
+    """row 70 (wave 1 of workgroup 0) and its copies: in workgroup 1, and the lone point of workgroup 2"""
+    return TIE_FIRST, p + 6, 2 * p
+
+
+def tie_case(p, q):
+    """N = 2 P + 1 rows against 6 noise-free round trips to row 70, which is copied bit for bit to the other rows of tie_rows: three
+    equal minima near zero, so this case is not one of every_case (a bound is no small share of a cost that is rounding alone)"""
+    n = 2 * p + 1
+    pts = K.latlon_source(29, n // 29 + 1).matrix()[:n].copy()
+    first, *copies = tie_rows(p)
+    pts[copies] = pts[first]
+    rng = np.random.default_rng(8500 + q)
+    tx, rx, _, _ = K.sensors(rng, pts[first], 6, True)
+    t = np.sort(rng.uniform(0.0, 240.0, 6))
+    sigma = rng.uniform(5e-8, 2e-7, 6)
+    toa = (np.linalg.norm(pts[first] - tx, axis=1) + np.linalg.norm(pts[first] - rx, axis=1)) / C
+    toa = toa + (128e-6 if q >= 1 else 0.0) + (2e-7 * t if q == 2 else 0.0)
+    rec = L._records_rtt(tx, rx, toa, sigma) if q == 0 else L._records_blind(tx, rx, t, toa, sigma, True, q)
+    return case(L._Source.points(pts), rec, q)
+
+
 def golden_cases(g):
     """the two inputs of tests/golden/rtt_a.npz as cases: the seeded plain search, the seeded blind search and the scenario
     (blind, and plain on the same times of arrival); the grids are rebuilt from the fixture's four tables"""

@@ -209,6 +209,23 @@ def test_a_point_on_a_sensor():
     assert list(idx) == [-1, -1] and np.isnan(val).all()
 
 
+def test_nothing_but_nan_reports_minus_one():
+    """N = 5 points against K = 2 records in two sets of one: the weights of the first record are NaN, so every cost of its set is
+    NaN in the grid and its arg min is (NaN, -1); the clean set beside it reports the restatement's arg min, with the grid written
+    and without"""
+    pts = latlon_source(1, 5).matrix()
+    rec = records(np.random.default_rng(6000), pts[3], 2, True)
+    rec[0, [13, 15]] = np.nan
+    starts = np.array([0, 1, 2])
+    for mode in MODES:
+        want, bound = R.cost_and_bound(pts, rec[1:], mode)
+        got, val, idx = gpu(L._Source.points(pts), mode, rec, starts)
+        assert got.shape == (2, 5) and np.isnan(got[0]).all() and np.isnan(val[0]) and idx[0] == -1
+        check(got[1:], val[1:], idx[1:], want[None], bound[None], "beside a set of NaN, %s" % mode)
+        _, val0, idx0 = gpu(L._Source.points(pts), mode, rec, starts, cost=None)
+        assert np.isnan(val0[0]) and idx0[0] == -1 and (val0[1], idx0[1]) == (val[1], idx[1])
+
+
 def test_more_than_2_to_the_32_points():
     """a 65537 x 65537 mesh that is never materialised, arg min only: the minimum beyond index 2^32 is found and its cost is the
     restated one"""

@@ -134,6 +134,26 @@ def test_a_point_on_a_sensor(q):
         assert g1[0, 0] == got[0, at] and i1[0] == 0 and v1[0] == g1[0, 0]
 
 
+@pytest.mark.parametrize("q", K.QS)
+def test_equal_minima_report_the_lower_index(q):
+    """the noise-free emitter's row three times, in wave 1 of workgroup 0, in workgroup 1 and as the lone point of workgroup 2: the
+    three costs are the same bits and the arg min is the first of them, with the grid written and without.  On the host every
+    other row's restated cost lies above the emitter's by more than both bounds, so the tie is all the device decides."""
+    p = geometry()[0]
+    cs = K.tie_case(p, q)
+    rows = list(K.tie_rows(p))
+    assert cs["source"].n == 2 * p + 1 and cs["records"].shape[0] == 6 and rows[0] == 70
+    want, bound = K.reference(R, cs)
+    others = np.setdiff1d(np.arange(want.shape[1]), rows)
+    assert np.all(want[0][others] - bound[0][others] > want[0][rows[0]] + bound[0][rows[0]])
+    got, val, idx = gpu(cs)
+    assert R.worst_ratio(got[0], want[0], bound[0]) <= 1.0
+    assert got[0][rows].view(np.uint64).tolist() == [got[0][rows[0]].view(np.uint64)] * 3
+    assert idx[0] == rows[0] == np.argmin(got[0]) and val[0] == got[0][rows[0]]
+    _, val0, idx0 = gpu(cs, cost=None)
+    same((val0, idx0), (val, idx))
+
+
 def test_nothing_but_nan_reports_minus_one():
     """a NaN among the measurements makes every cost of its set NaN: NaN in the grid, (NaN, -1) from the arg min; the other set
     of the batch is untouched"""

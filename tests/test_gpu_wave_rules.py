@@ -195,7 +195,7 @@ def test_local_maxima_compaction_carries_cross_every_lane_and_wave(k):
 
 
 def test_locate_argmin_first_of_equal_costs_across_waves_and_workgroups():
-    """k_locate / k_locate_fold (the arg min as block_argmax of the negated costs): records of weight zero make every term,
+    """k_locate / k_grid_fold (block_argmin: the arg max of the negated costs): records of weight zero make every term,
     and so the cost of every grid point, exactly zero -- in every wave of every workgroup.  The first point wins."""
     import locate_ref as R
     from pydsproutines_amd import localizationRoutines as L
