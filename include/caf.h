@@ -17,7 +17,12 @@
  * Pointer conventions: names starting with h_ are HOST pointers, d_ are DEVICE (HBM)
  * pointers on the current HIP device.  `stream` is a hipStream_t passed as void*
  * (NULL = the default stream).  Calls with d_ pointers are asynchronous on `stream`
- * unless stated otherwise; *_host entry points are blocking.
+ * unless stated otherwise; *_host entry points are blocking.  "Asynchronous" is a statement about ordering: all device work of
+ * the call is queued on `stream` and nowhere else.  Whether the host returns before that work has run is not promised: an entry
+ * point that takes pooled scratch, or that downloads an input to check it, waits for `stream`.  Independence from
+ * OTHER streams needs a hardware queue per stream in use at once: HIP maps streams onto GPU_MAX_HW_QUEUES queues (4 by default),
+ * and a stream that shares a queue waits behind the other stream's work.  A client that initialises HIP itself sets that variable
+ * to cover its streams plus the library's auxiliary ones (one per plan in use, at most 16 kept).
  *
  * Placement: every pointer is aligned to its element type (4 bytes for float32 / int32, 8 for a complex64 or float64 element,
  * 16 for complex128, 2 for int16, 1 for bytes) and nothing more is required unless the entry point says so; a view into a

@@ -416,11 +416,32 @@ def _share_rocm_runtime_with_torch():
             ct.CDLL(path)  # RTLD_LOCAL: global scope would interpose the amd::smi statics of libamd_smi
 
 
+MIN_HW_QUEUES = 16
+
+
+def _enough_hardware_queues():
+    """Streams beyond GPU_MAX_HW_QUEUES (HIP's default: 4) share a hardware queue, and work on a stream then waits behind
+    whatever an unrelated stream on the same queue has queued: a plan's auxiliary stream behind the caller's ingest stream, the
+    null stream's downloads behind an auxiliary stream that waits for the caller's.
+    The library keeps up to 16 auxiliary streams beside the callers' own and promises calls that are asynchronous on the
+    caller's stream, so it asks for at least MIN_HW_QUEUES queues.  The runtime reads the variable when it
+    initialises: this has to run before the first HIP call of the process (a client that has initialised HIP already keeps what
+    it had: INTEGRATION.md), and a larger value that is already set is kept.  A smaller one is raised, also one set on purpose:
+    with fewer queues than streams the header's promise does not hold, and child processes inherit the larger value."""
+    try:
+        cur = int(os.environ.get("GPU_MAX_HW_QUEUES", "0"))
+    except ValueError:
+        cur = 0
+    if cur < MIN_HW_QUEUES:
+        os.environ["GPU_MAX_HW_QUEUES"] = str(MIN_HW_QUEUES)
+
+
 def load():
     """Load libcaf.so (once).  Raises OSError with build instructions if absent."""
     global _lib
     if _lib is not None:
         return _lib
+    _enough_hardware_queues()
     _share_rocm_runtime_with_torch()
     try:
         # CAF_LIBRARY=<name>: a development switch for A/B runs of two builds on one box (e.g. libcaf_r02, kept beside

@@ -240,6 +240,8 @@ def clusterScores(x, labels, k=None, lengths=None, which=("sil",), points=False,
     _lib.check(_lib.load().caf_cluster_scores(_p(d_x), P, pitch, D, _p(d_len), jp_c, jk_c, J, kmax, _p(d_lab), rows_c, nrows, bits,
                                               _p(out.get("sil")), _p(out.get("db")), _p(out.get("ch")), _p(d_pts), _st(stream)),
                "caf_cluster_scores")
+    if stream is not None and (d_x is not x or d_len is not lengths or d_lab is not labels):
+        _lib.check(_lib.load().caf_stream_sync(_st(stream)), "sync")  # (what was uploaded here is freed on return)
     if points:
         out["sil_points"] = d_pts
     return out

@@ -105,6 +105,8 @@ def cmLines(d_x, lengths=None, nfft=None, moments=(2, 4), bands=None, peak=True,
     _lib.check(_lib.load().caf_cm_lines(_p(d_x), rows, pitch, _p(d_len), nfft, arr(*moments), K, arr(*[b[0] for b in bands]),
                                         arr(*[b[1] for b in bands]), _p(d_index), _p(d_peak), _p(d_side), _p(d_power), _st(stream)),
                "caf_cm_lines")
+    if stream is not None and d_len is not None and d_len is not lengths:
+        _lib.check(_lib.load().caf_stream_sync(_st(stream)), "sync")  # (the uploaded d_len is freed on return)
     return d_index, d_peak, d_side, d_power
 
 
@@ -290,6 +292,8 @@ def estimateBursts(d_xbatch, lengths=None, fs=1.0, max_m=4, nfft=None, threshold
     if lengths is None:
         h_len = np.full(rows, pitch, dtype=np.int32)
     else:
+        if isinstance(lengths, DeviceArray) and stream is not None:  # (the download runs on the null stream: drain the writer's)
+            _lib.check(_lib.load().caf_stream_sync(_st(stream)), "sync")
         h_len = np.ascontiguousarray(lengths.get() if isinstance(lengths, DeviceArray) else lengths, dtype=np.int32)
     nfft = default_nfft(h_len.max() if rows else 1) if nfft is None else int(nfft)
     moments = [0] + [m for m in (2, 4, 8) if m <= max_m]

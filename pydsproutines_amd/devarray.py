@@ -21,7 +21,7 @@ from . import _lib
 
 
 class DeviceArray:
-    __slots__ = ("ptr", "shape", "dtype", "_base", "_owned")
+    __slots__ = ("ptr", "shape", "dtype", "_base", "_owned", "__weakref__")
 
     def __init__(self, shape, dtype, ptr=None, base=None):
         if isinstance(shape, (int, np.integer)):

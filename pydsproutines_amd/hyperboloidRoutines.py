@@ -166,6 +166,8 @@ def lop_range(kind, jobs, omega=WGS84_OMEGA, lmbda=WGS84_LAMBDA, stream=None):
     b = d_jobs.shape[0]
     d_range, d_status = empty((b, 2), np.float64), empty((b,), np.int32)
     _lib.check(_lib.load().caf_lop_range(ct.byref(desc), _p(d_jobs), b, _p(d_range), _p(d_status), stream), "caf_lop_range")
+    if stream is not None and d_jobs is not jobs:  # an uploaded d_jobs goes back to the pool on return: nothing may still read it
+        _lib.check(_lib.load().caf_stream_sync(stream), "caf_stream_sync")
     return d_range, d_status
 
 

@@ -197,6 +197,7 @@ def hermitianEig(d_rx, stream=None):
     d_s, d_u, d_vh = empty((B, rows), np.float64), empty((B, rows, rows), np.complex128), empty((B, rows, rows), np.complex128)
     d_status = empty((B,), np.int32)
     _lib.check(_lib.load().caf_music_eig(_p(d_rx), B, rows, _p(d_s), _p(d_u), _p(d_vh), _p(d_status), stream), "caf_music_eig")
+    _lib.check(_lib.load().caf_stream_sync(stream), "sync")  # (d_status is read on the null stream)
     return d_s, d_u, d_vh, _check_status(d_status.get())
 
 
