@@ -480,7 +480,122 @@ def check(rc, what=""):
     raise RuntimeError("DLL returned an error. " + msg)
 
 
+# ------------------------------------------------------------------------------------------------------------------ the binding
+# How every module above libcaf.so calls it: coercion, status check, out-parameters and the lifetime of what a
+# wrapper uploads for one call are written here once.
+
+
+def ptr(a):
+    """c_void_p of a device array (anything with .ptr); None stays None"""
+    return None if a is None else ct.c_void_p(a.ptr)
+
+
+def stream_arg(stream):
+    """a caller's stream as ctypes takes it: None (the null stream), a c_void_p, or the handle as an int"""
+    if stream is None or isinstance(stream, ct.c_void_p):
+        return stream
+    return ct.c_void_p(int(stream))
+
+
+_POINTERS = {}  # name -> the positions of its pointer parameters: call() looks at these alone (most arguments are numbers)
+_ADDRESSES = frozenset((type(None), int, ct.c_void_p))  # what a pointer parameter takes as it is
+_NO_STREAM = object()
+
+
+def call(name, *args, stream=_NO_STREAM):
+    """libcaf's `name` on `args`: device arrays go as their pointers, structures by reference, `stream=` (for the functions that
+    take one) last; a status other than CAF_OK raises under the function's name."""
+    args = list(args)
+    if stream is not _NO_STREAM:
+        args.append(stream if stream is None else stream_arg(stream))
+    try:
+        pointers = _POINTERS[name]
+    except KeyError:
+        pointers = _POINTERS[name] = [i for i, t in enumerate(_SIGNATURES[name]) if t is _P or issubclass(t, ct._Pointer)]
+    for i in pointers:
+        a = args[i]
+        if type(a) not in _ADDRESSES:
+            try:
+                args[i] = _P(a.ptr)
+            except AttributeError:  # (ctypes arrays, pointers and references go as they are)
+                if isinstance(a, ct.Structure):
+                    args[i] = ct.byref(a)
+    rc = getattr(load(), name)(*args)
+    if rc:
+        check(rc, name)
+
+
+def malloc(nbytes):
+    """the address of a block from the library's pool.  Every wrapper allocates its outputs, so this one call skips call()'s look
+    at the arguments (profiles/r24/bench_ab.txt)"""
+    p = _P()
+    rc = load().caf_malloc(ct.byref(p), nbytes)
+    if rc:
+        check(rc, "caf_malloc")
+    return p.value or 0
+
+
+def query(name, *ins):
+    """the values of `name`'s out-parameters as a tuple: one scalar per POINTER(scalar) entry of its signature after `ins`"""
+    outs = [t._type_() for t in _SIGNATURES[name][len(ins):]]
+    call(name, *ins, *[ct.byref(o) for o in outs])
+    return tuple(o.value for o in outs)
+
+
+def drain(stream):
+    """wait until `stream` (None: the null stream) has run dry"""
+    call("caf_stream_sync", stream=stream)
+
+
+def download(arr, stream, null_too=False):
+    """the host copy of a result queued on `stream`: the stream is drained first (the download runs on the null stream, which a
+    caller's stream is not ordered with); the null stream itself only where the site says so"""
+    if null_too or stream is not None:
+        drain(stream)
+    return arr.get()
+
+
+IF_UPLOADED, CALLER, ALWAYS = "caller's stream, if something was uploaded", "caller's stream", "always, null stream included"
+
+
+class held:
+    """What a wrapper uploads for one call, kept until the stream is done with it.  A block that goes back to the pool under a
+    queued kernel is handed to the pool's next user while that kernel still reads it, so on the way out the stream is drained by
+    the site's rule (IF_UPLOADED, CALLER or ALWAYS) and only then are the uploads let go.  On the way out through an exception the
+    rule does not count: whatever was uploaded is drained, on the null stream too."""
+
+    def __init__(self, stream, rule):
+        if not any(rule is r for r in (IF_UPLOADED, CALLER, ALWAYS)):
+            raise ValueError("held: the rule is one of _lib.IF_UPLOADED, _lib.CALLER and _lib.ALWAYS, found %r" % (rule,))
+        self.stream, self.rule, self.uploads = stream, rule, []
+
+    def put(self, x, dtype=None):
+        """x if it is on the device already, else its upload"""
+        from .devarray import DeviceArray, asarray  # (devarray imports this module)
+
+        if isinstance(x, DeviceArray):
+            return x
+        self.uploads.append(asarray(x, dtype=dtype))
+        return self.uploads[-1]
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        try:
+            if exc_type is not None:
+                if self.uploads:
+                    drain(self.stream)
+            elif self.rule is ALWAYS or (self.rule is CALLER or self.uploads) and self.stream is not None:
+                drain(self.stream)
+        finally:
+            del self.uploads[:]
+        return False
+
+
 def device_count():
+    """0 when the library cannot say (no raise: require_device words the refusal), and on every wrapper's path through
+    require_device, so it keeps its direct call"""
     n = _I32(0)
     rc = load().caf_device_count(ct.byref(n))
     return n.value if rc == CAF_OK else 0

@@ -2,8 +2,6 @@
 transform run on the GPU through ``caf_burst_fft`` (csrc/caf_spectral.hip: k_burst_fold, then the row FFT).
 """
 
-import ctypes as ct
-
 import numpy as np
 
 from . import _lib
@@ -28,14 +26,12 @@ def _run(x, length, ndim, stream):
     if rows * n == 0:
         raise ValueError("x must not be empty")
     out = empty((rows, length), np.complex64)
-    _lib.check(_lib.load().caf_burst_fft(ct.c_void_p(d_x.ptr), rows, n, length, ct.c_void_p(out.ptr), stream), "caf_burst_fft")
+    _lib.call("caf_burst_fft", d_x, rows, n, length, out, stream=stream)
     if ndim == 1:
         out = out.reshape(length)
     if dev:
         return out
-    if stream is not None:  # the download runs on the null stream, which a caller's stream is not ordered with; d_x is still held
-        _lib.check(_lib.load().caf_stream_sync(stream), "caf_stream_sync")
-    return out.get()
+    return _lib.download(out, stream)  # d_x is still held
 
 
 def burstFFT(x, length, stream=None):

@@ -54,10 +54,9 @@ class CAFPlan:
         device=None,
         engine="auto",
     ):
-        lib = _lib.load()
         _lib.require_device()
         if device is not None:
-            _lib.check(lib.caf_set_device(int(device)), "caf_set_device")
+            _lib.call("caf_set_device", int(device))
         tm = np.ascontiguousarray(np.atleast_2d(templates), dtype=np.complex64)
         if tm.ndim != 2:
             raise ValueError("templates must be 1-D or 2-D")
@@ -98,15 +97,11 @@ class CAFPlan:
             raise ValueError("engine must be one of %s" % sorted(_lib.ENGINE_IDS))
         self.engine = engine
         h = ct.c_void_p()
-        _lib.check(lib.caf_plan_create(ct.byref(h), ct.byref(d)), "caf_plan_create")
+        _lib.call("caf_plan_create", ct.byref(h), d)
         self._h = h
         self.max_rx_len = int(max_rx_len)
-        blk, step, nb, ws = ct.c_int32(), ct.c_int32(), ct.c_int32(), ct.c_int64()
-        _lib.check(lib.caf_plan_info(h, ct.byref(blk), ct.byref(step), ct.byref(nb), ct.byref(ws)))
-        self.block, self.step, self.blocks_per_batch, self.workspace_bytes = blk.value, step.value, nb.value, ws.value
-        eng = ct.c_int32()
-        _lib.check(lib.caf_plan_engine(h, ct.byref(eng)))
-        self.engine_used = _lib.ENGINE_NAMES[eng.value]
+        self.block, self.step, self.blocks_per_batch, self.workspace_bytes = _lib.query("caf_plan_info", h)
+        self.engine_used = _lib.ENGINE_NAMES[_lib.query("caf_plan_engine", h)[0]]
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None
@@ -154,10 +149,8 @@ class CAFPlan:
             # caller put into the result object -- it may have been written since, or be a new tensor at an old address --
             # always goes to the library.
             if own_arg:
-                lib = _lib.load()
-                sp = ct.c_void_p(stream) if stream else None
-                _lib.check(lib.caf_memset(ct.c_void_p(res.row_arg.ptr), 0, res.row_arg.nbytes, sp), "caf_memset")
-                _lib.check(lib.caf_stream_sync(sp), "caf_stream_sync")
+                _lib.call("caf_memset", res.row_arg, 0, res.row_arg.nbytes, stream=stream or None)
+                _lib.drain(stream or None)
                 res._row_arg_zeroed = res.row_arg
             skip_arg = res._row_arg_zeroed is res.row_arg
         elif want_arg:
@@ -178,11 +171,7 @@ class CAFPlan:
         o.d_peak_val = res.peak_val.ptr if peak else None
         o.d_peak_delay = res.peak_delay.ptr if peak else None
         o.d_peak_freq = res.peak_freq.ptr if peak else None
-        _lib.check(
-            _lib.load().caf_plan_execute2(self._h, ct.c_void_p(ptr), rx_len, int(shift_start), S, ct.byref(o2),
-                                         ct.c_void_p(stream) if stream else None),
-            "caf_plan_execute",
-        )
+        _lib.call("caf_plan_execute2", self._h, ct.c_void_p(ptr), rx_len, int(shift_start), S, o2, stream=stream or None)
         return res
 
     def run_host(self, rx, shift_start=0, num_shifts=None, surface=False, rows=True, peak=True):
@@ -201,27 +190,24 @@ class CAFPlan:
         pd = np.empty(T, np.int32) if peak else None
         pf = np.empty(T, np.int32) if peak else None
         p = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
-        _lib.check(
-            _lib.load().caf_plan_execute_host(self._h, rx.ctypes.data, rx.size, int(shift_start), S, p(surf), p(rmax),
-                                              p(rarg), p(pv), p(pd), p(pf)),
-            "caf_plan_execute_host",
-        )
+        _lib.call("caf_plan_execute_host", self._h, rx.ctypes.data, rx.size, int(shift_start), S, p(surf), p(rmax), p(rarg), p(pv),
+                  p(pd), p(pf))
         return {"surface": surf, "row_max": rmax, "row_arg": rarg, "peak_val": pv, "peak_delay": pd, "peak_freq": pf}
 
     # ------------------------------------------------------------------------------------
     def watchdog(self):
         """(mark, fft_next) of the persistent engine's polling watchdog: (0, 0) unless its hand-off protocol broke."""
         m = (ct.c_int32 * 2)()
-        _lib.check(_lib.load().caf_plan_watchdog(self._h, m), "caf_plan_watchdog")
+        _lib.call("caf_plan_watchdog", self._h, m)
         return int(m[0]), int(m[1])
 
     def profile(self, enable=True):
-        _lib.check(_lib.load().caf_plan_profile(self._h, 1 if enable else 0))
+        _lib.call("caf_plan_profile", self._h, 1 if enable else 0)
 
     def profile_get(self):
         ms = (ct.c_double * _lib.CAF_NUM_STAGES)()
         n = (ct.c_int64 * _lib.CAF_NUM_STAGES)()
-        _lib.check(_lib.load().caf_plan_profile_get(self._h, ms, n))
+        _lib.call("caf_plan_profile_get", self._h, ms, n)
         return {name: (ms[i], n[i]) for i, name in enumerate(_lib.STAGE_NAMES)}
 
 

@@ -21,16 +21,10 @@ from .devarray import DeviceArray, asarray, empty
 _C64 = np.dtype(np.complex64)
 
 
-def _p(a):
-    return ct.c_void_p(a.ptr) if a is not None else None
-
-
 def cancel_geometry():
     """(samples at most, template samples per work item, samples per thread, rotor re-seed interval, jobs at most, rates at most,
     frequencies at most) of the search."""
-    v = [ct.c_int32(0) for _ in range(7)]
-    _lib.check(_lib.load().caf_cancel_geometry(*[ct.byref(x) for x in v]), "caf_cancel_geometry")
-    return tuple(int(x.value) for x in v)
+    return _lib.query("caf_cancel_geometry")
 
 
 def _templates(sigs, what, one_row):
@@ -128,22 +122,20 @@ class _SearchResult:
 
 
 def _search(d_sigs, B, N, d_rx, rx_len, d_idx, nu0, dnu, K, rates, surface=False):
-    lib = _lib.load()
     limits = cancel_geometry()
     if N > limits[0] or B > limits[4] or rates.size > limits[5] or K > limits[6]:
         raise ValueError("cancellation search: at most %d samples, %d jobs, %d accelerations and %d frequencies per call "
                          "(found %d, %d, %d, %d)." % (limits[0], limits[4], limits[5], limits[6], N, B, rates.size, K))
     d_rates = asarray(rates)
     r = _SearchResult(B, rates.size, K, surface)
-    _lib.check(lib.caf_cancel_search(_p(d_sigs), B, N, _p(d_rx), rx_len, _p(d_idx), nu0, dnu, K, _p(d_rates), rates.size,
-                                     ct.c_void_p(r.jk.ptr), ct.c_void_p(r.jk.ptr + 4 * B), r.row(0), r.row(1), r.row(2), r.row(4), r.row(5),
-                                     r.row(6), r.row(7), _p(r.surface), None), "caf_cancel_search")
+    _lib.call("caf_cancel_search", d_sigs, B, N, d_rx, rx_len, d_idx, nu0, dnu, K, d_rates, rates.size, r.jk,
+              ct.c_void_p(r.jk.ptr + 4 * B), r.row(0), r.row(1), r.row(2), r.row(4), r.row(5), r.row(6), r.row(7), r.surface,
+              stream=None)
     return r
 
 
 def _subtract(d_sigs, B, N, d_rx, rx_len, d_idx, r, d_out):
-    _lib.check(_lib.load().caf_cancel_subtract(_p(d_sigs), B, N, _p(d_rx), rx_len, _p(d_idx), r.row(0), r.row(1), r.row(2), _p(d_out), None),
-               "caf_cancel_subtract")
+    _lib.call("caf_cancel_subtract", d_sigs, B, N, d_rx, rx_len, d_idx, r.row(0), r.row(1), r.row(2), d_out, stream=None)
 
 
 def searchAndCancel(sig, rx, idx, freqs, accels=None, fs=1.0, returnSurface=False):
@@ -198,13 +190,12 @@ def cancelSignalsAtIdx(sigs, rx, idxs, freqs=None, accels=None, fs=1.0):
     if N > limits[0] or B > limits[4]:
         raise ValueError("%s: at most %d samples and %d templates per call (found %d, %d)." % (what, limits[0], limits[4], N, B))
     _lib.require_device()
-    lib = _lib.load()
     d_sigs, d_rx, d_idx = asarray(s), asarray(x), asarray(h_idx)
     r = _SearchResult(B)
     r.stats[0].set(per_job[0])
     r.stats[1].set(per_job[1])
-    _lib.check(lib.caf_cancel_estimate(_p(d_sigs), B, N, _p(d_rx), rx_len, _p(d_idx), r.row(0), r.row(1), r.row(2), r.row(4), r.row(5), r.row(6),
-                                       r.row(7), None), "caf_cancel_estimate")
+    _lib.call("caf_cancel_estimate", d_sigs, B, N, d_rx, rx_len, d_idx, r.row(0), r.row(1), r.row(2), r.row(4), r.row(5), r.row(6),
+              r.row(7), stream=None)
     out = empty((rx_len,), np.complex64)
     _subtract(d_sigs, B, N, d_rx, rx_len, d_idx, r, out)
     amps = r.host()["amp"].copy()

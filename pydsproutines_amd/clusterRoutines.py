@@ -45,16 +45,6 @@ SCORE_BITS = {"sil": 1, "db": 2, "ch": 4}
 KMeansResult = namedtuple("KMeansResult", "labels centers counts inertia n_iter status index best k_list n_init")
 
 
-def _p(a):
-    return ct.c_void_p(a.ptr) if a is not None else None
-
-
-def _st(stream):
-    if stream is None or isinstance(stream, ct.c_void_p):
-        return stream
-    return ct.c_void_p(int(stream))
-
-
 def _i32(a):
     a = np.ascontiguousarray(a, dtype=np.int32)
     return a, a.ctypes.data_as(ct.POINTER(ct.c_int32))
@@ -63,12 +53,8 @@ def _i32(a):
 def cluster_geometry(pitch, D=1, kmax=MAX_K):
     """dict(form, threads, tile, lloyd_lds_bytes, sil_lds_bytes, scratch_bytes) for problems of `pitch` points in D dimensions
     and up to kmax clusters: form "lds" (Lloyd keeps the points in LDS), "l2" (reads them every pass) or None (out of range)."""
-    form, threads, tile = ct.c_int32(0), ct.c_int32(0), ct.c_int32(0)
-    a, b, c = ct.c_int64(0), ct.c_int64(0), ct.c_int64(0)
-    _lib.check(_lib.load().caf_cluster_geometry(int(pitch), int(D), int(kmax), ct.byref(form), ct.byref(threads), ct.byref(tile),
-                                                ct.byref(a), ct.byref(b), ct.byref(c)), "caf_cluster_geometry")
-    return dict(form={1: "lds", 2: "l2"}.get(form.value), threads=threads.value, tile=tile.value, lloyd_lds_bytes=a.value,
-                sil_lds_bytes=b.value, scratch_bytes=c.value)
+    form, threads, tile, a, b, c = _lib.query("caf_cluster_geometry", int(pitch), int(D), int(kmax))
+    return dict(form={1: "lds", 2: "l2"}.get(form), threads=threads, tile=tile, lloyd_lds_bytes=a, sil_lds_bytes=b, scratch_bytes=c)
 
 
 def variates(random_state, round_index, n_guesses, n_init, kmax):
@@ -81,8 +67,8 @@ def variates(random_state, round_index, n_guesses, n_init, kmax):
     return u
 
 
-def _problems(x, lengths, mask):
-    """(d_x (P, pitch, D) float64, P, pitch, D, d_lengths, d_mask)"""
+def _problems(x, lengths, mask, put=asarray):
+    """(d_x (P, pitch, D) float64, P, pitch, D, d_lengths, d_mask); what is not on the device is uploaded with put (a holder's)"""
     if isinstance(x, DeviceArray):
         if x.dtype != np.float64:
             raise TypeError("cluster data must be float64, found %s" % x.dtype)
@@ -101,15 +87,15 @@ def _problems(x, lengths, mask):
         raise ValueError("P >= 1 and 1 <= pitch <= 2^17")
     _lib.require_device()
     if d_x is None:
-        d_x = asarray(np.ascontiguousarray(x, dtype=np.float64))
+        d_x = put(x, np.float64)
     d_len = None
     if lengths is not None:
-        d_len = lengths if isinstance(lengths, DeviceArray) else asarray(np.ascontiguousarray(lengths, dtype=np.int32))
+        d_len = put(lengths, np.int32)
         if d_len.dtype != np.int32 or d_len.shape != (P,):
             raise ValueError("lengths: one int32 per problem.")
     d_mask = None
     if mask is not None:
-        d_mask = mask if isinstance(mask, DeviceArray) else asarray(np.ascontiguousarray(mask, dtype=np.uint8))
+        d_mask = put(mask, np.uint8)
         if d_mask.dtype != np.uint8 or d_mask.shape != (P, pitch):
             raise ValueError("mask: uint8 (P, pitch).")
     return d_x, P, pitch, D, d_len, d_mask
@@ -132,7 +118,10 @@ def kmeans(x, k_list, lengths=None, mask=None, n_init=1, init=None, random_state
     init), and the host array best (P, G): the restart of lowest inertia among those with status 0, 2 or 3, the lowest restart
     of equal ones (-1: the problem did not run, or every restart had status 1), which with n_init > 1 costs one download of inertia
     and status (with n_init = 1 it is 0 for every problem that ran)."""
-    d_x, P, pitch, D, d_len, d_mask = _problems(x, lengths, mask)
+    # The holder is entered at the first launch, not here: nothing is queued before it, so nothing reads an upload, and a call
+    # with an empty `problems` returns below without a synchronisation, as it always did.  Keep every launch inside `with h`.
+    h = _lib.held(stream, _lib.CALLER)
+    d_x, P, pitch, D, d_len, d_mask = _problems(x, lengths, mask, h.put)
     ks = _k_list(k_list)
     G, R, kmax = len(ks), int(n_init), max(ks)
     if R < 1 or int(max_iter) < 1:
@@ -142,7 +131,6 @@ def kmeans(x, k_list, lengths=None, mask=None, n_init=1, init=None, random_state
     J = P * G * R
     d_cen = empty(shape + (kmax, D), np.float64)
     d_index = None
-    lib = _lib.load()
     if init is not None:
         c0 = np.asarray(init, dtype=np.float64)
         if c0.shape == (G, kmax, D):
@@ -154,7 +142,7 @@ def kmeans(x, k_list, lengths=None, mask=None, n_init=1, init=None, random_state
         d_cen.set(np.ascontiguousarray(c0))
     else:
         u = variates(random_state, round_index, G, R, kmax)
-        d_u = asarray(np.ascontiguousarray(np.broadcast_to(u[None], shape + (kmax,))))
+        d_u = h.put(np.broadcast_to(u[None], shape + (kmax,)))
         d_index = empty(shape + (kmax,), np.int32)
     d_lab = empty(shape + (pitch,), np.int32)
     d_cnt = empty(shape + (kmax,), np.int32)
@@ -165,20 +153,18 @@ def kmeans(x, k_list, lengths=None, mask=None, n_init=1, init=None, random_state
     # the jobs of one problem are contiguous, so each run of consecutive problems is one call on views of the arrays (all
     # problems: one run)
     GR = G * R
-    for a, b in _runs(plist):
-        n = (b - a) * GR
-        sl = slice(a * GR, b * GR)
-        pa, pa_c = _i32(np.repeat(np.arange(a, b), GR))
-        ka, ka_c = _i32(np.tile(np.repeat(ks, R), b - a))
-        f = lambda arr, *tail: _p(arr.reshape((J,) + tail)[sl])  # noqa: E731
-        if init is None:
-            _lib.check(lib.caf_kmeans_seed(_p(d_x), P, pitch, D, _p(d_len), _p(d_mask), pa_c, ka_c, n, kmax, f(d_u, kmax),
-                                           f(d_index, kmax), f(d_cen, kmax, D), _st(stream)), "caf_kmeans_seed")
-        _lib.check(lib.caf_kmeans_lloyd(_p(d_x), P, pitch, D, _p(d_len), _p(d_mask), pa_c, ka_c, n, kmax, int(max_iter),
-                                        f(d_cen, kmax, D), f(d_lab, pitch), f(d_cnt, kmax), f(d_in), f(d_it), f(d_stat),
-                                        _st(stream)), "caf_kmeans_lloyd")
-    if stream is not None:
-        _lib.check(lib.caf_stream_sync(_st(stream)), "sync")
+    with h:
+        for a, b in _runs(plist):
+            n = (b - a) * GR
+            sl = slice(a * GR, b * GR)
+            pa, pa_c = _i32(np.repeat(np.arange(a, b), GR))
+            ka, ka_c = _i32(np.tile(np.repeat(ks, R), b - a))
+            f = lambda arr, *tail: arr.reshape((J,) + tail)[sl]  # noqa: E731
+            if init is None:
+                _lib.call("caf_kmeans_seed", d_x, P, pitch, D, d_len, d_mask, pa_c, ka_c, n, kmax, f(d_u, kmax), f(d_index, kmax),
+                          f(d_cen, kmax, D), stream=stream)
+            _lib.call("caf_kmeans_lloyd", d_x, P, pitch, D, d_len, d_mask, pa_c, ka_c, n, kmax, int(max_iter), f(d_cen, kmax, D),
+                      f(d_lab, pitch), f(d_cnt, kmax), f(d_in), f(d_it), f(d_stat), stream=stream)
     best = np.full((P, G), -1, dtype=np.int64)
     if R == 1:
         best[plist] = 0
@@ -211,37 +197,35 @@ def clusterScores(x, labels, k=None, lengths=None, which=("sil",), points=False,
     that do not count.  One job per row of labels by default (job j: problem j, or job_problem[j]; k[j] clusters, k a number
     or one per job); job_rows selects the row of each job.  which: any of "sil", "db", "ch".  Returns a dict of (J) float64
     DeviceArrays, and "sil_points" (J, pitch) with points=True."""
-    d_x, P, pitch, D, d_len, _ = _problems(x, lengths, None)
-    d_lab = labels if isinstance(labels, DeviceArray) else asarray(np.ascontiguousarray(labels, dtype=np.int32))
-    if d_lab.dtype != np.int32 or d_lab.shape[-1] != pitch:
-        raise ValueError("labels: int32 (rows, pitch).")
-    nrows = d_lab.size // pitch
-    bits = 0
-    for w in which:
-        if w not in SCORE_BITS:
-            raise ValueError("which: any of 'sil', 'db', 'ch'.")
-        bits |= SCORE_BITS[w]
-    if not bits:
-        raise ValueError("which: at least one score.")
-    if points and not bits & 1:
-        raise ValueError("per-point values come with the silhouette.")
-    rows = np.arange(nrows) if job_rows is None else np.asarray(job_rows).ravel()
-    J = len(rows)
-    jp = np.arange(J) if job_problem is None else np.asarray(job_problem).ravel()
-    if k is None:
-        raise ValueError("k: the number of clusters, one number or one per job.")
-    jk = np.broadcast_to(np.asarray(k), (J,)) if np.ndim(k) == 0 else np.asarray(k).ravel()
-    if len(jp) != J or len(jk) != J:
-        raise ValueError("one problem and one k per job.")
-    kmax = int(jk.max()) if J else 1
-    (jp, jp_c), (jk, jk_c), (rows, rows_c) = _i32(jp), _i32(jk), _i32(rows)
-    out = {w: empty((J,), np.float64) for w in ("sil", "db", "ch") if bits & SCORE_BITS[w]}
-    d_pts = empty((J, pitch), np.float64) if points else None
-    _lib.check(_lib.load().caf_cluster_scores(_p(d_x), P, pitch, D, _p(d_len), jp_c, jk_c, J, kmax, _p(d_lab), rows_c, nrows, bits,
-                                              _p(out.get("sil")), _p(out.get("db")), _p(out.get("ch")), _p(d_pts), _st(stream)),
-               "caf_cluster_scores")
-    if stream is not None and (d_x is not x or d_len is not lengths or d_lab is not labels):
-        _lib.check(_lib.load().caf_stream_sync(_st(stream)), "sync")  # (what was uploaded here is freed on return)
+    with _lib.held(stream, _lib.IF_UPLOADED) as h:  # (what is uploaded here is freed on return)
+        d_x, P, pitch, D, d_len, _ = _problems(x, lengths, None, h.put)
+        d_lab = h.put(labels, np.int32)
+        if d_lab.dtype != np.int32 or d_lab.shape[-1] != pitch:
+            raise ValueError("labels: int32 (rows, pitch).")
+        nrows = d_lab.size // pitch
+        bits = 0
+        for w in which:
+            if w not in SCORE_BITS:
+                raise ValueError("which: any of 'sil', 'db', 'ch'.")
+            bits |= SCORE_BITS[w]
+        if not bits:
+            raise ValueError("which: at least one score.")
+        if points and not bits & 1:
+            raise ValueError("per-point values come with the silhouette.")
+        rows = np.arange(nrows) if job_rows is None else np.asarray(job_rows).ravel()
+        J = len(rows)
+        jp = np.arange(J) if job_problem is None else np.asarray(job_problem).ravel()
+        if k is None:
+            raise ValueError("k: the number of clusters, one number or one per job.")
+        jk = np.broadcast_to(np.asarray(k), (J,)) if np.ndim(k) == 0 else np.asarray(k).ravel()
+        if len(jp) != J or len(jk) != J:
+            raise ValueError("one problem and one k per job.")
+        kmax = int(jk.max()) if J else 1
+        (jp, jp_c), (jk, jk_c), (rows, rows_c) = _i32(jp), _i32(jk), _i32(rows)
+        out = {w: empty((J,), np.float64) for w in ("sil", "db", "ch") if bits & SCORE_BITS[w]}
+        d_pts = empty((J, pitch), np.float64) if points else None
+        _lib.call("caf_cluster_scores", d_x, P, pitch, D, d_len, jp_c, jk_c, J, kmax, d_lab, rows_c, nrows, bits, out.get("sil"),
+                  out.get("db"), out.get("ch"), d_pts, stream=stream)
     if points:
         out["sil_points"] = d_pts
     return out

@@ -24,8 +24,8 @@ import ctypes as ct
 import numpy as np
 
 from . import _lib
-from .devarray import empty, asarray
-from .localizationRoutines import LIGHTSPD, WGS84_A, WGS84_INV_F, GridLocalizer, _Source, _k1, _k3, _p, _st
+from .devarray import empty
+from .localizationRoutines import LIGHTSPD, WGS84_A, WGS84_INV_F, GridLocalizer, _Source, _k1, _k3
 
 __all__ = ["LocalizationCRBComponent", "AOA3DCRBComponent", "TDOACRBComponent", "TOACRBComponent", "RTTCRBComponent",
            "FDOACRBComponent", "CRB", "CRBMap", "CRBMapResult", "crb_map_geometry"]
@@ -38,9 +38,7 @@ _OUTPUTS = ("rms", "ellipse", "crb")
 def crb_map_geometry():
     """(points per workgroup, records per staged chunk, singular threshold) of the kernel: the sizes at which it changes path
     and the pivot ratio at or below which a point counts as unobservable."""
-    p, c, t = ct.c_int32(0), ct.c_int32(0), ct.c_double(0.0)
-    _lib.check(_lib.load().caf_crb_map_geometry(ct.byref(p), ct.byref(c), ct.byref(t)), "caf_crb_map_geometry")
-    return int(p.value), int(c.value), float(t.value)
+    return _lib.query("caf_crb_map_geometry")
 
 
 # ---- the reference's components (host NumPy) ---------------------------------------------------------------------------------------
@@ -409,17 +407,16 @@ class CRBMap:
             raise ValueError("at most 65535 measurement sets per call.")
         _lib.require_device()
         desc = src.desc(_lib.CAF_LOCATE_TD, np.dtype(dtype) == np.dtype(np.float32))
-        d_rec = asarray(np.ascontiguousarray(rec))
-        d_ss = asarray(starts) if b > 1 else None
-        d_rms = empty((b, n), np.dtype(dtype)) if "rms" in outputs else None
-        d_ell = empty((b, n, 3), np.float64) if "ellipse" in outputs else None
-        d_crb = empty((b, n, 6), np.float64) if "crb" in outputs else None
-        d_lo, d_li, d_hi, d_hi_i = empty((b,), np.float64), empty((b,), np.int64), empty((b,), np.float64), empty((b,), np.int64)
-        normal = (ct.c_double * 3)(*self.normal) if self.normal is not None else None
-        _lib.check(_lib.load().caf_crb_map(ct.byref(desc), _p(d_rec), rec.shape[0], _p(d_ss), b, self.constraint, normal, _p(d_crb),
-                                           _p(d_ell), _p(d_rms), _p(d_lo), _p(d_li), _p(d_hi), _p(d_hi_i), _st(stream)), "caf_crb_map")
-        if stream is not None:  # the uploads above go back to the pool on return: on a caller's stream nothing may still read them
-            _lib.check(_lib.load().caf_stream_sync(_st(stream)), "caf_stream_sync")
+        with _lib.held(stream, _lib.CALLER) as h:  # (on a caller's stream nothing may still read the uploads on return)
+            d_rec = h.put(rec)
+            d_ss = h.put(starts) if b > 1 else None
+            d_rms = empty((b, n), np.dtype(dtype)) if "rms" in outputs else None
+            d_ell = empty((b, n, 3), np.float64) if "ellipse" in outputs else None
+            d_crb = empty((b, n, 6), np.float64) if "crb" in outputs else None
+            d_lo, d_li, d_hi, d_hi_i = empty((b,), np.float64), empty((b,), np.int64), empty((b,), np.float64), empty((b,), np.int64)
+            normal = (ct.c_double * 3)(*self.normal) if self.normal is not None else None
+            _lib.call("caf_crb_map", desc, d_rec, rec.shape[0], d_ss, b, self.constraint, normal, d_crb, d_ell, d_rms, d_lo, d_li,
+                      d_hi, d_hi_i, stream=stream)
 
         def grid_out(d, tail):
             if d is None:

@@ -8,8 +8,6 @@ real limit of this implementation is hit.  dtype checks raise TypeError, shape/r
 ValueError, exactly as upstream.  Argmax tie-breaks follow NumPy (lowest index).
 """
 
-import ctypes as ct
-
 import numpy as np
 
 from . import _lib
@@ -27,10 +25,6 @@ requireCupyArray = requireDeviceArray  # upstream name (cupyHelpers.py:74-77)
 cupyRequireDtype = requireDtype  # upstream name (cupyHelpers.py:50-69)
 
 
-def _p(a):
-    return ct.c_void_p(a.ptr) if a is not None else None
-
-
 def cupyCheckExceedsSharedMem(requestedBytes, maximumBytes=160 * 1024):
     """ref: cupyHelpers.py:72-77; the limit here is the 160 KiB LDS of a CDNA4 CU."""
     if requestedBytes > maximumBytes:
@@ -46,7 +40,7 @@ def cupyGetEnoughBlocks(length, computedPerBlock):
 def cupyCopyGroups32fc(x, y, xStarts, yStarts, lengths, threads_per_blk=256):
     """ref: cupyExtensions.py:41-83.  y[yStarts[b]+i] = x[xStarts[b]+i], i < lengths[b]."""
     assert len(xStarts) == len(yStarts) and len(xStarts) == len(lengths)
-    _lib.check(_lib.load().caf_copy_groups(_p(x), _p(y), _p(xStarts), _p(yStarts), _p(lengths), len(xStarts), None))
+    _lib.call("caf_copy_groups", x, y, xStarts, yStarts, lengths, len(xStarts), stream=None)
 
 
 def cupyCopySlicesToMatrix_32fc(d_x, d_sliceBounds, rowLength=None, THREADS_PER_BLOCK=128):
@@ -58,8 +52,7 @@ def cupyCopySlicesToMatrix_32fc(d_x, d_sliceBounds, rowLength=None, THREADS_PER_
         b = d_sliceBounds.get()
         rowLength = int(np.max(b[:, 1] - b[:, 0]))
     d_out = empty((numSlices, rowLength), np.complex64)
-    _lib.check(_lib.load().caf_copy_slices_to_matrix(_p(d_x), d_x.size, _p(d_sliceBounds), 2, 0, 0, int(rowLength),
-                                                     numSlices, _p(d_out), None))
+    _lib.call("caf_copy_slices_to_matrix", d_x, d_x.size, d_sliceBounds, 2, 0, 0, int(rowLength), numSlices, d_out, stream=None)
     return d_out
 
 
@@ -73,8 +66,8 @@ def cupyCopyEqualSlicesToMatrix_32fc(d_x, d_xStartIdxs, rowLength, d_out=None):
         requireDtype(np.complex64, d_out)
         if d_out.shape != (d_xStartIdxs.size, rowLength):
             raise ValueError("d_out must have the shape %d, %d" % (d_xStartIdxs.size, rowLength))
-    _lib.check(_lib.load().caf_copy_slices_to_matrix(_p(d_x), d_x.size, _p(d_xStartIdxs), 1, 0, 0, int(rowLength),
-                                                     d_xStartIdxs.size, _p(d_out), None))
+    _lib.call("caf_copy_slices_to_matrix", d_x, d_x.size, d_xStartIdxs, 1, 0, 0, int(rowLength), d_xStartIdxs.size, d_out,
+              stream=None)
     return d_out
 
 
@@ -87,8 +80,8 @@ def cupyCopyIncrementalEqualSlicesToMatrix_32fc(d_x, startIdx, increment, rowLen
         requireDtype(np.complex64, d_out)
         if d_out.shape != (numRows, rowLength):
             raise ValueError("d_out must have the shape %d, %d" % (numRows, rowLength))
-    _lib.check(_lib.load().caf_copy_slices_to_matrix(_p(d_x), d_x.size, None, 1, int(startIdx), int(increment),
-                                                     int(rowLength), int(numRows), _p(d_out), None))
+    _lib.call("caf_copy_slices_to_matrix", d_x, d_x.size, None, 1, int(startIdx), int(increment), int(rowLength), int(numRows),
+              d_out, stream=None)
     return d_out
 
 
@@ -102,7 +95,7 @@ def cupyArgmax3d_uint32(d_x, THREADS_PER_BLOCK=128, alsoReturnMaxValue=False):
     numItems, dim1, dim2, dim3 = d_x.shape
     d_argmax = empty((numItems, 3), np.uint32)
     d_max = empty(numItems, np.uint32) if alsoReturnMaxValue else None
-    _lib.check(_lib.load().caf_argmax3d_u32(_p(d_x), numItems, dim1, dim2, dim3, _p(d_argmax), _p(d_max), None))
+    _lib.call("caf_argmax3d_u32", d_x, numItems, dim1, dim2, dim3, d_argmax, d_max, stream=None)
     if alsoReturnMaxValue:
         return d_argmax, d_max
     return d_argmax
@@ -129,8 +122,7 @@ def cupyArgmaxAbsRows_complex64(d_x, d_argmax=None, d_max=None, returnMaxValues=
                 raise ValueError("d_max shape must be 1D of length %d" % numRows)
     else:
         d_max = None
-    _lib.check(_lib.load().caf_argmax_abs_rows(_p(d_x), numRows, length, _p(d_argmax), _p(d_max),
-                                               1 if useNormSqInstead else 0, None))
+    _lib.call("caf_argmax_abs_rows", d_x, numRows, length, d_argmax, d_max, 1 if useNormSqInstead else 0, stream=None)
     if returnMaxValues:
         return d_argmax, d_max
     return d_argmax
@@ -142,14 +134,13 @@ def cupyComplexMagnSq(d_x, out_dtype=np.float64, THREADS_PER_BLOCK=128):
     if out_dtype == np.float32:
         requireDtype(np.complex64, d_x)
         out = empty(d_x.shape, np.float32)
-        _lib.check(_lib.load().caf_complex_magnsq(_p(d_x), d_x.size, 0, _p(out), 0, None))
+        _lib.call("caf_complex_magnsq", d_x, d_x.size, 0, out, 0, stream=None)
         return out
     if out_dtype == np.float64:
         if d_x.dtype not in (np.dtype(np.complex64), np.dtype(np.complex128)):
             raise TypeError("d_x must be complex64 or complex128.")
         out = empty(d_x.shape, np.float64)
-        _lib.check(_lib.load().caf_complex_magnsq(_p(d_x), d_x.size, 1 if d_x.dtype == np.complex128 else 0, _p(out), 1,
-                                                  None))
+        _lib.call("caf_complex_magnsq", d_x, d_x.size, 1 if d_x.dtype == np.complex128 else 0, out, 1, stream=None)
         return out
     raise TypeError("out_dtype must be float32 or float64.")
 
@@ -175,9 +166,8 @@ def multiplySlicesOptimistically(d_x, d_rows, d_sliceStarts, d_sliceLengths, d_r
     if not np.all(d_sliceLengths.get() <= outlength):
         raise ValueError("Some slices exceed the output length!")
     d_out = empty((numSlices, outlength), np.complex64)
-    _lib.check(_lib.load().caf_multiply_slices_indexed_rows(_p(d_x), d_x.size, _p(d_rows), numRows, rowLength,
-                                                            _p(d_sliceStarts), _p(d_sliceLengths), _p(d_rowIdxs),
-                                                            int(outlength), numSlices, _p(d_out), None))
+    _lib.call("caf_multiply_slices_indexed_rows", d_x, d_x.size, d_rows, numRows, rowLength, d_sliceStarts, d_sliceLengths,
+              d_rowIdxs, int(outlength), numSlices, d_out, stream=None)
     return d_out
 
 
@@ -204,8 +194,8 @@ def multiplySlidesNormalised(d_x, d_y, startIdx, idxlen, THREADS_PER_BLOCK=128, 
                 raise ValueError("coefficient should be a single element 1D array.")
             coef = float(c.reshape(-1)[0])
     d_pdts = empty((idxlen, d_x.size), np.complex64)
-    _lib.check(_lib.load().caf_sliding_multiply_normalised(_p(d_x), d_x.size, _p(d_y), d_y.size, int(startIdx),
-                                                           int(idxlen), coef, _p(d_pdts), None))
+    _lib.call("caf_sliding_multiply_normalised", d_x, d_x.size, d_y, d_y.size, int(startIdx), int(idxlen), coef, d_pdts,
+              stream=None)
     return d_pdts
 
 
@@ -233,9 +223,8 @@ def multiTemplateSlidingDotProduct(d_x, d_templates, startIdx, idxlen, d_templat
         raise MemoryError("x is too large to use this kernel.")
     d_templateIdx = empty(idxlen, np.int32)
     d_qf2 = empty(idxlen, np.float32)
-    _lib.check(_lib.load().caf_multi_template_sliding_dot(_p(d_templates), _p(d_templateEnergies), numTemplates,
-                                                          templateLength, _p(d_x), d_x.size, int(startIdx), int(idxlen),
-                                                          _p(d_templateIdx), _p(d_qf2), None))
+    _lib.call("caf_multi_template_sliding_dot", d_templates, d_templateEnergies, numTemplates, templateLength, d_x, d_x.size,
+              int(startIdx), int(idxlen), d_templateIdx, d_qf2, stream=None)
     return d_templateIdx, d_qf2
 
 
@@ -246,8 +235,7 @@ def cupyFindLocalMaxima(x, minHeight, numOutputPerBlk=32, THREADS_PER_BLK=32, ma
     requireDtype(np.float32, x)
     numPeaksFound = zeros(1, np.int32)
     peakIndex = zeros(maxNumPeaks, np.int32)
-    _lib.check(_lib.load().caf_find_local_maxima(_p(x), x.size, float(minHeight), int(maxNumPeaks), _p(peakIndex),
-                                                 _p(numPeaksFound), None))
+    _lib.call("caf_find_local_maxima", x, x.size, float(minHeight), int(maxNumPeaks), peakIndex, numPeaksFound, stream=None)
     return peakIndex, numPeaksFound
 
 
@@ -258,6 +246,6 @@ def fftRows(d_x, inverse=False, out=None):
     length = d_x.shape[-1]
     if out is None:
         out = empty(d_x.shape, np.complex64)
-    _lib.check(_lib.load().caf_fft_rows(_p(d_x), _p(out), rows, length, 1 if inverse else 0, None))
-    _lib.check(_lib.load().caf_stream_sync(None))
+    _lib.call("caf_fft_rows", d_x, out, rows, length, 1 if inverse else 0, stream=None)
+    _lib.drain(None)
     return out

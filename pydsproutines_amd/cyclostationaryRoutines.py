@@ -45,23 +45,11 @@ BurstParameters = namedtuple(
     "BurstParameters", "order offset baud ratios line_strength index peak side power moments bands nfft")
 
 
-def _p(a):
-    return ct.c_void_p(a.ptr) if a is not None else None
-
-
-def _st(stream):
-    if stream is None or isinstance(stream, ct.c_void_p):
-        return stream
-    return ct.c_void_p(int(stream))
-
-
 def cm_geometry(nfft):
     """dict(form, threads, rows_per_wg, lds_bytes) of a cmLines call at nfft: form "lds" (one kernel, spectra in LDS), "rocfft"
     (the composed form) or None (nfft out of range)."""
-    form, threads, rpw = ct.c_int32(0), ct.c_int32(0), ct.c_int32(0)
-    lds = ct.c_int64(0)
-    _lib.check(_lib.load().caf_cm_geometry(int(nfft), ct.byref(form), ct.byref(threads), ct.byref(rpw), ct.byref(lds)), "caf_cm_geometry")
-    return dict(form={1: "lds", 2: "rocfft"}.get(form.value), threads=threads.value, rows_per_wg=rpw.value, lds_bytes=lds.value)
+    form, threads, rpw, lds = _lib.query("caf_cm_geometry", int(nfft))
+    return dict(form={1: "lds", 2: "rocfft"}.get(form), threads=threads, rows_per_wg=rpw, lds_bytes=lds)
 
 
 def full_band(nfft):
@@ -87,26 +75,21 @@ def cmLines(d_x, lengths=None, nfft=None, moments=(2, 4), bands=None, peak=True,
     if len(bands) != K:
         raise ValueError("cmLines: one band per moment.")
     bands = [full_band(nfft) if b is None else (int(b[0]), int(b[1])) for b in bands]
-    d_len = None
-    if lengths is not None:
-        if isinstance(lengths, DeviceArray):
-            requireDtype(np.int32, lengths)
-            d_len = lengths
-        else:
-            d_len = asarray(np.ascontiguousarray(lengths, dtype=np.int32))
-        if d_len.shape != (rows,):
-            raise ValueError("cmLines: one length per row.")
-    _lib.require_device()
-    arr = ct.c_int32 * K
-    d_index = empty((rows, K), np.int32)
-    d_peak = empty((rows, K), np.float64) if peak else None
-    d_side = empty((rows, K, 2), np.float64) if side else None
-    d_power = empty((rows, K), np.float64) if power else None
-    _lib.check(_lib.load().caf_cm_lines(_p(d_x), rows, pitch, _p(d_len), nfft, arr(*moments), K, arr(*[b[0] for b in bands]),
-                                        arr(*[b[1] for b in bands]), _p(d_index), _p(d_peak), _p(d_side), _p(d_power), _st(stream)),
-               "caf_cm_lines")
-    if stream is not None and d_len is not None and d_len is not lengths:
-        _lib.check(_lib.load().caf_stream_sync(_st(stream)), "sync")  # (the uploaded d_len is freed on return)
+    with _lib.held(stream, _lib.IF_UPLOADED) as h:  # (an uploaded d_len is freed on return)
+        d_len = None
+        if lengths is not None:
+            d_len = h.put(lengths, np.int32)
+            requireDtype(np.int32, d_len)
+            if d_len.shape != (rows,):
+                raise ValueError("cmLines: one length per row.")
+        _lib.require_device()
+        arr = ct.c_int32 * K
+        d_index = empty((rows, K), np.int32)
+        d_peak = empty((rows, K), np.float64) if peak else None
+        d_side = empty((rows, K, 2), np.float64) if side else None
+        d_power = empty((rows, K), np.float64) if power else None
+        _lib.call("caf_cm_lines", d_x, rows, pitch, d_len, nfft, arr(*moments), K, arr(*[b[0] for b in bands]),
+                  arr(*[b[1] for b in bands]), d_index, d_peak, d_side, d_power, stream=stream)
     return d_index, d_peak, d_side, d_power
 
 
@@ -292,16 +275,13 @@ def estimateBursts(d_xbatch, lengths=None, fs=1.0, max_m=4, nfft=None, threshold
     if lengths is None:
         h_len = np.full(rows, pitch, dtype=np.int32)
     else:
-        if isinstance(lengths, DeviceArray) and stream is not None:  # (the download runs on the null stream: drain the writer's)
-            _lib.check(_lib.load().caf_stream_sync(_st(stream)), "sync")
-        h_len = np.ascontiguousarray(lengths.get() if isinstance(lengths, DeviceArray) else lengths, dtype=np.int32)
+        # (a device array's download runs on the null stream: the writer's stream is drained first)
+        h_len = np.ascontiguousarray(_lib.download(lengths, stream) if isinstance(lengths, DeviceArray) else lengths, dtype=np.int32)
     nfft = default_nfft(h_len.max() if rows else 1) if nfft is None else int(nfft)
     moments = [0] + [m for m in (2, 4, 8) if m <= max_m]
     bb = default_baud_band(nfft) if baud_band is None else (int(baud_band[0]), int(baud_band[1]))
     bands = [bb] + [full_band(nfft)] * (len(moments) - 1)
     d_index, d_peak, d_side, d_power = cmLines(d_xbatch, None if lengths is None else h_len, nfft, moments, bands, stream=stream)
-    if stream is not None:
-        _lib.check(_lib.load().caf_stream_sync(_st(stream)), "sync")
-    index, peak, side, power = d_index.get(), d_peak.get(), d_side.get(), d_power.get()
+    index, peak, side, power = _lib.download(d_index, stream), d_peak.get(), d_side.get(), d_power.get()
     order, offset, baud, ratios, strength = burst_parameters(index, peak, side, power, h_len, moments, bands, nfft, fs, max_m, threshold)
     return BurstParameters(order, offset, baud, ratios, strength, index, peak, side, power, tuple(moments), tuple(bands), nfft)

@@ -16,7 +16,6 @@ takes the leading eigenvector in closed form, so a burst agrees with a LAPACK-ba
 rotation, and exactly after ``ambleRotate``.
 """
 
-import ctypes as ct
 import warnings
 
 import numpy as np
@@ -32,21 +31,11 @@ __all__ = ["SimpleDemodulatorPSK", "SimpleDemodulatorBPSK", "SimpleDemodulatorQP
 cupyRequireDtype = requireDtype
 
 
-def _p(a):
-    return ct.c_void_p(a.ptr) if a is not None else None
-
-
-def _st(stream):
-    if stream is None or isinstance(stream, ct.c_void_p):
-        return stream
-    return ct.c_void_p(int(stream))
-
-
 def _zeros(shape, dtype, stream=None):
     """zeros behind the caller's stream (devarray.zeros clears on the null stream)"""
     a = DeviceArray(shape, dtype)
     if a.nbytes:
-        _lib.check(_lib.load().caf_memset(_p(a), 0, a.nbytes, _st(stream)), "caf_memset")
+        _lib.call("caf_memset", a, 0, a.nbytes, stream=stream)
     return a
 
 
@@ -55,10 +44,6 @@ def _dev(a, dtype=None):
     if isinstance(a, DeviceArray):
         return a, False
     return asarray(np.ascontiguousarray(a, dtype=dtype)), True
-
-
-def _sync(stream=None):
-    _lib.check(_lib.load().caf_stream_sync(_st(stream)), "sync")
 
 
 def _run_rows(d_x, rows, xlength, osr, m, lock, map_, d_m=None, d_lengths=None, d_abs=None, want=(), preambles=None,
@@ -102,7 +87,7 @@ def _run_rows(d_x, rows, xlength, osr, m, lock, map_, d_m=None, d_lengths=None, 
         out["payload"] = _zeros((rows, nsym), np.uint8, stream)
         out["count"] = _zeros((rows,), np.uint32, stream)  # (stays 0 where the preamble ends past the row)
         desc.d_best, desc.d_payload, desc.d_count, desc.out_length = out["best"].ptr, out["payload"].ptr, out["count"].ptr, nsym
-    _lib.check(_lib.load().caf_psk_demod_rows(ct.byref(desc), _st(stream)), "caf_psk_demod_rows")
+    _lib.call("caf_psk_demod_rows", desc, stream=stream)
     # The launch is asynchronous and the pool hands freed blocks out again, so whatever was uploaded for this call lives as
     # long as ANY of the results does.
     keep = (d_x, d_m, d_lengths, d_abs, preambles)
@@ -178,8 +163,7 @@ class SimpleDemodulatorPSK:
         d_abs = _dev(abs_x)[0] if abs_x is not None else None
         nsym = x.size // osr
         d_xeo, d_i, d_met = empty((1, nsym), np.complex64), empty(1, np.int32), empty((1, osr), np.float32)
-        _lib.check(_lib.load().caf_eye_opening_batch(_p(d_abs), _p(d_x), 1, x.size, osr, _p(d_xeo), nsym, _p(d_i), _p(d_met), None),
-                   "caf_eye_opening_batch")
+        _lib.call("caf_eye_opening_batch", d_abs, d_x, 1, x.size, osr, d_xeo, nsym, d_i, d_met, stream=None)
         self.eo_metric = d_met.get()[0] / np.float32(nsym)  # the mean; the kernel sums
         i = int(d_i.get()[0])
         xeo = d_xeo.reshape(nsym)
@@ -258,9 +242,8 @@ class SimpleDemodulatorPSK:
         d_amble = asarray(np.ascontiguousarray(amble))
         d_len = asarray(np.array([amble.size], np.int32))
         d_matches = _zeros((searchEnd - searchStart, self.m), np.uint32)
-        _lib.check(_lib.load().caf_compare_int_preambles(_p(d_syms), 1, syms.size, searchStart, searchEnd, _p(d_amble), amble.size,
-                                                         _p(d_len), 1, amble.size, self.m, None, _p(d_matches), None),
-                   "caf_compare_int_preambles")
+        _lib.call("caf_compare_int_preambles", d_syms, 1, syms.size, searchStart, searchEnd, d_amble, amble.size, d_len, 1,
+                  amble.size, self.m, None, d_matches, stream=None)
         self.matches = d_matches.get()
         best = int(np.argmax(self.matches))  # first maximum, search index major
         where, rotation = divmod(best, self.m)
@@ -394,10 +377,8 @@ class CupyDemodulatorPSK:
         d_abs = _dev(abs_x)[0] if abs_x is not None else None
         nsym = x.size // osr
         d_xeo, d_i, d_met = empty((1, nsym), np.complex64), empty(1, np.int32), empty((1, osr), np.float32)
-        _lib.check(_lib.load().caf_eye_opening_batch(_p(d_abs), _p(d_x), 1, x.size, osr, _p(d_xeo), nsym, _p(d_i), _p(d_met),
-                                                     _st(stream)), "caf_eye_opening_batch")
-        _sync(stream)
-        self.eo_metric = asarray(d_met.get()[0] / np.float32(nsym))
+        _lib.call("caf_eye_opening_batch", d_abs, d_x, 1, x.size, osr, d_xeo, nsym, d_i, d_met, stream=stream)
+        self.eo_metric = asarray(_lib.download(d_met, stream, null_too=True)[0] / np.float32(nsym))
         return d_xeo.reshape(nsym), d_i.reshape(())
 
     def getEyeOpeningBatch(self, xbatch, osr: int, abs_xbatch):
@@ -437,10 +418,9 @@ class CupyDemodulatorPSK:
         d_mask = _dev(psk_m)[0] if psk_m is not None else None
         d_lengths = asarray(np.asarray(lengths, dtype=np.int32))
         d_matches = _zeros((numSignals, len(lengths), searchEnd - searchStart, m), np.uint32, stream)
-        _lib.check(_lib.load().caf_compare_int_preambles(_p(d_s), numSignals, symsLength, int(searchStart), int(searchEnd), _p(d_pre),
-                                                         int(d_preamble_concat.size), _p(d_lengths), len(lengths),
-                                                         int(np.max(lengths)), int(m), _p(d_mask), _p(d_matches), _st(stream)),
-                   "caf_compare_int_preambles")
+        _lib.call("caf_compare_int_preambles", d_s, numSignals, symsLength, int(searchStart), int(searchEnd), d_pre,
+                  int(d_preamble_concat.size), d_lengths, len(lengths), int(np.max(lengths)), int(m), d_mask, d_matches,
+                  stream=stream)
         d_matches._base = (d_s, d_pre, d_mask, d_lengths)  # (uploaded arrays live as long as the asynchronous result)
         return d_matches
 
@@ -481,10 +461,8 @@ class CupyDemodulatorPSK:
             d_out = _zeros((numRows, outLength), np.uint8, stream)
         if alsoReturnWrittenCounts and d_count is None:
             d_count = _zeros(numRows, np.uint32, stream)
-        _lib.check(_lib.load().caf_cut_rotate_gray(_p(d_idx), numRows, _p(d_s), symsLength, _p(d_kl), int(d_preambleLengths.size),
-                                                   _p(d_stop), int(m), int(outLength), _p(d_out),
-                                                   _p(d_count) if alsoReturnWrittenCounts else None, _p(d_mask), _st(stream)),
-                   "caf_cut_rotate_gray")
+        _lib.call("caf_cut_rotate_gray", d_idx, numRows, d_s, symsLength, d_kl, int(d_preambleLengths.size), d_stop, int(m),
+                  int(outLength), d_out, d_count if alsoReturnWrittenCounts else None, d_mask, stream=stream)
         d_out._base = (d_idx, d_s, d_kl, d_stop, d_mask, d_out._base)
         if alsoReturnWrittenCounts:
             return d_out, d_count
@@ -530,8 +508,8 @@ class CupyDemodulatorQPSK:
     def _eye(xbatch, osr, abs_xbatch, d_xeo, rows, stream):
         d_x, _ = _dev(xbatch)
         d_abs = _dev(abs_xbatch)[0] if abs_xbatch is not None else None
-        _lib.check(_lib.load().caf_eye_opening_batch(_p(d_abs), _p(d_x), rows, xbatch.shape[1], int(osr), _p(d_xeo), d_xeo.shape[1],
-                                                     None, None, _st(stream)), "caf_eye_opening_batch")
+        _lib.call("caf_eye_opening_batch", d_abs, d_x, rows, xbatch.shape[1], int(osr), d_xeo, d_xeo.shape[1], None, None,
+                  stream=stream)
 
     @staticmethod
     def _getEyeOpeningBatch(xbatch, osr: int, abs_xbatch=None, d_xeo=None, count: int = None, THREADS_PER_BLOCK: int = 128,
@@ -574,8 +552,7 @@ class CupyDemodulatorQPSK:
         d_x, _ = _dev(x)
         d_abs = _dev(abs_x)[0] if abs_x is not None else None
         d_met = empty((1, osr), np.float32)
-        _lib.check(_lib.load().caf_eye_opening_batch(_p(d_abs), _p(d_x), 1, x.size, int(osr), None, 0, None, _p(d_met), None),
-                   "caf_eye_opening_batch")
+        _lib.call("caf_eye_opening_batch", d_abs, d_x, 1, x.size, int(osr), None, 0, None, d_met, stream=None)
         self.eo_metric = d_met.reshape(osr)
 
     def gather(self, reim):
@@ -586,7 +563,7 @@ class CupyDemodulatorQPSK:
         row = self.d_reim_batch[self.bctr]
         if isinstance(reim, DeviceArray):
             cupyRequireDtype(np.complex64, reim)
-            _lib.check(_lib.load().caf_d2d(_p(row), _p(reim), row.nbytes, None), "caf_d2d")
+            _lib.call("caf_d2d", row, reim, row.nbytes, stream=None)
         else:
             row.set(np.ascontiguousarray(reim, dtype=np.complex64).reshape(self.batchLength))
         self.bctr = self.bctr + 1
@@ -597,16 +574,14 @@ class CupyDemodulatorQPSK:
     @staticmethod
     def _demod_into(d_xeo, rows, L, amble, searchStart, searchlength, numBitsPerBurst, d_reimc, d_syms32, d_bm, d_br, d_bi, d_bits,
                     d_sym8, stream):
-        lib = _lib.load()
         d_amble, _ = _dev(amble)
         desc = _lib.CafDemodDesc()
         desc.d_x, desc.rows, desc.xlength, desc.osr, desc.m = d_xeo.ptr, rows, L, 1, 4
         desc.lock, desc.map = _lib.CAF_DEMOD_LOCK_EIG, _lib.CAF_DEMOD_MAP_GRAYBATCH
         desc.d_syms, desc.d_reimc = d_sym8.ptr, d_reimc.ptr
-        _lib.check(lib.caf_psk_demod_rows(ct.byref(desc), _st(stream)), "caf_psk_demod_rows")
-        _lib.check(lib.caf_amble_search_bits(_p(d_sym8), rows, L, _p(d_amble), int(amble.size), int(searchStart), int(searchlength),
-                                             _p(d_syms32), _p(d_bm), _p(d_br), _p(d_bi), _p(d_bits), int(numBitsPerBurst),
-                                             _st(stream)), "caf_amble_search_bits")
+        _lib.call("caf_psk_demod_rows", desc, stream=stream)
+        _lib.call("caf_amble_search_bits", d_sym8, rows, L, d_amble, int(amble.size), int(searchStart), int(searchlength), d_syms32,
+                  d_bm, d_br, d_bi, d_bits, int(numBitsPerBurst), stream=stream)
         # the uint8 symbols and an uploaded amble live as long as the results (asynchronous on the caller's stream)
         d_bits._base = (d_sym8, d_amble, d_xeo)
 
@@ -758,9 +733,8 @@ def _cp2fsk_tones(h, up):
 def _tone_metric(d_x, rows, xlength, up, h, start, step, count, want, stream=None):
     """One launch of caf_cp2fsk_tone_metric; the dict of the (rows, count) outputs named in ``want``: c0, c1, max, bits."""
     out = {k: DeviceArray((rows, count), np.uint8 if k == "bits" else np.float32) for k in want}
-    _lib.check(_lib.load().caf_cp2fsk_tone_metric(_p(d_x), rows, xlength, int(up), float(h), int(start), int(step), int(count),
-                                                  _p(out.get("c0")), _p(out.get("c1")), _p(out.get("max")), _p(out.get("bits")),
-                                                  _st(stream)), "caf_cp2fsk_tone_metric")
+    _lib.call("caf_cp2fsk_tone_metric", d_x, rows, xlength, int(up), float(h), int(start), int(step), int(count), out.get("c0"),
+              out.get("c1"), out.get("max"), out.get("bits"), stream=stream)
     for arr in out.values():
         arr._base = d_x  # (asynchronous: the input lives as long as the results)
     return out
@@ -858,9 +832,8 @@ class BurstyDemodulatorCP2FSK(BurstyDemodulator):
         d_mi = DeviceArray((rows,), np.int64)
         d_dbits = DeviceArray((rows, starts.size, self.burstLen), np.uint8)
         d_costs = DeviceArray((rows, searchCount), np.float64)
-        _lib.check(_lib.load().caf_cp2fsk_bursty_demod(_p(d_x), rows, n, int(self.up), float(self.h), int(self.burstLen),
-                                                       starts.ctypes.data, int(starts.size), int(searchStart), int(searchCount),
-                                                       _p(d_mi), _p(d_dbits), _p(d_costs), _st(stream)), "caf_cp2fsk_bursty_demod")
+        _lib.call("caf_cp2fsk_bursty_demod", d_x, rows, n, int(self.up), float(self.h), int(self.burstLen), starts.ctypes.data,
+                  int(starts.size), int(searchStart), int(searchCount), d_mi, d_dbits, d_costs, stream=stream)
         for arr in (d_mi, d_dbits, d_costs):
             arr._base = d_x
         return d_dbits, d_mi, d_costs

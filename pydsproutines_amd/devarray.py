@@ -30,9 +30,7 @@ class DeviceArray:
         self.dtype = np.dtype(dtype)
         self._base = base
         if ptr is None:
-            p = ct.c_void_p()
-            _lib.check(_lib.load().caf_malloc(ct.byref(p), self.nbytes), "caf_malloc")
-            self.ptr = p.value or 0
+            self.ptr = _lib.malloc(self.nbytes)
             self._owned = True
         else:
             self.ptr = int(ptr)
@@ -72,7 +70,7 @@ class DeviceArray:
     def get(self):
         out = np.empty(self.shape, dtype=self.dtype)
         if out.nbytes:
-            _lib.check(_lib.load().caf_d2h(out.ctypes.data, ct.c_void_p(self.ptr), out.nbytes, None), "caf_d2h")
+            _lib.call("caf_d2h", out.ctypes.data, self, out.nbytes, stream=None)
         return out
 
     def set(self, host):
@@ -80,7 +78,7 @@ class DeviceArray:
         if host.shape != self.shape:
             raise ValueError("shape mismatch: %s vs %s" % (host.shape, self.shape))
         if host.nbytes:
-            _lib.check(_lib.load().caf_h2d(ct.c_void_p(self.ptr), host.ctypes.data, host.nbytes, None), "caf_h2d")
+            _lib.call("caf_h2d", self, host.ctypes.data, host.nbytes, stream=None)
         return self
 
     def reshape(self, *shape):
@@ -123,8 +121,8 @@ class DeviceArray:
     def copy(self):
         out = DeviceArray(self.shape, self.dtype)
         if self.nbytes:
-            _lib.check(_lib.load().caf_d2d(ct.c_void_p(out.ptr), ct.c_void_p(self.ptr), self.nbytes, None), "caf_d2d")
-            _lib.check(_lib.load().caf_stream_sync(None), "sync")
+            _lib.call("caf_d2d", out, self, self.nbytes, stream=None)
+            _lib.drain(None)
         return out
 
     def conj(self):
@@ -154,20 +152,18 @@ def empty(shape, dtype=np.float32):
 def zeros(shape, dtype=np.float32):
     a = DeviceArray(shape, dtype)
     if a.nbytes:
-        _lib.check(_lib.load().caf_memset(ct.c_void_p(a.ptr), 0, a.nbytes, None), "caf_memset")
+        _lib.call("caf_memset", a, 0, a.nbytes, stream=None)
     return a
 
 
 def free_all_blocks():
     """Return the allocator's cached blocks to the driver (cp.get_default_memory_pool().free_all_blocks())."""
-    _lib.check(_lib.load().caf_pool_trim(), "caf_pool_trim")
+    _lib.call("caf_pool_trim")
 
 
 def pool_stats():
     """dict(cached_bytes, in_use_bytes, hits, misses) of the caching allocator."""
-    v = [ct.c_int64() for _ in range(4)]
-    _lib.check(_lib.load().caf_pool_stats(*[ct.byref(x) for x in v]), "caf_pool_stats")
-    return dict(zip(("cached_bytes", "in_use_bytes", "hits", "misses"), (int(x.value) for x in v)))
+    return dict(zip(("cached_bytes", "in_use_bytes", "hits", "misses"), _lib.query("caf_pool_stats")))
 
 
 def requireDeviceArray(var):

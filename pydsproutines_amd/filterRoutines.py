@@ -20,10 +20,6 @@ from . import _lib
 from .devarray import DeviceArray, asarray, empty, requireDtype, zeros
 
 
-def _p(a):
-    return ct.c_void_p(a.ptr) if a is not None else None
-
-
 class CupyKernelFilter:
     """ref: filterRoutines.py:95-575."""
 
@@ -63,8 +59,7 @@ class CupyKernelFilter:
                 requireDtype(np.float32, d_outabs)
         else:
             d_outabs = None
-        _lib.check(_lib.load().caf_upfirdn(_p(d_x), rows, n, _p(d_taps), d_taps.size, int(up), int(down), _p(d_out),
-                                           _p(d_outabs), outlen, None))
+        _lib.call("caf_upfirdn", d_x, rows, n, d_taps, d_taps.size, int(up), int(down), d_out, d_outabs, outlen, stream=None)
         return (d_out, d_outabs) if alsoReturnAbs else d_out
 
     def upfirdn_naive(self, d_x, d_taps, up, down, THREADS_PER_BLOCK=256, alsoReturnAbs=False, d_out=None,
@@ -92,8 +87,7 @@ class CupyKernelFilter:
                     raise ValueError("d_outabs must be at least length %d" % outlen)
         else:
             d_outabs = None
-        _lib.check(_lib.load().caf_upfirdn(_p(d_x), 1, d_x.size, _p(d_taps), d_taps.size, int(up), int(down), _p(d_out),
-                                           _p(d_outabs), outlen, None))
+        _lib.call("caf_upfirdn", d_x, 1, d_x.size, d_taps, d_taps.size, int(up), int(down), d_out, d_outabs, outlen, stream=None)
         return (d_out, d_outabs) if alsoReturnAbs else d_out
 
     def run_upfirdn(self, d_x, d_taps, up, down, THREADS_PER_BLOCK=256):
@@ -102,12 +96,11 @@ class CupyKernelFilter:
             raise TypeError("Delay has not been allocated. Re-initialize with memory argument.")
         dl = self.delay.size
         d_xext = empty(dl + d_x.size, np.complex64)
-        lib = _lib.load()
-        _lib.check(lib.caf_d2d(ct.c_void_p(d_xext.ptr), _p(self.delay), dl * 8, None))
-        _lib.check(lib.caf_d2d(ct.c_void_p(d_xext.ptr + dl * 8), _p(d_x), d_x.size * 8, None))
+        _lib.call("caf_d2d", d_xext, self.delay, dl * 8, stream=None)
+        _lib.call("caf_d2d", ct.c_void_p(d_xext.ptr + dl * 8), d_x, d_x.size * 8, stream=None)
         d_out = self.upfirdn_naive(d_xext, d_taps, up, down)
-        _lib.check(lib.caf_d2d(_p(self.delay), ct.c_void_p(d_x.ptr + (d_x.size - dl) * 8), dl * 8, None))
-        _lib.check(lib.caf_stream_sync(None))
+        _lib.call("caf_d2d", self.delay, ct.c_void_p(d_x.ptr + (d_x.size - dl) * 8), dl * 8, stream=None)
+        _lib.drain(None)
         length2return = int(d_x.size * up // down)
         skip = int(dl * up // down)
         return d_out[skip : skip + length2return]
@@ -128,9 +121,8 @@ class CupyKernelFilter:
             raise TypeError("Delay has not been allocated. Re-initialize with memory argument.")
         # (no tap limit: beyond a few hundred taps per kept output libcaf switches to its overlap-save form, any length;
         # the reference's kernel stops where the taps no longer fit its shared memory, cupyHelpers.py:50-77)
-        _lib.check(_lib.load().caf_fir_lfilter(_p(d_x), d_x.size, _p(d_taps), d_taps.size, _p(delay),
-                                               delay.size if delay is not None else 0, int(dsr), int(dsPhase),
-                                               _p(d_out), outlength, None))
+        _lib.call("caf_fir_lfilter", d_x, d_x.size, d_taps, d_taps.size, delay, delay.size if delay is not None else 0, int(dsr),
+                  int(dsPhase), d_out, outlength, stream=None)
         return d_out
 
     def run_filter_smtaps(self, d_x, d_taps, THREADS_PER_BLOCK=128, OUTPUT_PER_BLK=128):
@@ -139,9 +131,8 @@ class CupyKernelFilter:
             raise TypeError("Delay has not been allocated. Re-initialize with memory argument.")
         d_out = self.filter_smtaps(d_x, d_taps, useInternalDelay=True)
         dl = self.delay.size
-        lib = _lib.load()
-        _lib.check(lib.caf_d2d(_p(self.delay), ct.c_void_p(d_x.ptr + (d_x.size - dl) * 8), dl * 8, None))
-        _lib.check(lib.caf_stream_sync(None))
+        _lib.call("caf_d2d", self.delay, ct.c_void_p(d_x.ptr + (d_x.size - dl) * 8), dl * 8, stream=None)
+        _lib.drain(None)
         return d_out
 
     def filter_smtaps_sminput(self, d_x, d_taps, THREADS_PER_BLOCK=128, OUTPUT_PER_BLK=256):
@@ -168,7 +159,7 @@ def cupyMultiMovingAverage(d_x, avgLength, THREADS_PER_BLOCK=32):
     if d_x.shape[0] == 0:
         raise ValueError("Input array must have at least one row.")
     d_avg = empty(d_x.shape, np.float32)
-    _lib.check(_lib.load().caf_moving_average(_p(d_x), d_x.shape[0], d_x.shape[1], int(avgLength), 0, _p(d_avg), None))
+    _lib.call("caf_moving_average", d_x, d_x.shape[0], d_x.shape[1], int(avgLength), 0, d_avg, stream=None)
     return d_avg
 
 
@@ -179,7 +170,7 @@ def cupyMovingAverage(x, avgLength, NUM_PER_THREAD=33, THREADS_PER_BLK=32, sumIn
     if NUM_PER_THREAD % 2 == 0:
         raise ValueError("NUM_PER_THREAD must be odd.")
     d_out = empty(x.shape, np.float32)
-    _lib.check(_lib.load().caf_moving_average(_p(x), 1, x.size, int(avgLength), 1 if sumInstead else 0, _p(d_out), None))
+    _lib.call("caf_moving_average", x, 1, x.size, int(avgLength), 1 if sumInstead else 0, d_out, stream=None)
     return d_out
 
 
@@ -189,7 +180,7 @@ def cupyComplexMovingSum(x, sumLength, NUM_PER_THREAD=33, THREADS_PER_BLK=32, su
     if NUM_PER_THREAD % 2 == 0:
         raise ValueError("NUM_PER_THREAD must be odd.")
     d_out = empty(x.size - sumLength + 1, np.float32)
-    _lib.check(_lib.load().caf_complex_moving_sum(_p(x), x.size, int(sumLength), _p(d_out), None))
+    _lib.call("caf_complex_moving_sum", x, x.size, int(sumLength), d_out, stream=None)
     return d_out
 
 
@@ -210,8 +201,8 @@ def _wola_device(d_x, f_tap, N, Dec, d_hist=None, layout="time"):
     if rows == 0:
         return d_out
     d_taps = asarray(np.ascontiguousarray(f_tap, dtype=np.float32).ravel())
-    _lib.check(_lib.load().caf_wola(_p(d_x), d_x.size, _p(d_hist), d_hist.size if d_hist is not None else 0, _p(d_taps),
-                                    d_taps.size, N, Dec, _LAYOUTS[layout], _p(d_out), rows, None), "caf_wola")
+    _lib.call("caf_wola", d_x, d_x.size, d_hist, d_hist.size if d_hist is not None else 0, d_taps, d_taps.size, N, Dec,
+              _LAYOUTS[layout], d_out, rows, stream=None)
     return d_out
 
 
@@ -278,9 +269,8 @@ class Channeliser:
             if x.size < L:
                 raise ValueError("could not broadcast input array from shape (%d,) into shape (%d,)" % (x.size, L))
             # the new history: the last L input samples, device to device, behind the kernel on the same stream
-            lib = _lib.load()
-            _lib.check(lib.caf_d2d(_p(self._d_delay), ct.c_void_p(x.ptr + (x.size - L) * 8), L * 8, None))
-            _lib.check(lib.caf_stream_sync(None))
+            _lib.call("caf_d2d", self._d_delay, ct.c_void_p(x.ptr + (x.size - L) * 8), L * 8, stream=None)
+            _lib.drain(None)
             return d_out
         x = np.asarray(x)
         if x.size % self.Dec != 0:
@@ -340,7 +330,7 @@ def medfilt(d_x, kernel_size=None):
     _lib.require_device()
     d_x = asarray(d_x)
     d_out = empty(d_x.shape, d_x.dtype)
-    _lib.check(_lib.load().caf_medfilt(_p(d_x), d_x.size, is_f64, W, _p(d_out), None), "caf_medfilt")
+    _lib.call("caf_medfilt", d_x, d_x.size, is_f64, W, d_out, stream=None)
     return d_out
 
 
@@ -350,7 +340,7 @@ def _abs_ampsq(d_x):
         raise TypeError("Must be one of complex64, complex128, float32, float64, found %s" % d_x.dtype)
     code, rdt = _REAL_OF[d_x.dtype]
     d_abs, d_sq = empty(d_x.shape, rdt), empty(d_x.shape, rdt)
-    _lib.check(_lib.load().caf_abs_ampsq(_p(d_x), d_x.size, code, _p(d_abs), _p(d_sq), None), "caf_abs_ampsq")
+    _lib.call("caf_abs_ampsq", d_x, d_x.size, code, d_abs, d_sq, stream=None)
     return d_abs, d_sq
 
 
@@ -377,8 +367,7 @@ def cupyThresholdEdges(d_x, threshold, THREADS_PER_BLOCK=128, edgesMaxPerBlock=N
     rows = -(-n // B)
     d_edges = empty((rows, emax), np.int32)
     d_counts = empty(rows, np.int32)
-    _lib.check(_lib.load().caf_threshold_edges(_p(d_x), n, float(np.float32(threshold)), tpb, emax, _p(d_edges),
-                                               _p(d_counts), None), "caf_threshold_edges")
+    _lib.call("caf_threshold_edges", d_x, n, float(np.float32(threshold)), tpb, emax, d_edges, d_counts, stream=None)
     if not ignoreEdgesCountCheck and rows and np.any(d_counts.get() > emax):
         raise RuntimeError("Some blocks have dropped their edges!")
     return d_edges, d_counts
@@ -393,30 +382,27 @@ def cupyGatherEdges(d_edges, d_edgeBlockCounts, minimumLength=0, maximumLength=2
         raise ValueError("d_edges must be (rows, edgesMaxPerBlock) with one count per row.")
     _lib.require_device()
     rows, emax = d_edges.shape
-    lib = _lib.load()
     cap = max(d_edges.size, 1)
     d_tmp = empty((cap, 2), np.int32)
     K = ct.c_int64(0)
-    _lib.check(lib.caf_gather_edges(_p(d_edges), rows, max(emax, 1), _p(d_edgeBlockCounts), int(minimumLength),
-                                    int(maximumLength), _p(d_tmp), cap, ct.byref(K), None), "caf_gather_edges")
+    _lib.call("caf_gather_edges", d_edges, rows, max(emax, 1), d_edgeBlockCounts, int(minimumLength), int(maximumLength), d_tmp,
+              cap, ct.byref(K), stream=None)
     d_out = empty((K.value, 2), np.int32)
     if K.value:
-        _lib.check(lib.caf_d2d(_p(d_out), _p(d_tmp), d_out.nbytes, None), "caf_d2d")
-        _lib.check(lib.caf_stream_sync(None), "sync")
+        _lib.call("caf_d2d", d_out, d_tmp, d_out.nbytes, stream=None)
+        _lib.drain(None)
     return d_out
 
 
 def _threshold_runs(d_x, threshold):
     """(int64 indices of x > threshold, host array of the positions where each run of consecutive indices starts)."""
     is_f64 = _is_f64(d_x)
-    lib = _lib.load()
     counts = (ct.c_int64 * 2)()
-    _lib.check(lib.caf_threshold_indices(_p(d_x), d_x.size, is_f64, float(threshold), None, 0, None, 0, counts, None),
-               "caf_threshold_indices")
+    _lib.call("caf_threshold_indices", d_x, d_x.size, is_f64, float(threshold), None, 0, None, 0, counts, stream=None)
     d_idx, d_starts = empty(counts[0], np.int64), empty(counts[1], np.int64)
     if counts[0]:
-        _lib.check(lib.caf_threshold_indices(_p(d_x), d_x.size, is_f64, float(threshold), _p(d_idx), counts[0],
-                                             _p(d_starts), counts[1], counts, None), "caf_threshold_indices")
+        _lib.call("caf_threshold_indices", d_x, d_x.size, is_f64, float(threshold), d_idx, counts[0], d_starts, counts[1], counts,
+                  stream=None)
     return d_idx, d_starts.get()
 
 
@@ -502,8 +488,7 @@ class BurstDetector:
         d_x = self.d_medfiltered
         self.edges = asarray(edges)
         self.counts = empty(edges.size - 1, np.int64)
-        _lib.check(_lib.load().caf_histogram(_p(d_x), d_x.size, _is_f64(d_x), _p(self.edges), edges.size, _p(self.counts),
-                                             None), "caf_histogram")
+        _lib.call("caf_histogram", d_x, d_x.size, _is_f64(d_x), self.edges, edges.size, self.counts, stream=None)
         counts = self.counts.get()
 
         # We iterate from 1, because the 0 index shouldn't be compared to the end
@@ -548,7 +533,7 @@ class BurstDetector:
             rows = d_x.size // P
             if rows == 0:
                 raise ValueError("cannot reshape array of size 0 into shape (%d)" % P)
-            _lib.check(_lib.load().caf_column_means(_p(d_x), rows, P, is_f64, 1, _p(d_means), None), "caf_column_means")
+            _lib.call("caf_column_means", d_x, rows, P, is_f64, 1, d_means, stream=None)
             x = d_means.get()[:P].astype(d_x.dtype)
 
             ratio = 1.5

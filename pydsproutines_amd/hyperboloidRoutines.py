@@ -19,12 +19,10 @@ the reference's order.  The reference's quirks are kept where a caller could see
 provided: ``visualize``.  There is no CPU path for the spheroid: without a GPU ``intersectOblateSpheroid`` raises RuntimeError.
 """
 
-import ctypes as ct
-
 import numpy as np
 
 from . import _lib
-from .devarray import DeviceArray, asarray, empty
+from .devarray import DeviceArray, empty
 
 __all__ = ["Hyperboloid", "lop_geometry", "lop_points", "lop_range", "LopPoints", "hyperboloid_jobs", "sphere_jobs", "polyline"]
 
@@ -36,16 +34,10 @@ _SPACINGS = {"list": _lib.CAF_LOP_LIST, "linspace": _lib.CAF_LOP_LINSPACE, "cheb
 _REC = 16  # doubles per job: mu(3) e0(3) e1(3) e2(3) a c p_min p_max
 
 
-def _p(a):
-    return ct.c_void_p(a.ptr) if a is not None else None
-
-
 def lop_geometry():
     """(samples per workgroup of caf_lop_points, jobs per workgroup of caf_lop_range, its search rounds, parameters per round):
     the sizes at which the kernels change path"""
-    v = [ct.c_int32(0) for _ in range(4)]
-    _lib.check(_lib.load().caf_lop_geometry(*(ct.byref(x) for x in v)), "caf_lop_geometry")
-    return tuple(int(x.value) for x in v)
+    return _lib.query("caf_lop_geometry")
 
 
 # ---- job records ------------------------------------------------------------------------------------------------------------------
@@ -162,12 +154,11 @@ def lop_range(kind, jobs, omega=WGS84_OMEGA, lmbda=WGS84_LAMBDA, stream=None):
     desc = _desc(kind, omega, lmbda)
     jobs = _jobs_dev(jobs)
     _lib.require_device()
-    d_jobs = asarray(jobs)
-    b = d_jobs.shape[0]
-    d_range, d_status = empty((b, 2), np.float64), empty((b,), np.int32)
-    _lib.check(_lib.load().caf_lop_range(ct.byref(desc), _p(d_jobs), b, _p(d_range), _p(d_status), stream), "caf_lop_range")
-    if stream is not None and d_jobs is not jobs:  # an uploaded d_jobs goes back to the pool on return: nothing may still read it
-        _lib.check(_lib.load().caf_stream_sync(stream), "caf_stream_sync")
+    with _lib.held(stream, _lib.IF_UPLOADED) as h:  # (an uploaded d_jobs goes back to the pool on return)
+        d_jobs = h.put(jobs)
+        b = d_jobs.shape[0]
+        d_range, d_status = empty((b, 2), np.float64), empty((b,), np.int32)
+        _lib.call("caf_lop_range", desc, d_jobs, b, d_range, d_status, stream=stream)
     return d_range, d_status
 
 
@@ -193,17 +184,15 @@ def lop_points(kind, jobs, omega=WGS84_OMEGA, lmbda=WGS84_LAMBDA, p=None, ranges
     if ranges is not None and (ranges.shape != (b, 2) or ranges.dtype != np.float64):
         raise ValueError("ranges must be a B x 2 float64 table.")
     _lib.require_device()
-    d_jobs = asarray(jobs)
-    d_p = asarray(p) if p is not None else None
-    d_rng = asarray(ranges) if ranges is not None else None
-    desc = _desc(kind, omega, lmbda, spacing, num, d_p)
-    shapes = {"count": ((b, num), np.int32), "phi": ((b, num, 4), np.float64), "xyz": ((b, num, 4, 3), np.float64),
-              "latlon": ((b, num, 4, 2), np.float64), "p": ((b, num), np.float64)}
-    o = {k: (empty(*shapes[k]) if k in want else None) for k in shapes}
-    _lib.check(_lib.load().caf_lop_points(ct.byref(desc), _p(d_jobs), b, _p(d_rng), _p(o["count"]), _p(o["phi"]), _p(o["xyz"]),
-                                          _p(o["latlon"]), _p(o["p"]), stream), "caf_lop_points")
-    if stream is not None:  # the uploads above go back to the pool on return: on a caller's stream nothing may still read them
-        _lib.check(_lib.load().caf_stream_sync(stream), "caf_stream_sync")
+    with _lib.held(stream, _lib.CALLER) as h:  # (the uploads go back to the pool on return: nothing on a caller's stream may read them)
+        d_jobs = h.put(jobs)
+        d_p = h.put(p) if p is not None else None
+        d_rng = h.put(ranges) if ranges is not None else None
+        desc = _desc(kind, omega, lmbda, spacing, num, d_p)
+        shapes = {"count": ((b, num), np.int32), "phi": ((b, num, 4), np.float64), "xyz": ((b, num, 4, 3), np.float64),
+                  "latlon": ((b, num, 4, 2), np.float64), "p": ((b, num), np.float64)}
+        o = {k: (empty(*shapes[k]) if k in want else None) for k in shapes}
+        _lib.call("caf_lop_points", desc, d_jobs, b, d_rng, o["count"], o["phi"], o["xyz"], o["latlon"], o["p"], stream=stream)
     return LopPoints(o["count"], o["phi"], o["xyz"], o["latlon"], o["p"])
 
 

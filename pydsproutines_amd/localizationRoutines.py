@@ -37,7 +37,6 @@ come first).  The CRB functions are host NumPy, as in the reference; ``crbMap`` 
 every grid point on the device (crbRoutines.py).
 """
 
-import ctypes as ct
 from enum import Enum
 
 import numpy as np
@@ -64,28 +63,14 @@ _MODES = {"td": _lib.CAF_LOCATE_TD, "fd": _lib.CAF_LOCATE_FD, "tdfd": _lib.CAF_L
 _RTT = {"rtt": 0, "rtt1": 1, "rtt2": 2}  # caf_locate_rtt and its number of nuisance parameters
 
 
-def _p(a):
-    return ct.c_void_p(a.ptr) if a is not None else None
-
-
-def _st(stream):
-    if stream is None or isinstance(stream, ct.c_void_p):
-        return stream
-    return ct.c_void_p(int(stream))
-
-
 def locate_geometry():
     """(points per workgroup, records per staged chunk) of the kernel: the sizes at which it changes path."""
-    p, c = ct.c_int32(0), ct.c_int32(0)
-    _lib.check(_lib.load().caf_locate_geometry(ct.byref(p), ct.byref(c)), "caf_locate_geometry")
-    return int(p.value), int(c.value)
+    return _lib.query("caf_locate_geometry")
 
 
 def locate_rtt_geometry():
     """the same two sizes of the round-trip kernel; a set of at most one chunk is staged once for both passes"""
-    p, c = ct.c_int32(0), ct.c_int32(0)
-    _lib.check(_lib.load().caf_locate_rtt_geometry(ct.byref(p), ct.byref(c)), "caf_locate_rtt_geometry")
-    return int(p.value), int(c.value)
+    return _lib.query("caf_locate_rtt_geometry")
 
 
 # ---- host preparation of the measurement records ------------------------------------------------------------------------------
@@ -337,19 +322,16 @@ def _search(source, mode, records, set_starts=None, cost=None, argmin=False, str
         raise ValueError("the cost grid is float64 or float32.")
     _lib.require_device()
     desc = source.desc(_MODES[mode] if nuisance is None else _lib.CAF_LOCATE_TD, cost is not None and np.dtype(cost) == np.dtype(np.float32))
-    d_rec = asarray(records)
-    d_ss = asarray(ss) if ss is not None else None
-    d_cost = empty((b, source.n), np.dtype(cost)) if cost is not None else None
-    d_val = empty((b,), np.float64) if argmin else None
-    d_idx = empty((b,), np.int64) if argmin else None
-    if nuisance is None:
-        _lib.check(_lib.load().caf_locate_grid(ct.byref(desc), _p(d_rec), k, _p(d_ss), b, _p(d_cost), _p(d_val), _p(d_idx), _st(stream)),
-                   "caf_locate_grid")
-    else:
-        _lib.check(_lib.load().caf_locate_rtt(ct.byref(desc), _p(d_rec), k, _p(d_ss), b, nuisance, _p(d_cost), _p(d_val), _p(d_idx),
-                                              _st(stream)), "caf_locate_rtt")
-    if stream is not None:  # the uploads above go back to the pool on return: on a caller's stream nothing may still read them
-        _lib.check(_lib.load().caf_stream_sync(_st(stream)), "caf_stream_sync")
+    with _lib.held(stream, _lib.CALLER) as h:  # (the uploads go back to the pool on return: nothing on a caller's stream may read them)
+        d_rec = h.put(records)
+        d_ss = h.put(ss) if ss is not None else None
+        d_cost = empty((b, source.n), np.dtype(cost)) if cost is not None else None
+        d_val = empty((b,), np.float64) if argmin else None
+        d_idx = empty((b,), np.int64) if argmin else None
+        if nuisance is None:
+            _lib.call("caf_locate_grid", desc, d_rec, k, d_ss, b, d_cost, d_val, d_idx, stream=stream)
+        else:
+            _lib.call("caf_locate_rtt", desc, d_rec, k, d_ss, b, nuisance, d_cost, d_val, d_idx, stream=stream)
     return d_cost, d_val, d_idx
 
 

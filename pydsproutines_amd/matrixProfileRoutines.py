@@ -34,19 +34,12 @@ from .devarray import DeviceArray, asarray, empty, requireDeviceArray, requireDt
 _FIRST_CAPACITY = 1 << 16  # runs fetched by the first chains call; a record with more is counted first and fetched by a second call
 
 
-def _p(a):
-    return ct.c_void_p(a.ptr) if a is not None else None
-
-
 def mp_geometry(n=0, w=0, num_diagonals=0):
     """dict(segment, chunk, max_window, products_per_thread, energy_bytes, chains_bytes, profile_bytes, lds_bytes) of the kernels:
     window positions and diagonals per work item, the longest window, and for a record of n samples and a window w the sizes that
     follow (0 where n or w is out of range)."""
-    i32 = [ct.c_int32(0) for _ in range(4)]
-    i64 = [ct.c_int64(0) for _ in range(4)]
-    _lib.check(_lib.load().caf_mp_geometry(int(n), int(w), int(num_diagonals), *[ct.byref(v) for v in i32 + i64]), "caf_mp_geometry")
     names = ("segment", "chunk", "max_window", "products_per_thread", "energy_bytes", "chains_bytes", "profile_bytes", "lds_bytes")
-    return dict(zip(names, (int(v.value) for v in i32 + i64)))
+    return dict(zip(names, _lib.query("caf_mp_geometry", int(n), int(w), int(num_diagonals))))
 
 
 def packed_offsets(numWindows, k0, k1):
@@ -129,7 +122,7 @@ class MatrixProfile:
         _lib.require_device()
         d_x = asarray(x)
         d_out = empty((int(packed_offsets(M, k0, k1)[-1]),), np.float32)
-        _lib.check(_lib.load().caf_mp_raw(_p(d_x), n, W, k0, k1, _p(d_out), None), "caf_mp_raw")
+        _lib.call("caf_mp_raw", d_x, n, W, k0, k1, d_out, stream=None)
         return d_out, k0, k1, M
 
     def _runs_device(self, x, diagonals, diagIdx, what):
@@ -151,15 +144,14 @@ class MatrixProfile:
             h = None
             k0, k1 = self._range(diagonals, M, what)
         _lib.require_device()
-        lib = _lib.load()
         d_x = asarray(x)
         d_diag = None if h is None else asarray(h.astype(np.int32))
         total = ct.c_int64(0)
         cap = _FIRST_CAPACITY
         while True:
             d_runs = empty((cap, 3), np.int32)
-            _lib.check(lib.caf_mp_chains(_p(d_x), n, W, k0, k1, _p(d_diag), 0 if h is None else h.size, float(thr), cap, _p(d_runs),
-                                         ct.byref(total), None), "caf_mp_chains")
+            _lib.call("caf_mp_chains", d_x, n, W, k0, k1, d_diag, 0 if h is None else h.size, float(thr), cap, d_runs,
+                      ct.byref(total), stream=None)
             if total.value <= cap:
                 return d_runs[: total.value].get()
             cap = int(total.value)
@@ -174,7 +166,7 @@ class MatrixProfile:
         _lib.require_device()
         d_x = asarray(x)
         d_val, d_idx = empty((M,), np.float32), empty((M,), np.int32)
-        _lib.check(_lib.load().caf_mp_profile(_p(d_x), n, W, kmin, kmax, _p(d_val), _p(d_idx), None), "caf_mp_profile")
+        _lib.call("caf_mp_profile", d_x, n, W, kmin, kmax, d_val, d_idx, stream=None)
         return d_val, d_idx
 
     # -- upstream's interface --------------------------------------------------------------------------------------------

@@ -21,8 +21,6 @@ eigenvalues are known: ``p`` above the numerical rank with ``useSignalAsNumerato
 (``s[-1] <= rows 2^-52 s[0]``).  ``musicAlg(useAutoCorr=True)`` raises NotImplementedError.  An eigensolve that runs out of sweeps
 raises RuntimeError.  There is no host fallback: without a device every ``run`` raises."""
 
-import ctypes as ct
-
 import numpy as np
 
 from . import _lib
@@ -45,15 +43,9 @@ _EPS = 2.0 ** -52
 _COMPLEX = (np.dtype(np.complex64), np.dtype(np.complex128))
 
 
-def _p(a):
-    return ct.c_void_p(a.ptr) if a is not None else None
-
-
 def music_geometry():
     """(rows at least, rows at most, sweep limit, covariance tile, batch at most) of the kernels."""
-    v = [ct.c_int32(0) for _ in range(5)]
-    _lib.check(_lib.load().caf_music_geometry(*[ct.byref(x) for x in v]), "caf_music_geometry")
-    return tuple(int(x.value) for x in v)
+    return _lib.query("caf_music_geometry")
 
 
 # ---- checks: plain Python, nothing here touches the library ----------------------------------------------------------------
@@ -180,9 +172,8 @@ def snapshotCovariance(d_x, segs, rows, jump, scale, fwdBwd=False, avgToToeplitz
     _lib.require_device()
     B, nseg = segs.shape[:2]
     d_rx = empty((B, rows, rows), np.complex128)
-    _lib.check(_lib.load().caf_music_cov(_p(d_x), int(d_x.dtype == _COMPLEX[1]), d_x.size, segs.ctypes.data, nseg, B, rows, int(jump),
-                                         scale.ctypes.data, int(bool(fwdBwd)), int(bool(avgToToeplitz)), _p(d_rx), stream),
-               "caf_music_cov")
+    _lib.call("caf_music_cov", d_x, int(d_x.dtype == _COMPLEX[1]), d_x.size, segs.ctypes.data, nseg, B, rows, int(jump),
+              scale.ctypes.data, int(bool(fwdBwd)), int(bool(avgToToeplitz)), d_rx, stream=stream)
     return d_rx
 
 
@@ -196,9 +187,8 @@ def hermitianEig(d_rx, stream=None):
     _lib.require_device()
     d_s, d_u, d_vh = empty((B, rows), np.float64), empty((B, rows, rows), np.complex128), empty((B, rows, rows), np.complex128)
     d_status = empty((B,), np.int32)
-    _lib.check(_lib.load().caf_music_eig(_p(d_rx), B, rows, _p(d_s), _p(d_u), _p(d_vh), _p(d_status), stream), "caf_music_eig")
-    _lib.check(_lib.load().caf_stream_sync(stream), "sync")  # (d_status is read on the null stream)
-    return d_s, d_u, d_vh, _check_status(d_status.get())
+    _lib.call("caf_music_eig", d_rx, B, rows, d_s, d_u, d_vh, d_status, stream=stream)
+    return d_s, d_u, d_vh, _check_status(_lib.download(d_status, stream, null_too=True))  # (it is read on the null stream)
 
 
 def pseudoSpectrum(d_u, d_s, freqlist, plist, mode=MODE_NOISE, parts=False, stream=None):
@@ -215,14 +205,14 @@ def pseudoSpectrum(d_u, d_s, freqlist, plist, mode=MODE_NOISE, parts=False, stre
         raise ValueError("mode must be 0, 1 or 2.")
     pl = np.zeros(1, np.int32) if mode == MODE_CAPON else _check_plist(plist, rows)[0]
     _lib.require_device()
-    d_freqs = asarray(freqlist)
     shape = (B, pl.size, freqlist.size)
-    d_f = empty(shape, np.float64)
-    d_denom = empty(shape, np.float64) if parts else None
-    d_num = empty(shape, np.float64) if parts else None
-    _lib.check(_lib.load().caf_music_spectrum(_p(d_u), _p(d_s), B, rows, _p(d_freqs), freqlist.size, pl.ctypes.data, pl.size, int(mode),
-                                              _p(d_f), _p(d_denom), _p(d_num), stream), "caf_music_spectrum")
-    _lib.check(_lib.load().caf_stream_sync(stream), "sync")  # (d_freqs may be freed on return)
+    with _lib.held(stream, _lib.ALWAYS) as h:
+        d_freqs = h.put(freqlist)
+        d_f = empty(shape, np.float64)
+        d_denom = empty(shape, np.float64) if parts else None
+        d_num = empty(shape, np.float64) if parts else None
+        _lib.call("caf_music_spectrum", d_u, d_s, B, rows, d_freqs, freqlist.size, pl.ctypes.data, pl.size, int(mode), d_f, d_denom,
+                  d_num, stream=stream)
     return (d_f, d_denom, d_num) if parts else d_f
 
 
@@ -240,11 +230,11 @@ def xcorrFront(d_rx, d_cutout, taps, shifts, stream=None):
     if shifts.min() < 0 or shifts.max() + n > d_rx.size:
         raise ValueError("A shift reaches outside rx.")
     _lib.require_device()
-    d_taps = asarray(taps)
-    d_out = empty((shifts.size, n), np.complex128)
-    _lib.check(_lib.load().caf_music_xcorr_front(_p(d_rx), d_rx.size, _p(d_cutout), n, _p(d_taps), taps.size, shifts.ctypes.data,
-                                                 shifts.size, _p(d_out), stream), "caf_music_xcorr_front")
-    _lib.check(_lib.load().caf_stream_sync(stream), "sync")  # (d_taps may be freed on return)
+    with _lib.held(stream, _lib.ALWAYS) as h:
+        d_taps = h.put(taps)
+        d_out = empty((shifts.size, n), np.complex128)
+        _lib.call("caf_music_xcorr_front", d_rx, d_rx.size, d_cutout, n, d_taps, taps.size, shifts.ctypes.data, shifts.size, d_out,
+                  stream=stream)
     return d_out
 
 

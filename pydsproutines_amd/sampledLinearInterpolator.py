@@ -12,7 +12,6 @@ upstream: the window is half-open; ``timevec`` must be uniform with step T and t
 then a DeviceArray.  Every argument is checked before the library is touched; without a device the propagate calls raise.
 PySampledLinearInterpolator_64f.lerp, a helper of a few NumPy lines, stays on the host."""
 
-import ctypes as ct
 from fractions import Fraction
 
 import numpy as np
@@ -163,9 +162,6 @@ class BurstTable:
                                          self.phase_off.ctypes.data, self.d_phase.ptr)
         return self
 
-    def byref(self):
-        return ct.byref(self.struct)
-
 
 def _outDtype(out_dtype):
     dt = np.dtype(out_dtype)
@@ -193,14 +189,11 @@ def _lerpPropagate(emitters, t, tau, phis, jumps, startIdx, out_dtype):
     start = startIdx if 0 <= startIdx < n else 0  # (upstream: a start index out of range is ignored)
     table = BurstTable(emitters, phis, jumps)
     _lib.require_device()
-    lib = _lib.load()
     table.upload()
-    d_t = t if isinstance(t, DeviceArray) else asarray(t)
-    d_tau = tau if isinstance(tau, DeviceArray) else asarray(tau)
-    out = empty((n,), dt)
-    _lib.check(lib.caf_lerp_propagate(table.byref(), ct.c_void_p(d_t.ptr), ct.c_void_p(d_tau.ptr), n, start,
-                                      int(dt == np.dtype(np.complex128)), ct.c_void_p(out.ptr), None), "caf_lerp_propagate")
-    _lib.check(lib.caf_stream_sync(None), "sync")
+    with _lib.held(None, _lib.ALWAYS) as h:
+        d_t, d_tau = h.put(t), h.put(tau)
+        out = empty((n,), dt)
+        _lib.call("caf_lerp_propagate", table.struct, d_t, d_tau, n, start, int(dt == np.dtype(np.complex128)), out, stream=None)
     return out if on_device else out.get()
 
 
@@ -235,9 +228,8 @@ class Scene:
         dtype = _outDtype(out_dtype)
         if out is None:
             out = empty((self.rows, int(N)), dtype)
-        _lib.check(_lib.load().caf_scene_propagate(self.tx.byref(), self.rx.byref(), self.bursts.byref(), float(t0), float(dt), int(N),
-                                                   int(dtype == np.dtype(np.complex128)), ct.c_void_p(out.ptr), None),
-                   "caf_scene_propagate")
+        _lib.call("caf_scene_propagate", self.tx.struct, self.rx.struct, self.bursts.struct, float(t0), float(dt), int(N),
+                  int(dtype == np.dtype(np.complex128)), out, stream=None)
         return out
 
 
@@ -250,5 +242,5 @@ def propagateAlongTrajectories(emitters, receivers, t0, dt, N, out_dtype=np.comp
     if not (np.isfinite(t0) and np.isfinite(dt) and dt > 0 and N >= 1):
         raise ValueError("t0 must be finite, dt positive and finite, N at least 1.")
     out = Scene(emitters, receivers).upload().run(t0, dt, N, dtype)  # (every check is in the constructor)
-    _lib.check(_lib.load().caf_stream_sync(None), "sync")
+    _lib.drain(None)
     return out

@@ -3,12 +3,10 @@ return values as the reference's signalCreationRoutines.py (makeFreq :380-386, r
 symsFromBits :24-43, randPSKsyms :47-69, randnoise :72-104, addSigToNoise :107-145, makeCPFSKsyms :220-251,
 makePulsedCPFSKsyms :254-293), and the propagation and tone routines, which run on the device (further down)."""
 
-import ctypes as ct
-
 import numpy as np
 
 from . import _lib
-from .devarray import DeviceArray, asarray, empty, requireDeviceArray
+from .devarray import DeviceArray, empty, requireDeviceArray
 
 
 def makeFreq(length, fs):
@@ -119,10 +117,6 @@ def makePulsedCPFSKsyms(bits, baud, g=np.ones(8) / 16, m=2, h=0.5, up=8, phase=0
 PROPAGATE_EXACT_MAX_LEN = 1 << 20  # caf_propagate_exact: N^2 terms per row
 
 
-def _p(a):
-    return ct.c_void_p(a.ptr) if a is not None else None
-
-
 def _signal_rows(sig, what):
     """(DeviceArray or None, complex64 host matrix or None, rows, N) of a 1-D or 2-D signal."""
     if isinstance(sig, DeviceArray):
@@ -180,22 +174,20 @@ def propagateSignal(sig, time, fs, freq=None, tone=None):
         if not np.isfinite(freq):
             raise ValueError("propagateSignal: freq must be finite.")
     _lib.require_device()
-    lib = _lib.load()
     if tone is None and freq is not None:
         if on_device:
             tone = empty((n,), np.complex64)
-            _lib.check(lib.caf_gen_tones(freq / fs, 0.0, 1, n, 0, _p(tone), None), "caf_gen_tones")
+            _lib.call("caf_gen_tones", freq / fs, 0.0, 1, n, 0, tone, stream=None)
             d_tone = tone
         else:
             tone = np.exp(1j * 2 * np.pi * freq * np.arange(n) / fs)
-    if tone is not None and d_tone is None:
-        d_tone = asarray(np.ascontiguousarray(tone, dtype=np.complex64).reshape(-1))
-    if d_sig is None:
-        d_sig = asarray(h_sig)
-    d_time = asarray(t)
-    out = empty((t.size, n), np.complex64)
-    _lib.check(lib.caf_propagate(_p(d_sig), rows, n, _p(d_time), t.size, fs, _p(d_tone), _p(out), None), "caf_propagate")
-    _lib.check(lib.caf_stream_sync(None), "sync")  # (the uploads above may be freed on return)
+    with _lib.held(None, _lib.ALWAYS) as h:
+        if tone is not None and d_tone is None:
+            d_tone = h.put(np.ascontiguousarray(tone, dtype=np.complex64).reshape(-1))
+        d_sig = h.put(h_sig if d_sig is None else d_sig)
+        d_time = h.put(t)
+        out = empty((t.size, n), np.complex64)
+        _lib.call("caf_propagate", d_sig, rows, n, d_time, t.size, fs, d_tone, out, stream=None)
     result = out if on_device else out.get()
     return result if tone is None else (result, tone)
 
@@ -226,23 +218,17 @@ def propagateSignalExact(sig, tau, fs, f_c=0.0):
     if not (np.isfinite(fs) and fs > 0 and np.isfinite(f_c)):
         raise ValueError("propagateSignalExact: fs must be positive, fs and f_c finite.")
     _lib.require_device()
-    lib = _lib.load()
-    if d_sig is None:
-        d_sig = asarray(h_sig)
-    if d_tau is None:
-        d_tau = asarray(tau)
-    out = empty(shape, np.complex64)
-    _lib.check(lib.caf_propagate_exact(_p(d_sig), _p(d_tau), 1 if len(shape) == 1 else shape[0], n, fs, f_c, _p(out), None),
-               "caf_propagate_exact")
-    _lib.check(lib.caf_stream_sync(None), "sync")
+    with _lib.held(None, _lib.ALWAYS) as h:
+        d_sig = h.put(h_sig if d_sig is None else d_sig)
+        d_tau = h.put(tau if d_tau is None else d_tau)
+        out = empty(shape, np.complex64)
+        _lib.call("caf_propagate_exact", d_sig, d_tau, 1 if len(shape) == 1 else shape[0], n, fs, f_c, out, stream=None)
     return out if on_device else out.get()
 
 
 def propagate_geometry():
     """(samples at most, rotor re-seed interval, outputs per workgroup, waves per workgroup) of caf_propagate_exact."""
-    v = [ct.c_int32(0) for _ in range(4)]
-    _lib.check(_lib.load().caf_propagate_geometry(*[ct.byref(x) for x in v]), "caf_propagate_geometry")
-    return tuple(int(x.value) for x in v)
+    return _lib.query("caf_propagate_geometry")
 
 
 def timeSliceSignal(x, tstart, tstop, fs):
@@ -258,11 +244,10 @@ def freqshiftSignal(x, freq, fs=1.0):
     if not (np.isfinite(freq) and np.isfinite(fs) and fs != 0):
         raise ValueError("freqshiftSignal: freq must be finite, fs finite and not zero.")
     _lib.require_device()
-    if d_x is None:
-        d_x = asarray(h_x)
-    out = empty(x.shape if on_device else np.shape(x), np.complex64)
-    _lib.check(_lib.load().caf_freq_shift(_p(d_x), rows, n, freq / fs, _p(out), None), "caf_freq_shift")
-    _lib.check(_lib.load().caf_stream_sync(None), "sync")
+    with _lib.held(None, _lib.ALWAYS) as h:
+        d_x = h.put(h_x if d_x is None else d_x)
+        out = empty(x.shape if on_device else np.shape(x), np.complex64)
+        _lib.call("caf_freq_shift", d_x, rows, n, freq / fs, out, stream=None)
     return out if on_device else out.get()
 
 
@@ -272,8 +257,7 @@ def cupyAddTonePhase(phase, freq, tstart, tstep):
     if phase.dtype != np.dtype(np.float32):
         raise TypeError("Phase is expected to be 32-bit float.")
     _lib.require_device()
-    _lib.check(_lib.load().caf_add_tone_phase(_p(phase), phase.size, float(freq), float(tstart), float(tstep), None),
-               "caf_add_tone_phase")
+    _lib.call("caf_add_tone_phase", phase, phase.size, float(freq), float(tstart), float(tstep), stream=None)
 
 
 def _genTones(f0, fstep, numFreqs, length, dtype):
@@ -283,8 +267,8 @@ def _genTones(f0, fstep, numFreqs, length, dtype):
         raise ValueError("numFreqs and length must be at least 1.")
     _lib.require_device()
     out = empty((int(numFreqs), int(length)), dtype)
-    _lib.check(_lib.load().caf_gen_tones(float(f0), float(fstep), int(numFreqs), int(length),
-                                         int(np.dtype(dtype) == np.dtype(np.complex128)), _p(out), None), "caf_gen_tones")
+    _lib.call("caf_gen_tones", float(f0), float(fstep), int(numFreqs), int(length), int(np.dtype(dtype) == np.dtype(np.complex128)),
+              out, stream=None)
     return out
 
 

@@ -9,8 +9,6 @@ arbitrary frequencies (:637-659) and IntegerMultipleFFT (:128-232), all through 
 ``czt_scipy`` and the plots.
 """
 
-import ctypes as ct
-
 import numpy as np
 
 from . import _lib
@@ -71,12 +69,7 @@ class _CZTBase:
     def _run_dev(self, d_x, rows, out=None):
         if out is None:
             out = empty((rows, self.k), np.complex64)
-        _lib.check(
-            _lib.load().caf_czt_run_many(ct.c_void_p(d_x.ptr), rows, self.m, self.k, self.nfft, ct.c_void_p(self.d_aa.ptr),
-                                         ct.c_void_p(self.d_fv.ptr), ct.c_void_p(self._d_wws.ptr), ct.c_void_p(out.ptr),
-                                         None),
-            "caf_czt_run_many",
-        )
+        _lib.call("caf_czt_run_many", d_x, rows, self.m, self.k, self.nfft, self.d_aa, self.d_fv, self._d_wws, out, stream=None)
         return out
 
 
@@ -165,24 +158,11 @@ def cupyDotTonesScaling(f0, fstep, numFreqs, src):
     length = src.size
     nblocks = (length + 63) // 64
     out = empty((nblocks, int(numFreqs)), np.complex64)
-    _lib.check(_lib.load().caf_dot_tones(ct.c_void_p(src.ptr), length, float(f0), float(fstep), int(numFreqs),
-                                         ct.c_void_p(out.ptr), None), "caf_dot_tones")
+    _lib.call("caf_dot_tones", src, length, float(f0), float(fstep), int(numFreqs), out, stream=None)
     return out
 
 
 # ---- tone spectra (ref: spectralRoutines.py:394-571, 663-679; csrc/caf_spectral.hip: k_tone_spectrum) ------------------------
-
-def _p(a):
-    return ct.c_void_p(a.ptr)
-
-
-def _download(out, stream):
-    """the host copy of a result queued on ``stream``: the stream is drained first (the download runs on the null stream, which a
-    caller's stream is not ordered with), while the caller still holds the uploaded input"""
-    if stream is not None:
-        _lib.check(_lib.load().caf_stream_sync(stream), "caf_stream_sync")
-    return out.get()
-
 
 def _f64_vector(name, a):
     requireDeviceArray(a)
@@ -203,8 +183,8 @@ def toneSpectrum_gpu(f0, d_freqs, fs, N, phi=0.0, A=1.0, stream=None):
     _f64_vector("d_freqs", d_freqs)
     out = empty(d_freqs.shape, np.complex128)
     if out.size:
-        _lib.check(_lib.load().caf_tone_spectrum_one(float(f0), float(phi), float(A), _p(d_freqs), d_freqs.size, float(fs), int(N),
-                                                     _p(out), stream), "caf_tone_spectrum_one")
+        _lib.call("caf_tone_spectrum_one", float(f0), float(phi), float(A), d_freqs, d_freqs.size, float(fs), int(N), out,
+                  stream=stream)
     return out
 
 
@@ -218,8 +198,8 @@ def toneSpectrumMulti_gpu(d_f0List, d_freqs, fs, N, d_phiList, d_AList, stream=N
             raise ValueError("d_f0List, d_phiList and d_AList must have one length")
     out = empty((d_f0List.size, d_freqs.size), np.complex128)
     if out.size:
-        _lib.check(_lib.load().caf_tone_spectrum(_p(d_f0List), _p(d_phiList), _p(d_AList), d_f0List.size, _p(d_freqs), d_freqs.size,
-                                                 float(fs), int(N), _p(out), stream), "caf_tone_spectrum")
+        _lib.call("caf_tone_spectrum", d_f0List, d_phiList, d_AList, d_f0List.size, d_freqs, d_freqs.size, float(fs), int(N), out,
+                  stream=stream)
     return out
 
 
@@ -241,10 +221,7 @@ def toneSpectrum(f0, freqs, fs, N, phi=0, A=1.0):
 def dft_geometry():
     """(T, C, R, max_len, W) of ``caf_dft_geometry``: frequencies per workgroup, samples per LDS chunk, the re-seed interval of the
     phase, the largest row length, and the workgroups per row that the cut of a long row aims for."""
-    t, c, r, w = ct.c_int32(), ct.c_int32(), ct.c_int32(), ct.c_int32()
-    mx = ct.c_int64()
-    _lib.check(_lib.load().caf_dft_geometry(ct.byref(t), ct.byref(c), ct.byref(r), ct.byref(mx), ct.byref(w)), "caf_dft_geometry")
-    return t.value, c.value, r.value, mx.value, w.value
+    return _lib.query("caf_dft_geometry")
 
 
 def dftRows(d_x, d_freqs, fs, stream=None):
@@ -262,8 +239,8 @@ def dftRows(d_x, d_freqs, fs, stream=None):
         return zeros(shape, np.complex128)
     out = empty(shape, np.complex128)
     if out.size:
-        _lib.check(_lib.load().caf_dft_rows(_p(d_x), int(d_x.dtype == np.complex128), rows, length, _p(d_freqs), d_freqs.size, float(fs),
-                                            _p(out), stream), "caf_dft_rows")
+        _lib.call("caf_dft_rows", d_x, int(d_x.dtype == np.complex128), rows, length, d_freqs, d_freqs.size, float(fs), out,
+                  stream=stream)
     return out
 
 
@@ -308,8 +285,7 @@ class IntegerMultipleFFT:
         shape = (rows, multiple * n) if reorder else (rows, multiple, n)
         out = empty(shape, np.complex64)
         if out.size:
-            _lib.check(_lib.load().caf_integer_multiple_fft(_p(d_x), rows, n, multiple, int(bool(reorder)), _p(out), stream),
-                       "caf_integer_multiple_fft")
+            _lib.call("caf_integer_multiple_fft", d_x, rows, n, multiple, int(bool(reorder)), out, stream=stream)
         return out
 
     def _check(self, x, ndim):
@@ -335,13 +311,13 @@ class IntegerMultipleFFT:
         d_x, dev = self._check(x, 1)
         out = self._run(d_x, 1, reorder, stream)
         out = out.reshape(out.shape[1:])
-        return out if dev else _download(out, stream)
+        return out if dev else _lib.download(out, stream)
 
     def fftMany(self, xmany, reorder: bool = False, stream=None):
         """``fft`` of every row of a (rows, N) array: (rows, multiple, N), or (rows, multiple N) with ``reorder``."""
         d_x, dev = self._check(xmany, 2)
         out = self._run(d_x, d_x.shape[0], reorder, stream)
-        return out if dev else _download(out, stream)
+        return out if dev else _lib.download(out, stream)
 
     def setMultiple(self, multiple: int):
         self._multiple = multiple

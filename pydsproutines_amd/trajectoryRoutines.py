@@ -12,7 +12,6 @@ or  c tau = |p_self(t) - p_other(t - tau)|  (``frm``: t is the receive time):
   * TauMethod.Position_Vector_Chasing_Iterator, or an interpolated side: tau <- |p_self(t) - p_other(t +- tau)| / c, 5 times from 0.
     The contraction factor is |v| / c; speeds of 1e-4 c or more are refused (5 steps then no longer reach float64)."""
 
-import ctypes as ct
 from enum import IntEnum
 
 import numpy as np
@@ -234,40 +233,30 @@ class TrajectoryTable:
         self.struct = _lib.CafTrajTable(n, 0, self.kind.ctypes.data, self.x0v.ctypes.data, self.off.ctypes.data,
                                         self.d_tp.ptr if tps else None, self.d_xp.ptr if xps else None)
 
-    def byref(self):
-        return ct.byref(self.struct)
-
 
 def deviceTau(me, others, t, direction, method):
     """(len(others), len(t)) float64 DeviceArray of light times (caf_traj_tau); direction 0 = to, 1 = frm."""
-    from .devarray import DeviceArray, asarray, empty
+    from .devarray import DeviceArray, empty
 
     if isinstance(t, DeviceArray):
         if t.dtype != np.dtype(np.float64) or t.ndim != 1:
             raise TypeError("A device t must be a 1-D float64 array.")
-        d_t = t
     else:
         t = _times(t)
-        d_t = None
-    if (d_t.size if d_t is not None else t.size) < 1:
+    if t.size < 1:
         raise ValueError("t must hold at least one time.")
     _lib.require_device()
-    lib = _lib.load()
-    if d_t is None:
-        d_t = asarray(np.ascontiguousarray(t))
-    a, b = TrajectoryTable([me]), TrajectoryTable(others)
-    out = empty((len(others), d_t.size), np.float64)
-    _lib.check(lib.caf_traj_tau(a.byref(), b.byref(), ct.c_void_p(d_t.ptr), d_t.size, direction, method, ct.c_void_p(out.ptr), None),
-               "caf_traj_tau")
-    _lib.check(lib.caf_stream_sync(None), "sync")
+    with _lib.held(None, _lib.ALWAYS) as h:
+        d_t = h.put(t)
+        a, b = TrajectoryTable([me]), TrajectoryTable(others)
+        out = empty((len(others), d_t.size), np.float64)
+        _lib.call("caf_traj_tau", a.struct, b.struct, d_t, d_t.size, direction, method, out, stream=None)
     return out
 
 
 def scene_geometry():
     """(emitters, receivers, bursts per emitter, knots at most; threads, outputs per workgroup) of csrc/caf_scene.hip."""
-    v = [ct.c_int32(0), ct.c_int32(0), ct.c_int32(0), ct.c_int64(0), ct.c_int32(0), ct.c_int32(0)]
-    _lib.check(_lib.load().caf_scene_geometry(*[ct.byref(x) for x in v]), "caf_scene_geometry")
-    return tuple(int(x.value) for x in v)
+    return _lib.query("caf_scene_geometry")
 
 
 # ---- sampled trajectories (host) -------------------------------------------------------------------------------------------

@@ -19,8 +19,7 @@ def iq16_to_complex64(d_iq16, scale=1.0):
         raise ValueError("interleaved IQ needs an even number of int16 values")
     n = d_iq16.size // 2
     out = empty(n, np.complex64)
-    _lib.check(_lib.load().caf_iq16_to_c64(ct.c_void_p(d_iq16.ptr), n, float(scale), ct.c_void_p(out.ptr), None),
-               "caf_iq16_to_c64")
+    _lib.call("caf_iq16_to_c64", d_iq16, n, float(scale), out, stream=None)
     return out
 
 
@@ -55,11 +54,9 @@ class Iq16FrontEnd:
         n = d_iq16.size // 2
         nout = max(0, (n - self.phase + self.dsr - 1) // self.dsr)
         out = empty(nout, np.complex64)
-        lib = _lib.load()
         dl = self.delay.size // 2 if self.delay is not None else 0
-        _lib.check(lib.caf_iq16_fir_decimate(ct.c_void_p(d_iq16.ptr), n, self.scale, ct.c_void_p(self.d_taps.ptr),
-                                             self.d_taps.size, ct.c_void_p(self.delay.ptr) if dl else None, dl, self.dsr,
-                                             self.phase, ct.c_void_p(out.ptr), nout, None), "caf_iq16_fir_decimate")
+        _lib.call("caf_iq16_fir_decimate", d_iq16, n, self.scale, self.d_taps, self.d_taps.size, self.delay if dl else None, dl,
+                  self.dsr, self.phase, out, nout, stream=None)
         # carry the last ntaps-1 input pairs (old history + this chunk) and the phase into the next call
         keep = self.d_taps.size - 1
         if keep > 0:
@@ -68,15 +65,13 @@ class Iq16FrontEnd:
             from_old = keep - from_x
             if from_old:
                 if dl >= from_old:
-                    _lib.check(lib.caf_d2d(ct.c_void_p(nd.ptr), ct.c_void_p(self.delay.ptr + 4 * (dl - from_old)),
-                                           4 * from_old, None))
+                    _lib.call("caf_d2d", nd, ct.c_void_p(self.delay.ptr + 4 * (dl - from_old)), 4 * from_old, stream=None)
                 else:  # not enough history yet: zeros in front
-                    _lib.check(lib.caf_memset(ct.c_void_p(nd.ptr), 0, 4 * (from_old - dl), None))
+                    _lib.call("caf_memset", nd, 0, 4 * (from_old - dl), stream=None)
                     if dl:
-                        _lib.check(lib.caf_d2d(ct.c_void_p(nd.ptr + 4 * (from_old - dl)), ct.c_void_p(self.delay.ptr),
-                                               4 * dl, None))
-            _lib.check(lib.caf_d2d(ct.c_void_p(nd.ptr + 4 * from_old), ct.c_void_p(d_iq16.ptr + 4 * (n - from_x)),
-                                   4 * from_x, None))
+                        _lib.call("caf_d2d", ct.c_void_p(nd.ptr + 4 * (from_old - dl)), self.delay, 4 * dl, stream=None)
+            _lib.call("caf_d2d", ct.c_void_p(nd.ptr + 4 * from_old), ct.c_void_p(d_iq16.ptr + 4 * (n - from_x)), 4 * from_x,
+                      stream=None)
             self.delay = nd
         # next kept sample index relative to the next chunk's start
         self.phase = self.phase + nout * self.dsr - n

@@ -13,8 +13,6 @@ Not provided: the reference's prints and its step methods (``calcAllBranchMetric
 kernel carries survivor tails instead of re-synthesising every guess, so those intermediate matrices never exist.
 There is no host fallback: without a device ``run`` raises."""
 
-import ctypes as ct
-
 import numpy as np
 
 from . import _lib
@@ -25,21 +23,9 @@ __all__ = ["ViterbiDemodulator", "BurstyViterbiDemodulator", "viterbi_geometry"]
 _NEVER = 255  # a slot no step has written (the reference leaves 0 there)
 
 
-def _p(a):
-    return ct.c_void_p(a.ptr) if a is not None else None
-
-
-def _st(stream):
-    if stream is None or isinstance(stream, ct.c_void_p):
-        return stream
-    return ct.c_void_p(int(stream))
-
-
 def viterbi_geometry():
     """(states at most, pulse samples at most, steps per traceback chunk) of the kernel."""
-    v = [ct.c_int32(0) for _ in range(3)]
-    _lib.check(_lib.load().caf_viterbi_geometry(*[ct.byref(x) for x in v]), "caf_viterbi_geometry")
-    return tuple(int(x.value) for x in v)
+    return _lib.query("caf_viterbi_geometry")
 
 
 class ViterbiDemodulator:
@@ -98,12 +84,12 @@ class ViterbiDemodulator:
 
     def _get_table(self, pathlen, stream):
         if self._table is None or self._table.shape[0] < pathlen:
-            d_pulses = asarray(np.ascontiguousarray(self.pulses, dtype=np.complex128))
-            d_omegas = asarray(np.ascontiguousarray(self.omegas, dtype=np.float64))
-            table = empty((pathlen, self.pulselen), np.complex128)
-            _lib.check(_lib.load().caf_viterbi_table(_p(d_pulses), _p(d_omegas), self.L, self.pulselen, int(self.up), int(pathlen),
-                                                     _p(table), _st(stream)), "caf_viterbi_table")
-            _lib.check(_lib.load().caf_stream_sync(_st(stream)), "sync")  # (the uploads above may be freed on return)
+            with _lib.held(stream, _lib.ALWAYS) as h:
+                d_pulses = h.put(self.pulses, np.complex128)
+                d_omegas = h.put(self.omegas, np.float64)
+                table = empty((pathlen, self.pulselen), np.complex128)
+                _lib.call("caf_viterbi_table", d_pulses, d_omegas, self.L, self.pulselen, int(self.up), int(pathlen), table,
+                          stream=stream)
             self._table = table
         return self._table
 
@@ -138,7 +124,7 @@ class ViterbiDemodulator:
             h_allowed=allowed.ctypes.data if allowed.size else None, num_allowed=allowed.size, d_table=table.ptr, d_y=Y.ptr,
             rows=B, ylength=Y.shape[1], d_states=d_states.ptr if states else None, d_metrics=d_metrics.ptr, d_best=d_best.ptr,
             d_best_path=d_best_path.ptr)
-        _lib.check(_lib.load().caf_viterbi_demod(ct.byref(desc), _st(stream)), "caf_viterbi_demod")
+        _lib.call("caf_viterbi_demod", desc, stream=stream)
         return d_best_path, d_metrics, d_states, d_best
 
     def run(self, y, pathlen):

@@ -84,7 +84,7 @@ def _host_take(d_row, rel, dtype):
         lo = int(rel[0])
         if d_row.dtype == np.float32 and np.dtype(dtype) == np.float64:
             out = np.empty(n, np.float64)
-            _lib.check(_lib.load().caf_d2h_f64(out.ctypes.data, ct.c_void_p(d_row.ptr + 4 * lo), n, None), "caf_d2h_f64")
+            _lib.call("caf_d2h_f64", out.ctypes.data, ct.c_void_p(d_row.ptr + 4 * lo), n, stream=None)
             return out
         return d_row[lo : lo + n].get().astype(dtype, copy=False)
     return d_row.get()[rel].astype(dtype, copy=False)
@@ -93,17 +93,12 @@ def _host_take(d_row, rel, dtype):
 def _perdelay(d_cut, n, d_rx, rx_len, start, step, num, zero_oor, want_qf2, want_idx, want_caf, want_ccaf,
               device_out=False):
     """One caf_xcorr_perdelay call; returns host arrays (DeviceArrays with ``device_out``)."""
-    lib = _lib.load()
     qf2 = empty(num, np.float32) if want_qf2 else None
     idx = empty(num, np.int32) if want_idx else None
     caf = empty((num, n), np.float32) if want_caf else None
     ccaf = empty((num, n), np.complex64) if want_ccaf else None
-    p = lambda a: ct.c_void_p(a.ptr) if a is not None else None  # noqa: E731
-    _lib.check(
-        lib.caf_xcorr_perdelay(p(d_cut), n, p(d_rx), rx_len, int(start), int(step), int(num), 1 if zero_oor else 0,
-                               p(qf2), p(idx), p(caf), p(ccaf), 0, None),
-        "caf_xcorr_perdelay",
-    )
+    _lib.call("caf_xcorr_perdelay", d_cut, n, d_rx, rx_len, int(start), int(step), int(num), 1 if zero_oor else 0, qf2, idx, caf,
+              ccaf, 0, stream=None)
     if device_out:
         return qf2, idx, caf, ccaf
     g = lambda a: a.get() if a is not None else None  # noqa: E731
@@ -129,8 +124,7 @@ def _take_f64(d_f32, rel, out=None):
     rel = np.asarray(rel)
     out = empty(rel.size, np.float64) if out is None else out
     d_idx = _dev_index(rel, d_f32.size)
-    _lib.check(_lib.load().caf_gather_f32_f64(ct.c_void_p(d_f32.ptr), d_f32.size, ct.c_void_p(d_idx.ptr) if d_idx is not None
-                                              else None, rel.size, ct.c_void_p(out.ptr), None), "caf_gather_f32_f64")
+    _lib.call("caf_gather_f32_f64", d_f32, d_f32.size, d_idx, rel.size, out, stream=None)
     return out
 
 
@@ -139,12 +133,10 @@ def _take_u32(d_i32, rel, out=None):
     rel = np.asarray(rel)
     out = empty(rel.size, np.uint32) if out is None else out
     d_idx = _dev_index(rel, d_i32.size)
-    lib = _lib.load()
     if d_idx is None:
-        _lib.check(lib.caf_d2d(ct.c_void_p(out.ptr), ct.c_void_p(d_i32.ptr), 4 * rel.size, None), "caf_d2d")
+        _lib.call("caf_d2d", out, d_i32, 4 * rel.size, stream=None)
     else:
-        _lib.check(lib.caf_gather_b32(ct.c_void_p(d_i32.ptr), d_i32.size, ct.c_void_p(d_idx.ptr), rel.size,
-                                      ct.c_void_p(out.ptr), None), "caf_gather_b32")
+        _lib.call("caf_gather_b32", d_i32, d_i32.size, d_idx, rel.size, out, stream=None)
     return out
 
 
@@ -159,7 +151,6 @@ def _host_surface(plan, d_rx, lo, cnt, rel, dtype):
     delay-major launch (tests/test_gpu_fullsize.py::test_c2_hypothesis_major_surface)."""
     rel = np.asarray(rel)
     F = plan.F
-    lib = _lib.load()
     # (CAF_HOST_SURFACE_DELAY_MAJOR=1: the delay-major launch + plain download + NumPy selection / widening of rounds 1-4 --
     #  an A/B switch for scripts/time_host_surface.py)
     if plan.T == 1 and F > 1 and plan.engine_used == "persistent" and plan.block == 16384 \
@@ -169,8 +160,8 @@ def _host_surface(plan, d_rx, lo, cnt, rel, dtype):
         c0, nc = (int(rel[0]), int(rel.size)) if contiguous else (0, cnt)
         out = np.empty((nc, F), dtype)
         if nc:
-            _lib.check(lib.caf_d2h_transposed(out.ctypes.data, 1 if out.dtype == np.float64 else 0, ct.c_void_p(res.surface_t.ptr),
-                                              F, cnt, c0, nc, None), "caf_d2h_transposed")
+            _lib.call("caf_d2h_transposed", out.ctypes.data, 1 if out.dtype == np.float64 else 0, res.surface_t, F, cnt, c0, nc,
+                      stream=None)
         return out if contiguous else out[rel]
     # (the other engines: the delay-major surface is the reference's layout already; a contiguous run of delays is downloaded
     #  straight into the result -- widened to float64 by the transfer lanes, caf_d2h_f64 -- instead of download + selection +
@@ -182,9 +173,9 @@ def _host_surface(plan, d_rx, lo, cnt, rel, dtype):
         out = np.empty((int(rel.size), F), dtype)
         src = ct.c_void_p(res.surface.ptr + int(rel[0]) * F * 4)
         if out.dtype == np.float64:
-            _lib.check(lib.caf_d2h_f64(out.ctypes.data, src, out.size, None), "caf_d2h_f64")
+            _lib.call("caf_d2h_f64", out.ctypes.data, src, out.size, stream=None)
         else:
-            _lib.check(lib.caf_d2h(out.ctypes.data, src, out.size * 4, None), "caf_d2h")
+            _lib.call("caf_d2h", out.ctypes.data, src, out.size * 4, stream=None)
         return out
     return res.surface.get()[0][rel].astype(dtype, copy=False)
 
@@ -245,7 +236,7 @@ def fastXcorr(cutout, rx, freqsearch=False, outputCAF=False, shifts=None, absRes
         res = plan.run(d_rx, shift_start=lo, num_shifts=cnt, rows="max" if absResult else False, peak=False, cqf=not absResult)
         if absResult:
             if rel is None:  # float32 on the device -> the float64 result, widened by the download (caf_d2h_f64)
-                _lib.check(_lib.load().caf_d2h_f64(out.ctypes.data, ct.c_void_p(res.row_max.ptr), ns, None), "caf_d2h_f64")
+                _lib.call("caf_d2h_f64", out.ctypes.data, res.row_max, ns, stream=None)
             else:
                 out[:] = _host_take(res.row_max[0], rel, np.float64)
         else:
@@ -398,7 +389,7 @@ def cztXcorr(cutout, rx, f_searchMin, f_searchMax, fs, cztStep=0.1, outputCAF=Fa
         d_spec = czt.runMany(d_pdts)  # (cnt, k) complex QF
         if outputCAF:
             out = empty((cnt, k), np.float32)
-            _lib.check(_lib.load().caf_complex_magnsq(ct.c_void_p(d_spec.ptr), d_spec.size, 0, ct.c_void_p(out.ptr), 0, None))
+            _lib.call("caf_complex_magnsq", d_spec, d_spec.size, 0, out, 0, stream=None)
             return out.get()[rel].astype(np.float64), f_search
         spec = d_spec.get()[rel]
         mi = np.argmax(np.abs(spec), axis=1)
@@ -498,7 +489,6 @@ class _GroupEngine:
     def _run_rows(self, d_rx, shifts):
         f1, f2, bw, fs = self._czt_grid
         G, L, S = int(self._len.size), int(self._len[0]), int(shifts.size)
-        lib = _lib.load()
         st = getattr(self, "_rows_state", None)
         if st is None:
             tm = np.stack([self._comp[r : r + L] for r in self._rel])
@@ -524,17 +514,15 @@ class _GroupEngine:
             d_len = asarray(np.full(G * Sc, L, np.int32))
             d_row = asarray(np.repeat(np.arange(G, dtype=np.int32), Sc))
             d_mul = empty((G * Sc, L), np.complex64)
-            _lib.check(lib.caf_multiply_slices_indexed_rows(ct.c_void_p(d_rx.ptr), d_rx.size, ct.c_void_p(st["d_tm"].ptr), G, L,
-                                                            ct.c_void_p(d_starts.ptr), ct.c_void_p(d_len.ptr), ct.c_void_p(d_row.ptr),
-                                                            L, G * Sc, ct.c_void_p(d_mul.ptr), None), "caf_multiply_slices_indexed_rows")
+            _lib.call("caf_multiply_slices_indexed_rows", d_rx, d_rx.size, st["d_tm"], G, L, d_starts, d_len,
+                      d_row, L, G * Sc, d_mul, stream=None)
             d_planes = czt.runMany(d_mul)  # (G Sc, k) complex64
             d_e = empty((G * Sc,), np.float32)
             d_ei = asarray((starts + L - 1).astype(np.int32))
-            _lib.check(lib.caf_gather_b32(ct.c_void_p(d_msum.ptr), d_msum.size, ct.c_void_p(d_ei.ptr), G * Sc, ct.c_void_p(d_e.ptr), None),
-                       "caf_gather_b32")
+            _lib.call("caf_gather_b32", d_msum, d_msum.size, d_ei, G * Sc, d_e, stream=None)
             d_norm = asarray(d_e.get().astype(np.float64).reshape(G, Sc).sum(axis=0))
-            _lib.check(lib.caf_sum_groups_qf2(ct.c_void_p(d_planes.ptr), G, Sc, k, ct.c_void_p(st["d_ph"].ptr), ct.c_void_p(d_norm.ptr),
-                                              st["ynormsq"], ct.c_void_p(d_out[s0 : s0 + Sc].ptr), None), "caf_sum_groups_qf2")
+            _lib.call("caf_sum_groups_qf2", d_planes, G, Sc, k, st["d_ph"], d_norm, st["ynormsq"],
+                      d_out[s0 : s0 + Sc], stream=None)
         return _RowsResult(d_out), np.arange(S)
 
 
@@ -743,8 +731,7 @@ class TemplateCrossCorrelator:
             res = self._plan_max.run(x, surface=False, rows="max", peak=False)
             qf = empty(S, np.float32)
             ti = empty(S, np.int64)
-            _lib.check(_lib.load().caf_colmax_sqrt(ct.c_void_p(res.row_max.ptr), T, S, ct.c_void_p(qf.ptr),
-                                                   ct.c_void_p(ti.ptr), None))
+            _lib.call("caf_colmax_sqrt", res.row_max, T, S, qf, ti, stream=None)
             return qf, ti
         if self._plan is None:
             # templates of up to 8192 samples: the one-launch in-LDS engine writes the complex rows itself (one transform
@@ -756,8 +743,7 @@ class TemplateCrossCorrelator:
             return nout
         qf = empty(S, np.float32)
         ti = empty(S, np.int64)  # cp.argmax's dtype, written by the kernel
-        _lib.check(_lib.load().caf_colmax_abs(ct.c_void_p(nout.ptr), T, S, ct.c_void_p(qf.ptr), ct.c_void_p(ti.ptr), 1,
-                                              None))
+        _lib.call("caf_colmax_abs", nout, T, S, qf, ti, 1, stream=None)
         return qf, ti
 
 
@@ -824,16 +810,14 @@ def cp_fastXcorr_v2(cutout, rx, startIdx=0, idxlen=None, THREADS_PER_BLOCK=32, n
         d_qf2 = empty(idxlen, np.float32)
     else:
         d_out = empty((idxlen, ncols), np.float32)
-    lib = _lib.load()
     n = int(cutout.size)
     if (flattenCAF and cztObj is None and _one_kernel_cutout(n) and startIdx >= 0
             and startIdx + idxlen - 1 + n <= rx.size):
         # power-of-two cutout, 100 / 1000 / 10000 samples (radix-10 passes) or any other 2^a 3^b 5^c 7^d length up to 16200
         # (mixed-radix passes), every window inside rx: the whole chain (product, row transform, |.|^2, argmax, both norms)
         # is ONE kernel (caf_perdelay.hip, caf_perdelay_mr.hip) -- no (idxlen, N) matrix, no batches
-        _lib.check(lib.caf_xcorr_perdelay(ct.c_void_p(cutout.ptr), n, ct.c_void_p(rx.ptr), rx.size, int(startIdx), 1,
-                                          int(idxlen), 0, ct.c_void_p(d_qf2.ptr), ct.c_void_p(d_freqIdx.ptr), None, None,
-                                          0, None), "caf_xcorr_perdelay")
+        _lib.call("caf_xcorr_perdelay", cutout, n, rx, rx.size, int(startIdx), 1, int(idxlen), 0, d_qf2, d_freqIdx, None, None, 0,
+                  stream=None)
         return d_freqIdx, d_qf2
     fi = 0
     while fi < idxlen:
@@ -844,8 +828,7 @@ def cp_fastXcorr_v2(cutout, rx, startIdx=0, idxlen=None, THREADS_PER_BLOCK=32, n
             cupyArgmaxAbsRows_complex64(d_spec, d_argmax=d_freqIdx[fi : fi + nb], d_max=d_qf2[fi : fi + nb],
                                         returnMaxValues=True, useNormSqInstead=True)
         else:
-            _lib.check(lib.caf_complex_magnsq(ct.c_void_p(d_spec.ptr), d_spec.size, 0, ct.c_void_p(d_out[fi : fi + nb].ptr),
-                                              0, None))
+            _lib.call("caf_complex_magnsq", d_spec, d_spec.size, 0, d_out[fi : fi + nb], 0, stream=None)
         fi += nb  # (no synchronisation per batch: the scratch of a batch is recycled in stream order)
     if flattenCAF:
         return d_freqIdx, d_qf2
@@ -1001,13 +984,9 @@ def makeTimeScanSteervec(td_scan_range, fs, siglen):
     return np.exp(1j * 2 * np.pi * sigFreq * np.asarray(td_scan_range).reshape((-1, 1)))
 
 
-def _p(a):
-    return ct.c_void_p(a.ptr)
-
-
 def _mul_conj(d_a, d_b):
     out = empty(d_a.shape, np.complex64)
-    _lib.check(_lib.load().caf_mul_conj(_p(d_a), _p(d_b), d_a.size, _p(out), None), "caf_mul_conj")
+    _lib.call("caf_mul_conj", d_a, d_b, d_a.size, out, stream=None)
     return out
 
 
@@ -1015,7 +994,7 @@ def _steer_dot(d_vec, d_steer, scale=1.0):
     """scale * sum_k vec[k] * conj(steer[r, k]) for every row r, float64 accumulation; complex128 host result."""
     rows, n = d_steer.shape
     out = empty((rows,), np.complex128)
-    _lib.check(_lib.load().caf_steer_dot(_p(d_vec), _p(d_steer), rows, n, float(scale), _p(out), None), "caf_steer_dot")
+    _lib.call("caf_steer_dot", d_vec, d_steer, rows, n, float(scale), out, stream=None)
     return out.get()
 
 
@@ -1157,14 +1136,12 @@ class GroupXcorrCZT_Permutations:
         # E[d] = msum[d + L - 1]); the (G, S) energies of the wanted shifts are gathered there too -- only the
         # per-group start indices (S int32 each) are uploaded, nothing of rx's length comes back
         d_msum = cupyMovingAverage(cupyComplexMagnSq(d_rx, np.float32), L, sumInstead=True)
-        lib = _lib.load()
         self.d_rxgroupNormSq = empty((G, S), np.float32)
         d_starts = []
         for g in range(G):
             d_starts.append(asarray((shifts + int(self.groupStarts[g])).astype(np.int32)))
             d_e = asarray((shifts + int(self.groupStarts[g]) + L - 1).astype(np.int32))
-            _lib.check(lib.caf_gather_b32(ct.c_void_p(d_msum.ptr), d_msum.size, ct.c_void_p(d_e.ptr), S,
-                                          ct.c_void_p(self.d_rxgroupNormSq[g].ptr), None), "caf_gather_b32")
+            _lib.call("caf_gather_b32", d_msum, d_msum.size, d_e, S, self.d_rxgroupNormSq[g], stream=None)
         self._rxgroupNormSq_host = None  # (G, S) float64 host copy, read back on first use
         self.d_xcTemplates = empty((T, S, k), np.complex64)
         d_len = asarray(np.full(S, L, np.int32))
@@ -1174,11 +1151,8 @@ class GroupXcorrCZT_Permutations:
             g = int(self.ygroupIdxs[t])
             # multiplySlicesOptimistically (cupyExtensions.py:405-488) without its per-call host check of the slice
             # lengths: they are all L by construction
-            _lib.check(lib.caf_multiply_slices_indexed_rows(ct.c_void_p(d_rx.ptr), d_rx.size,
-                                                            ct.c_void_p(self._d_ygroups[t].ptr), 1, L,
-                                                            ct.c_void_p(d_starts[g].ptr), ct.c_void_p(d_len.ptr),
-                                                            ct.c_void_p(d_row0.ptr), L, S, ct.c_void_p(d_mul.ptr), None),
-                       "caf_multiply_slices_indexed_rows")
+            _lib.call("caf_multiply_slices_indexed_rows", d_rx, d_rx.size, self._d_ygroups[t], 1, L, d_starts[g], d_len, d_row0, L,
+                      S, d_mul, stream=None)
             czts[g].runMany(d_mul, out=self.d_xcTemplates[t])
         self._shape = (S, k)
         return cztFreq
@@ -1225,12 +1199,8 @@ class GroupXcorrCZT_Permutations:
         S, k = self._shape
         out = empty((S, k), np.float64)
         d_norm = asarray(np.ascontiguousarray(rxnormsq, dtype=np.float64))
-        _lib.check(
-            _lib.load().caf_sum_planes_qf2(ct.c_void_p(self.d_xcTemplates.ptr), self.numTemplates, S, k,
-                                           sel.ctypes.data_as(ct.c_void_p), sel.size, ct.c_void_p(d_norm.ptr), ynormsq,
-                                           ct.c_void_p(out.ptr), None),
-            "caf_sum_planes_qf2",
-        )
+        _lib.call("caf_sum_planes_qf2", self.d_xcTemplates, self.numTemplates, S, k, sel.ctypes.data_as(ct.c_void_p), sel.size,
+                  d_norm, ynormsq, out, stream=None)
         return out
 
     def getCAF(self, templateIdx, numThreads=4):

@@ -12,8 +12,6 @@ benchmarks/benchmark_groupXcorrs.py:37-72) -- with ONE libcaf call, ``caf_zoom_c
 This module is a thin caller: it allocates the k-row result table, makes the call and reads the table back.
 """
 
-import ctypes as ct
-
 import numpy as np
 
 from . import _lib
@@ -22,9 +20,7 @@ from .devarray import DeviceArray, asarray, empty, requireDeviceArray
 
 def zoom_num_bins(span, step):
     """Number of fine-grid bins of a zoom over -span ... +span in steps of ``step`` (any common unit)."""
-    nb = ct.c_int32()
-    _lib.check(_lib.load().caf_zoom_num_bins(float(span), float(step), ct.byref(nb)), "caf_zoom_num_bins")
-    return nb.value
+    return _lib.query("caf_zoom_num_bins", float(span), float(step))[0]
 
 
 def zoom_czt(plan, d_rx, plan_result, k=8, min_height=0.0, span=None, step=None, template=0, shift_start=0,
@@ -47,13 +43,8 @@ def zoom_czt(plan, d_rx, plan_result, k=8, min_height=0.0, span=None, step=None,
     ff = empty(k, np.float64)
     pl = empty((k, nb), np.float32) if planes else None
     o = _lib.CafZoomOutputs(cnt.ptr, dly.ptr, cidx.ptr, cq.ptr, fidx.ptr, ff.ptr, fq.ptr, pl.ptr if planes else None)
-    _lib.check(
-        _lib.load().caf_zoom_czt(plan._h, int(template), ct.c_void_p(d_rx.ptr), d_rx.size,
-                                 ct.c_void_p(plan_result.row_max.ptr + 4 * S * template),
-                                 ct.c_void_p(plan_result.row_arg.ptr + 4 * S * template), int(shift_start), S, k,
-                                 float(min_height), float(span), float(step), ct.byref(o), None),
-        "caf_zoom_czt",
-    )
+    _lib.call("caf_zoom_czt", plan._h, int(template), d_rx, d_rx.size, plan_result.row_max[template], plan_result.row_arg[template],
+              int(shift_start), S, k, float(min_height), float(span), float(step), o, stream=None)
     n = int(cnt.get()[0])
     if n < 0:
         raise ValueError("more than 2^20 local maxima above min_height=%g; raise min_height" % min_height)
@@ -103,8 +94,7 @@ def gather(d_x, d_idx, n=None):
         raise TypeError("Must be int32, found %s" % d_idx.dtype)
     n = d_idx.size if n is None else int(n)
     out = empty(max(n, 1), d_x.dtype)
-    _lib.check(_lib.load().caf_gather_b32(ct.c_void_p(d_x.ptr), d_x.size, ct.c_void_p(d_idx.ptr), n, ct.c_void_p(out.ptr),
-                                          None), "caf_gather_b32")
+    _lib.call("caf_gather_b32", d_x, d_x.size, d_idx, n, out, stream=None)
     return out.get()[:n]
 
 
@@ -140,18 +130,16 @@ def czt_zoom(cutout, d_rx, delays, coarse_freqs, fs, span, step):
     if npk == 0:
         return np.zeros(0, np.float64), np.zeros(0, np.float32), []
     d_cc = asarray(cutout.conj())
-    lib = _lib.load()
     rows = empty((npk, n), np.complex64)
     for i, d in enumerate(delays):
         # (1, n): rx[d:d+n] * conj(cutout) / norms -- on the n-sample view, so that the energy pass covers n samples
         row = multiplySlidesNormalised(d_cc, d_rx[int(d) : int(d) + n], 0, 1)
-        _lib.check(lib.caf_d2d(ct.c_void_p(rows.ptr + 8 * n * i), ct.c_void_p(row.ptr), 8 * n, None), "caf_d2d")
+        _lib.call("caf_d2d", rows[i], row, 8 * n, stream=None)
     f0 = np.asarray(coarse_freqs, dtype=np.float64)
     cyc = np.outer(f0 / fs, np.arange(n, dtype=np.float64))
     rot = np.exp(2j * np.pi * (cyc - np.floor(cyc))).astype(np.complex64)  # rows * conj(rot)
     d_rot = asarray(rot)
-    _lib.check(lib.caf_mul_conj(ct.c_void_p(rows.ptr), ct.c_void_p(d_rot.ptr), npk * n, ct.c_void_p(rows.ptr), None),
-               "caf_mul_conj")
+    _lib.call("caf_mul_conj", rows, d_rot, npk * n, rows, stream=None)
     key = (n, float(span), float(step), float(fs))
     cz = _ZOOM_CZT.get(key)
     if cz is None:

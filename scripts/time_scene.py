@@ -18,6 +18,7 @@ import os
 
 os.environ["OMP_NUM_THREADS"] = "1"  # the baseline is a one-core figure
 
+import ctypes as ct  # noqa: E402
 import sys  # noqa: E402
 import time  # noqa: E402
 
@@ -104,7 +105,7 @@ def main():
             for dtype in (np.complex64, np.complex128):
                 size = np.dtype(dtype).itemsize
                 out = empty((n,), dtype)
-                call = lambda: _lib.check(lib.caf_lerp_propagate(scene.bursts.byref(), d_t.ptr, d_tau.ptr, n, 0, int(size == 16), out.ptr,  # noqa: E731
+                call = lambda: _lib.check(lib.caf_lerp_propagate(ct.byref(scene.bursts.struct), d_t.ptr, d_tau.ptr, n, 0, int(size == 16), out.ptr,  # noqa: E731
                                                                  None), "caf_lerp_propagate")
                 t = median_ms(call, reps, warm=1)
                 report("array N 2^%d E %2d %s" % (log2n, E, np.dtype(dtype).name), t, n, 1.0 * n * E, n * size, OPS_ARRAY)
@@ -119,7 +120,7 @@ def main():
         tp = -0.1 + np.linspace(0.0, n / FS, knots)
         xp = np.stack([7.0e3 * tp, 50.0 * np.sin(tp), np.zeros(knots)], axis=1)
         other = T.TrajectoryTable([T.InterpolatedTrajectory(xp, tp)])
-        call = lambda: _lib.check(lib.caf_traj_tau(me.byref(), other.byref(), d_t.ptr, n, 1, 0, out.ptr, None), "caf_traj_tau")  # noqa: E731
+        call = lambda: _lib.check(lib.caf_traj_tau(ct.byref(me.struct), ct.byref(other.struct), d_t.ptr, n, 1, 0, out.ptr, None), "caf_traj_tau")  # noqa: E731
         t = median_ms(call, reps, warm=1)
         print("caf_traj_tau N 2^%d, interpolated other of %7d knots: %9.3f ms (%.3f .. %.3f) = %6.2f G light times/s; HBM write bound "
               "%.3f ms" % (int(np.log2(n)), knots, t[0], t[1], t[2], n / t[0] / 1e6, n * 8 / HBM_WRITE * 1e3), flush=True)
