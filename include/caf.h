@@ -940,6 +940,55 @@ CAF_EXPORT int32_t caf_cm_lines(const float* d_x, int64_t rows, int64_t pitch, c
  * bytes of dynamic LDS of a workgroup.  Every output is optional (NULL).  No device work. */
 CAF_EXPORT int32_t caf_cm_geometry(int64_t nfft, int32_t* form, int32_t* threads, int32_t* rows_per_wg, int64_t* lds_bytes);
 
+/* ---- FAM spectral-correlation estimator (cyclostationaryRoutines.py: scfFAM, cycleLines, estimateBaudSCF; caf_scf.hip) ----
+ * Per row x of n complex64 samples, a window a(n), n < N' = num_channels, a hop of L = hop samples, P = num_hops hops and a
+ * smoothing g(r) >= 0, r < P (d_smooth == NULL: all ones), with signed channels k, l in [-N'/2, N'/2):
+ *   X(k, r)    = sum_{n < N'} a(n) x(rL + n) e^{-j 2 pi k (rL + n) / N'}        (absolute phase, formed from (k (rL + n)) mod N')
+ *   S(k, l, q) = sum_r g(r) X(k, r) conj(X(l, r)) e^{-j 2 pi q r / P}           (conjugate = 1 drops the conj)
+ *   psd(k)     = sum_r g(r) |X(k, r)|^2                                          (float64)
+ * M = P L / N' and q in [-M/2, M/2) is kept.  d = k - l, s = k + l, dmin = -(N' - 1) (conjugate form: d = k + l, s = k - l,
+ * dmin = -N'); the cell (k, l, q) lies at cycle frequency alpha = (d M + q) fs / (P L) and frequency f = s fs / (2 N'), in
+ * alpha-bin a = (d - dmin) M + (q + M/2) of A = (2 N' - 1) M.  A cell's value is |S|^2, or with coherence = 1
+ * |S|^2 / (psd(k) psd(l)) (0 where the denominator is 0), formed in float64 from the float32 transform and rounded once to float32.
+ *   d_scf        (rows, N', N', M) float32 at [k + N'/2][l + N'/2][q + M/2]
+ *   d_alpha_val  (rows, A) float32: per alpha-bin the largest value over the pairs of its d
+ *   d_alpha_arg  (rows, A) int32: the s of that pair, the smaller s of equal values
+ *   d_psd        (rows, N') float64 at [k + N'/2]
+ * Each output is optional (NULL); at least one is required.  Accepted: N' a power of two in 64 .. 1024, L a power of two in
+ * 1 .. N'/4, P a power of two in 64 .. 16384, M >= 2, n >= (P - 1) L + N' (samples beyond that are not read), rows >= 1,
+ * pitch >= n.  Everything else is CAF_ERR_INVALID before anything touches a device; there is no composed form.
+ * Every output is the same bits alone, in any batch, at any place in it and on every run.  A non-finite sample spoils its own
+ * row only (its values come out NaN or unspecified).  Pooled scratch of caf_scf_geometry's scratch_bytes_per_row per row, at
+ * most 256 MiB of demodulates at a time.  CAF_SCF_DEBUG=1 prints one line per call on stderr (`[caf scf] fam np=... out=...`).
+ * The stream is a field of the descriptor: all device work of the call is queued on desc->stream and nowhere else, as for every
+ * entry point that ends in `void* stream`; tests/test_gpu_scf.py holds it to that behind a stalled stream. */
+typedef struct caf_scf_desc {
+    const float* d_x;       /* (rows, pitch) complex64 */
+    int64_t rows, pitch, n; /* n <= pitch samples used per row */
+    int32_t num_channels;   /* N' */
+    int32_t hop;            /* L  */
+    int32_t num_hops;       /* P  */
+    int32_t conjugate;      /* 0 / 1 */
+    int32_t coherence;      /* 0 / 1 */
+    int32_t reserved;
+    const float* d_window;  /* (N') float32, device, required */
+    const float* d_smooth;  /* (P) float32, device, or NULL = ones */
+    void* stream;
+} caf_scf_desc;
+
+typedef struct caf_scf_outputs { /* each optional */
+    float* d_scf;                /* (rows, N', N', M)  [k + N'/2][l + N'/2][q + M/2] */
+    float* d_alpha_val;          /* (rows, A) */
+    int32_t* d_alpha_arg;        /* (rows, A), s of the winner */
+    double* d_psd;               /* (rows, N') */
+} caf_scf_outputs;
+
+CAF_EXPORT int32_t caf_scf_fam(const caf_scf_desc* desc, const caf_scf_outputs* out);
+/* m = M, num_alpha = A, min_samples = (P - 1) L + N', threads and bytes of dynamic LDS of a workgroup of the pair kernel, bytes
+ * of pooled scratch per row.  Every output is optional (NULL).  Sizes that caf_scf_fam refuses: CAF_ERR_INVALID.  No device work. */
+CAF_EXPORT int32_t caf_scf_geometry(int32_t num_channels, int32_t hop, int32_t num_hops, int32_t* m, int64_t* num_alpha,
+                                    int64_t* min_samples, int32_t* threads, int64_t* lds_bytes, int64_t* scratch_bytes_per_row);
+
 /* ---- batched k-means and cluster scores (clusterRoutines.py: ClusterEngine, ClusterEngine2D, AngularClusterEngine;
  *      caf_cluster.hip) ---------------------------------------------------------------------------------------------------
  * Everything is float64.  d_x: (P, pitch, D) row-major, P problems of up to `pitch` points in D dimensions.  d_lengths:

@@ -220,6 +220,33 @@ class CafBurstTable(ct.Structure):
     ]
 
 
+class CafScfDesc(ct.Structure):
+    _fields_ = [
+        ("d_x", ct.c_void_p),
+        ("rows", ct.c_int64),
+        ("pitch", ct.c_int64),
+        ("n", ct.c_int64),
+        ("num_channels", ct.c_int32),
+        ("hop", ct.c_int32),
+        ("num_hops", ct.c_int32),
+        ("conjugate", ct.c_int32),
+        ("coherence", ct.c_int32),
+        ("reserved", ct.c_int32),
+        ("d_window", ct.c_void_p),
+        ("d_smooth", ct.c_void_p),
+        ("stream", ct.c_void_p),
+    ]
+
+
+class CafScfOutputs(ct.Structure):
+    _fields_ = [
+        ("d_scf", ct.c_void_p),
+        ("d_alpha_val", ct.c_void_p),
+        ("d_alpha_arg", ct.c_void_p),
+        ("d_psd", ct.c_void_p),
+    ]
+
+
 CAF_TRAJ_STATIONARY = 0
 CAF_TRAJ_CONSTANT_VELOCITY = 1
 CAF_TRAJ_INTERPOLATED = 2
@@ -369,6 +396,9 @@ _SIGNATURES = {
     "caf_mp_profile": [_P, _I64, _I32, _I32, _I32, _P, _P, _P],
     "caf_cm_geometry": [_I64] + [ct.POINTER(_I32)] * 3 + [ct.POINTER(_I64)],
     "caf_cm_lines": [_P, _I64, _I64, _P, _I64, ct.POINTER(_I32), _I32, ct.POINTER(_I32), ct.POINTER(_I32), _P, _P, _P, _P, _P],
+    "caf_scf_fam": [ct.POINTER(CafScfDesc), ct.POINTER(CafScfOutputs)],
+    "caf_scf_geometry": [_I32, _I32, _I32, ct.POINTER(_I32), ct.POINTER(_I64), ct.POINTER(_I64), ct.POINTER(_I32), ct.POINTER(_I64),
+                         ct.POINTER(_I64)],
     "caf_cluster_geometry": [_I64, _I32, _I32] + [ct.POINTER(_I32)] * 3 + [ct.POINTER(_I64)] * 3,
     "caf_kmeans_seed": [_P, _I64, _I64, _I32, _P, _P, ct.POINTER(_I32), ct.POINTER(_I32), _I64, _I32, _P, _P, _P, _P],
     "caf_kmeans_lloyd": [_P, _I64, _I64, _I32, _P, _P, ct.POINTER(_I32), ct.POINTER(_I32), _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P],

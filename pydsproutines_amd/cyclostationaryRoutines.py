@@ -27,7 +27,16 @@ any other nfft is composed from an elementwise kernel, the rocFFT rows and a lin
                             evident intent, without the overwrite), offset and baud refined by a three-point parabola.
 
 Limits of the method: a shaped m-PSK burst has lines at m f0 +- k baud, so an x^8 search can land one baud
-line away; the baud line needs a few hundred symbols.  Without a device the calls raise; there is no host path."""
+line away; the baud line needs a few hundred symbols.  Without a device the calls raise; there is no host path.
+
+The spectral correlation function (csrc/caf_scf.hip) is the general tool where a power law is not: scfFAM is the
+FFT accumulation method on a record that nothing has been cut out of -- N' windowed channels every L samples with absolute phase,
+then for every pair of channels (k, l) a P-point transform of X_k conj(X_l) (conjugate=True: of X_k X_l), of which the M = P L / N'
+bins around zero are kept.  Cell (k, l, q) lies at cycle frequency alpha = ((k - l) M + q) fs / (P L) and frequency
+f = (k + l) fs / (2 N').  Every cycle frequency of the record comes out at once: a shaped PSK or QAM signal shows its baud in the
+non-conjugate coherence whatever its order, BPSK shows 2 f0 in the conjugate one.  The profile (per alpha-bin the largest cell
+and the f of that cell) is folded inside the launch, so a wide search writes (2 N' - 1) M values per row and not N'^2 M.
+cycleLines and estimateBaudSCF read lines off the profile on the host; scfAlpha and scfFreq give the axes."""
 
 import ctypes as ct
 from collections import namedtuple
@@ -285,3 +294,144 @@ def estimateBursts(d_xbatch, lengths=None, fs=1.0, max_m=4, nfft=None, threshold
     index, peak, side, power = _lib.download(d_index, stream), d_peak.get(), d_side.get(), d_power.get()
     order, offset, baud, ratios, strength = burst_parameters(index, peak, side, power, h_len, moments, bands, nfft, fs, max_m, threshold)
     return BurstParameters(order, offset, baud, ratios, strength, index, peak, side, power, tuple(moments), tuple(bands), nfft)
+
+
+# ---- the spectral correlation function (FAM) ---------------------------------------------------------------------------------
+SCF = namedtuple("SCF", "scf alpha_val alpha_arg psd M num_alpha Np L P conjugate coherence")
+CycleLines = namedtuple("CycleLines", "alpha value freq bin")
+SCF_MIN_HOPS, SCF_MAX_HOPS = 64, 16384
+
+
+def scf_geometry(Np, L, P):
+    """dict(M, num_alpha, min_samples, threads, lds_bytes, scratch_bytes_per_row) of a scfFAM call; ValueError for sizes that are
+    refused (Np a power of two in 64 .. 1024, L in 1 .. Np/4, P in 64 .. 16384, P L / Np >= 2)."""
+    names = ("M", "num_alpha", "min_samples", "threads", "lds_bytes", "scratch_bytes_per_row")
+    return dict(zip(names, _lib.query("caf_scf_geometry", int(Np), int(L), int(P))))
+
+
+def scf_default_hops(N, Np, L):
+    """the largest accepted power of two P with (P - 1) L + Np <= N"""
+    P = SCF_MAX_HOPS
+    while P >= SCF_MIN_HOPS and ((P - 1) * L + Np > N or P * L < 2 * Np):
+        P //= 2
+    if P < SCF_MIN_HOPS or P * L < 2 * Np:
+        raise ValueError("scfFAM: %d samples are too few for Np = %d and L = %d." % (N, Np, L))
+    return P
+
+
+def scfFAM(d_x, Np, L=None, P=None, window=None, smooth=None, conjugate=False, coherence=True, full=False, profile=True, psd=True):
+    """The FAM spectral correlation of d_x, a complex64 DeviceArray (N,) or (B, N): Np channels every L samples (default Np/4), P
+    hops (default: as many as N holds), window (Np) (default np.hamming(Np)) and smoothing (P) (default ones) as host arrays or
+    float32 DeviceArrays.  Returns SCF(scf (B, Np, Np, M) with full=True, alpha_val and alpha_arg (B, A) with profile=True, psd
+    (B, Np) float64 with psd=True, ...): DeviceArrays, None for the ones not asked for; see the module text for the axes."""
+    requireDeviceArray(d_x)
+    requireDtype(np.complex64, d_x)
+    if d_x.ndim == 1:
+        d_x = d_x.reshape(1, -1)
+    if d_x.ndim != 2:
+        raise ValueError("scfFAM: d_x must be (N,) or (B, N).")
+    if not (full or profile or psd):
+        raise ValueError("scfFAM: no output asked for.")
+    B, N = d_x.shape
+    Np = int(Np)
+    L = Np // 4 if L is None else int(L)
+    if Np < 1 or L < 1:
+        raise ValueError("scfFAM: Np and L must be positive.")
+    P = scf_default_hops(N, Np, L) if P is None else int(P)
+    geo = scf_geometry(Np, L, P)
+    M, A = geo["M"], geo["num_alpha"]
+    with _lib.held(None, _lib.IF_UPLOADED) as h:
+        d_w = h.put(np.hamming(Np) if window is None else window, np.float32)
+        requireDtype(np.float32, d_w)
+        if d_w.shape != (Np,):
+            raise ValueError("scfFAM: the window has Np entries.")
+        d_g = None
+        if smooth is not None:
+            d_g = h.put(smooth, np.float32)
+            requireDtype(np.float32, d_g)
+            if d_g.shape != (P,):
+                raise ValueError("scfFAM: the smoothing has P entries.")
+        _lib.require_device()
+        d_scf = empty((B, Np, Np, M), np.float32) if full else None
+        d_val = empty((B, A), np.float32) if profile else None
+        d_arg = empty((B, A), np.int32) if profile else None
+        d_psd = empty((B, Np), np.float64) if psd else None
+        desc = _lib.CafScfDesc(d_x=d_x.ptr, rows=B, pitch=N, n=N, num_channels=Np, hop=L, num_hops=P, conjugate=int(bool(conjugate)),
+                               coherence=int(bool(coherence)), d_window=d_w.ptr, d_smooth=None if d_g is None else d_g.ptr, stream=None)
+        out = _lib.CafScfOutputs(*[None if a is None else a.ptr for a in (d_scf, d_val, d_arg, d_psd)])
+        _lib.call("caf_scf_fam", desc, out)
+    return SCF(d_scf, d_val, d_arg, d_psd, M, A, Np, L, P, bool(conjugate), bool(coherence))
+
+
+def scfBins(res):
+    """the signed alpha index d M + q of every alpha-bin: alpha = index fs / (P L)"""
+    zero = (res.Np if res.conjugate else res.Np - 1) * res.M + res.M // 2
+    return np.arange(res.num_alpha, dtype=np.int64) - zero
+
+
+def scfAlpha(res, fs=1.0):
+    """the cycle frequency of every alpha-bin, (A,)"""
+    return scfBins(res) * (float(fs) / (res.P * res.L))
+
+
+def scfFreq(res, fs=1.0, s=None):
+    """the frequency f = s fs / (2 Np) of channel sums s (an alpha_arg array), or with s=None the axis of a cell's channels:
+    k fs / Np, k = -Np/2 .. Np/2 - 1"""
+    if s is None:
+        return np.arange(-(res.Np // 2), res.Np // 2) * (float(fs) / res.Np)
+    return np.asarray(s, dtype=np.float64) * (float(fs) / (2 * res.Np))
+
+
+def cycle_lines(val, arg, bins, Np, L, P, conjugate, fs=1.0, num=4, guard=None):
+    """The host half of cycleLines on one profile (A,): (alpha, value, freq, bin) of the `num` strongest local maxima with
+    |alpha| >= guard (default fs / Np: the zero tile and its skirts), strongest first, NaN / 0 where there are fewer.  The
+    non-conjugate profile is its own mirror image in alpha, so there only alpha > 0 is searched."""
+    val = np.asarray(val, dtype=np.float64)
+    step = float(fs) / (P * L)
+    guard = float(fs) / Np if guard is None else float(guard)
+    a = np.arange(1, val.size - 1)
+    alpha = bins[a] * step
+    keep = (val[a] > val[a - 1]) & (val[a] >= val[a + 1]) & (np.abs(alpha) >= guard)
+    if not conjugate:
+        keep &= alpha > 0
+    a = a[keep]
+    a = a[np.argsort(-val[a], kind="stable")][:num]
+    o_alpha, o_val, o_f = np.full(num, np.nan), np.zeros(num), np.full(num, np.nan)
+    o_bin = np.zeros(num, dtype=np.int64)
+    delta = parabola(val[a - 1], val[a], val[a + 1])
+    o_alpha[: a.size] = (bins[a] + delta) * step
+    o_val[: a.size] = val[a]
+    o_f[: a.size] = np.asarray(arg)[a] * (float(fs) / (2 * Np))
+    o_bin[: a.size] = bins[a]
+    return o_alpha, o_val, o_f, o_bin
+
+
+def cycleLines(res, fs=1.0, num=4, guard=None):
+    """CycleLines(alpha, value, freq, bin), each (B, num): the strongest lines of every row's profile (see cycle_lines); alpha is
+    refined by a three-point parabola, freq is the f of the winning cell, bin the signed alpha index of the maximum."""
+    if res.alpha_val is None:
+        raise ValueError("cycleLines: the result has no profile.")
+    val, arg, bins = res.alpha_val.get(), res.alpha_arg.get(), scfBins(res)
+    rows = [cycle_lines(val[r], arg[r], bins, res.Np, res.L, res.P, res.conjugate, fs, num, guard) for r in range(val.shape[0])]
+    return CycleLines(*[np.stack([row[i] for row in rows]) for i in range(4)])
+
+
+def estimateBaudSCF(d_xbatch, fs, baud_band, Np=64, L=None, P=None):
+    """Per row of d_xbatch (B, N) the strongest line of the non-conjugate coherence with alpha inside baud_band = (lo, hi):
+    (baud, value, freq) host arrays of B entries, NaN / 0 for a row without a local maximum in the band."""
+    res = scfFAM(d_xbatch, Np, L, P, psd=False)
+    val, arg, bins = res.alpha_val.get().astype(np.float64), res.alpha_arg.get(), scfBins(res)
+    step = float(fs) / (res.P * res.L)
+    alpha = bins * step
+    B = val.shape[0]
+    baud, value, freq = np.full(B, np.nan), np.zeros(B), np.full(B, np.nan)
+    a = np.arange(1, val.shape[1] - 1)
+    inside = (alpha[a] >= float(baud_band[0])) & (alpha[a] <= float(baud_band[1]))
+    for r in range(B):
+        v = val[r]
+        c = a[inside & (v[a] > v[a - 1]) & (v[a] >= v[a + 1])]
+        if c.size:
+            i = c[np.argmax(v[c])]
+            baud[r] = (bins[i] + float(parabola(v[i - 1], v[i], v[i + 1]))) * step
+            value[r], freq[r] = v[i], arg[r, i] * (float(fs) / (2 * res.Np))
+    return baud, value, freq
