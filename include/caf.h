@@ -61,7 +61,10 @@ CAF_EXPORT int32_t caf_set_device(int32_t device);
 CAF_EXPORT int32_t caf_device_info(int32_t device, char* name, int32_t name_len, int64_t* total_mem,
                                    int32_t* compute_units);
 /* caf_malloc / caf_free go through a caching allocator (the counterpart of cupy's default memory pool, which
- * every cp.empty / cp.zeros of the reference's wrappers hits): freed blocks are kept and reused in stream order;
+ * every cp.empty / cp.zeros of the reference's wrappers hits): freed blocks are kept and reused.  A block may be freed
+ * while work on the NULL stream still uses it: it is then handed out again only once that work has completed (or to the
+ * library's own null-stream scratch, which is ordered behind it), so its next user may sit on any stream.  Work on any
+ * other stream must be drained before its blocks are freed;
  * CAF_POOL_MB bounds the cached bytes (default 8192, 0 = plain hipMalloc / hipFree).  caf_pool_trim returns the
  * cache to the driver (cp.get_default_memory_pool().free_all_blocks()).  CAF_POOL_POISON=<32-bit hex word> (diagnostic,
  * read on every allocation; unset, empty or 0 = off) fills every block handed out, reused or fresh, with that word

@@ -590,8 +590,9 @@ IF_UPLOADED, CALLER, ALWAYS = "caller's stream, if something was uploaded", "cal
 
 class held:
     """What a wrapper uploads for one call, kept until the stream is done with it.  A block that goes back to the pool under a
-    queued kernel is handed to the pool's next user while that kernel still reads it, so on the way out the stream is drained by
-    the site's rule (IF_UPLOADED, CALLER or ALWAYS) and only then are the uploads let go.  On the way out through an exception the
+    kernel queued on a caller's stream is handed to the pool's next user while that kernel still reads it (the pool looks after
+    the null stream alone: caf_pool.hip), so on the way out the stream is drained by the site's rule (IF_UPLOADED, CALLER or
+    ALWAYS) and only then are the uploads let go.  On the way out through an exception the
     rule does not count: whatever was uploaded is drained, on the null stream too."""
 
     def __init__(self, stream, rule):

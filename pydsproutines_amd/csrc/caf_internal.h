@@ -77,14 +77,17 @@ int host_d2h_transposed(void* h_dst, bool dst_f64, const float* d_src, int64_t r
     } while (0)
 
 // caching device allocator (caf_pool.hip)
-int pool_alloc(void** out, int64_t bytes);
+// behind_null_stream: the block's user is ordered behind everything queued on the null stream so far, so it may have a block
+// that was freed under null-stream work still running (caf_pool.hip)
+int pool_alloc(void** out, int64_t bytes, bool behind_null_stream = false);
 int pool_free(void* p);
 void pool_trim();
 void pool_stats(int64_t* cached, int64_t* in_use, int64_t* hits, int64_t* misses);
 
 // The one owner of pooled scratch.  A block may go back to the pool only once nothing on a stream other than the null stream
-// can still touch it (caf_pool.hip): on the null stream the block's next user is ordered behind the work that uses it now,
-// on a caller's own stream the next user may sit anywhere, so that stream is synchronised first.  An entry point ends with
+// can still touch it (caf_pool.hip): a caller's own stream is synchronised first.  On the null stream the blocks go back with
+// the kernels that use them still queued; the pool keeps them as pending while the null stream is busy and hands a pending block to
+// null-stream scratch alone (which is ordered behind those kernels), never to a user that may sit on another stream.  An entry point ends with
 // `return sc.finish();`; the destructor covers every earlier return, where it blocks (on whatever stream) rather than free
 // blocks that are still in use.  blocking: the call also blocks on the null stream (kept per entry point: DESIGN.md).
 class Scratch {
@@ -96,7 +99,7 @@ public:
     int get(T** p, int64_t count) {
         void* q = nullptr;
         const int64_t bytes = count * (int64_t)sizeof(T);
-        const int rc = pool_alloc(&q, bytes < 16 ? 16 : bytes);
+        const int rc = pool_alloc(&q, bytes < 16 ? 16 : bytes, st_ == nullptr);
         if (rc) return rc;
         ptrs_.push_back(q);
         *p = (T*)q;

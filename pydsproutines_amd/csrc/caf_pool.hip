@@ -3,9 +3,12 @@
 // The reference leans on cupy's memory pool: every cp.empty / cp.zeros inside its wrappers is a pool hit, not a
 // cudaMalloc.  hipMalloc + hipFree cost 100-300 us per pair and hipFree synchronises the device, which is more than
 // most of the kernel-level entry points take, so freed blocks are kept per (device, rounded size) and handed out
-// again.  Reuse is safe in stream order: a block freed while a kernel on stream S still uses it is only ever touched
-// again by later work, so callers that stay on one stream (the host layer uses the null stream) need no
-// synchronisation; callers mixing streams synchronise before freeing, as with any stream-ordered pool.
+// again.  A block may be freed while work on the NULL stream still uses it (the host layer and null-stream scratch do
+// that); work on any other stream has to be drained by whoever frees (Scratch::finish, _lib.held).  So pool_free looks
+// at the null stream: if it is busy, the block is kept as pending.  Until an event recorded on that stream after the free
+// has completed (Marks, below) the block goes only to a user that says it is ordered behind the null stream (null-stream Scratch); every other
+// pool_alloc -- caf_malloc, scratch on a caller's stream, plan buffers: their next use may sit on a non-blocking stream or
+// a staging lane, which nothing on the null stream is ordered with -- passes it over and takes another block or misses.
 //
 //   CAF_POOL_MB       upper bound of cached (free) bytes per process, default 8192; 0 disables caching.
 //   CAF_POOL_POISON   diagnostic, read on every pool_alloc: a 32-bit word in hex (unset, empty or 0 = off).  When on, the
@@ -17,6 +20,7 @@
 #include <map>
 #include <mutex>
 #include <unordered_map>
+#include <vector>
 
 #include "caf_internal.h"
 
@@ -32,7 +36,20 @@ std::mutex g_mu;
 struct Cached {
     void* p;
     uint64_t seq;  // when it was freed (larger = more recent)
+    bool pending;  // freed while the null stream was busy: see Marks
 };
+// What is known of the null stream of one device.  Every block freed with seq <= settled is free of null-stream work.  A
+// block freed later while that stream was busy waits for an event recorded there after its free.  No event is recorded at the
+// free (every event is a packet on the stream it guards, and most blocks are never asked for by another stream's user): the
+// first pool_alloc that is refused a pending block records ONE event for everything freed so far, and the blocks settle
+// together once it has completed.  At most one event is in flight per device.
+struct Marks {
+    uint64_t settled = 0, covers = 0;  // covers: g_seq when the event in flight was recorded
+    hipEvent_t ev = nullptr;
+    bool in_flight = false;
+};
+constexpr int kMarkedDevices = 16;  // (beyond that a free under a busy null stream waits for the stream instead)
+Marks g_marks[kMarkedDevices];
 std::multimap<std::pair<int, int64_t>, Cached> g_free;  // (device, rounded bytes) -> block
 uint64_t g_seq = 0;
 std::unordered_map<void*, Live> g_live;                // blocks handed out
@@ -64,6 +81,30 @@ uint32_t poison_word() {
     return e && *e ? (uint32_t)std::strtoul(e, nullptr, 16) : 0u;
 }
 
+// caller holds g_mu and `dev` is current; whether a block of `dev` freed at `seq` while the null stream was busy is free of that work
+bool settled(int dev, uint64_t seq) {
+    Marks& m = g_marks[dev];
+    if (seq <= m.settled) return true;
+    if (m.in_flight) {
+        if (hipEventQuery(m.ev) != hipSuccess) {
+            (void)hipGetLastError();  // (hipErrorNotReady is the answer, not a failure)
+            return false;
+        }
+        m.in_flight = false;
+        if (m.covers > m.settled) m.settled = m.covers;
+        if (seq <= m.settled) return true;
+    }
+    // nothing in flight covers this block: one event for everything freed so far
+    if (!m.ev && hipEventCreateWithFlags(&m.ev, hipEventDisableTiming) != hipSuccess) m.ev = nullptr;
+    if (m.ev && hipEventRecord(m.ev, nullptr) == hipSuccess) {
+        m.in_flight = true;
+        m.covers = g_seq;
+    } else {
+        (void)hipGetLastError();
+    }
+    return false;
+}
+
 // caller holds g_mu; hipFree of every cached block of `dev` (or of all devices when dev < 0)
 void trim_locked(int dev) {
     for (auto it = g_free.begin(); it != g_free.end();) {
@@ -79,12 +120,22 @@ void trim_locked(int dev) {
 
 }  // namespace
 
-int pool_alloc(void** out, int64_t bytes) {
+int pool_alloc(void** out, int64_t bytes, bool behind_null_stream) {
     int dev = 0;
     CAF_HIP_TRY(hipGetDevice(&dev));
     const int64_t r = round_size(bytes);
+    const uint32_t poison = poison_word();
+    if (poison) CAF_HIP_TRY(hipDeviceSynchronize());  // the block's previous user may still run, on whatever stream
     std::lock_guard<std::mutex> lk(g_mu);
-    auto it = g_free.find({dev, r});
+    auto range = g_free.equal_range({dev, r});
+    auto it = g_free.end();
+    // Blocks of one size lie in the order they were freed, and a block settles no later than one freed after it, so only the
+    // first is looked at: one hipEventQuery per call at the most, however many blocks wait.
+    if (range.first != range.second) {
+        const Cached& c = range.first->second;
+        // (a poisoned pool has just waited for the device: nothing is pending any more)
+        if (behind_null_stream || !c.pending || poison || settled(dev, c.seq)) it = range.first;
+    }
     void* p = nullptr;
     if (it != g_free.end()) {
         p = it->second.p;
@@ -108,8 +159,7 @@ int pool_alloc(void** out, int64_t bytes) {
     g_live[p] = Live{r, dev};
     g_in_use += r;
     *out = p;
-    if (const uint32_t w = poison_word()) {  // (r is a multiple of 512)
-        CAF_HIP_TRY(hipDeviceSynchronize());  // the block's previous user may still run on another stream
+    if (const uint32_t w = poison) {  // (r is a multiple of 512)
         CAF_HIP_TRY(hipMemsetD32((hipDeviceptr_t)p, (int)w, (size_t)(r / 4)));
         CAF_HIP_TRY(hipDeviceSynchronize());
     }
@@ -142,7 +192,19 @@ int pool_free(void* p) {
         g_cached -= old->first.second;
         g_free.erase(old);
     }
-    g_free.emplace(std::make_pair(l.dev, l.bytes), Cached{p, ++g_seq});
+    int cur = l.dev;
+    (void)hipGetDevice(&cur);
+    if (cur != l.dev) (void)hipSetDevice(l.dev);  // (the null stream asked is the one of the block's device)
+    bool pending = false;
+    if (hipStreamQuery(nullptr) == hipSuccess) {  // idle: this block and every block of the device freed before it are settled
+        if (l.dev >= 0 && l.dev < kMarkedDevices) g_marks[l.dev].settled = g_seq + 1;
+    } else {
+        (void)hipGetLastError();  // (hipErrorNotReady is the answer, not a failure)
+        if (l.dev >= 0 && l.dev < kMarkedDevices) pending = true;
+        else (void)hipStreamSynchronize(nullptr);
+    }
+    if (cur != l.dev) (void)hipSetDevice(cur);
+    g_free.emplace(std::make_pair(l.dev, l.bytes), Cached{p, ++g_seq, pending});
     g_cached += l.bytes;
     return CAF_OK;
 }

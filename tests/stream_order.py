@@ -21,6 +21,10 @@ and the three uploads themselves: Iq16FrontEnd.run copies the tail of its input 
 null stream right after the kernel, and null-stream code that clears or refills an array expects the kernel before it to be done
 with it.  None of this hides a misplaced launch: the compute call has been issued behind the stall by then.  `mode="outer"` is for
 wrappers that take stream=: nothing is substituted, stalled or drained; the test calls reproduce_on itself.
+
+The other way round (tests/test_gpu_pool_streams.py, tests/test_pool_streams_host.py): `Handoff` stalls the NULL stream and reads
+the flag on an idle caller's stream, and `lockstep` runs one null-stream case twice so that each compute call is issued once on
+the stalled null stream and once on the caller's stream: the pool's counters then say whether a block of the first went to the second.
 """
 
 import contextlib
@@ -346,3 +350,186 @@ def session(mode, stream=None, lib=None, case=None, **kw):
                 sess.close()
             finally:
                 _merge(sess)
+
+
+# ------------------------------------------------------------------------------------------ the hand-off of pooled blocks
+# tests/test_gpu_pool_streams.py: the NULL stream is stalled, a call A is issued on it, a call B on an idle caller's stream.
+# While A's kernels are queued, no block A took may be handed to a call that is not ordered behind A.
+class HandedOff(AssertionError):
+    pass
+
+
+def handoff_verdict(hits_before, hits_after, flag_set, since_stall, idle_stall, what=""):
+    """What B's return says.  hits_*: the pool's hit count before and after B (after caf_pool_trim the cache holds what A gave
+    back and nothing else, so a hit is one of A's blocks); flag_set: the stall had ended when B had returned (read after the
+    counters); since_stall: host seconds from the stall's first memset to B's return; idle_stall: what the same stall takes on an
+    idle null stream, measured in this process.
+      "withheld"  the stall still ran and B missed every time
+      "ordered"   B returned only once the stall had ended, no earlier than half its idle duration: B waited for A
+      HandedOff   the stall still ran and B had a hit
+      Inconclusive  the stall ended early: nothing can be said"""
+    if not flag_set:
+        if hits_after != hits_before:
+            raise HandedOff("%s: %d pool hit(s) on a caller's stream while the null-stream call that freed the blocks was still queued "
+                            "behind the stall" % (what, hits_after - hits_before))
+        return "withheld"
+    if since_stall < 0.5 * idle_stall:
+        raise Inconclusive("inconclusive: %s: the stall had ended %.2f ms after its first memset, idle it takes %.2f ms"
+                           % (what, 1e3 * since_stall, 1e3 * idle_stall))
+    return "ordered"
+
+
+class Handoff:
+    """The stall on the null stream, the probe on the caller's stream and the check of one pair of calls, on one library
+    object (the real CDLL, or a recording fake)."""
+
+    def __init__(self, lib, stream, nbytes=NBYTES, rounds=ROUNDS):
+        self.s = Session(lib, stream, None, "outer", nbytes=nbytes, rounds=rounds)
+        self.lib, self.stream, self.idle = lib, stream, None
+        self.verdicts = []  # (what, verdict of A, verdict of B)
+
+    def probe(self):
+        """the flag, read on the caller's stream: Session.flag_set reads it on the null stream, behind the stall"""
+        word = ct.c_uint32(0x12345678)
+        self.s._ok(self.lib.caf_d2h(ct.byref(word), self.s.d_flag, 4, self.stream), "caf_d2h")
+        assert word.value in (0, 0xFFFFFFFF), "the flag holds 0x%08X" % word.value
+        return word.value != 0
+
+    def stats(self):
+        v = [ct.c_int64() for _ in range(4)]
+        self.s._ok(self.lib.caf_pool_stats(*[ct.byref(x) for x in v]), "caf_pool_stats")
+        return dict(cached=v[0].value, in_use=v[1].value, hits=v[2].value, misses=v[3].value)
+
+    def arm(self, trim=True):
+        """both streams drained, the cache emptied, the flag zeroed, the null stream stalled"""
+        self.s.sync(self.stream)
+        self.s.sync(None)
+        if trim:
+            self.s._ok(self.lib.caf_pool_trim(), "caf_pool_trim")
+        self.s._ok(self.lib.caf_memset(self.s.d_flag, 0, 4, None), "caf_memset")
+        self.s.sync(None)
+        self.s.stall(None)
+
+    def drain(self):
+        self.s.sync(None)
+        self.s.sync(self.stream)
+
+    def measure_idle(self):
+        """the stall on an idle null stream, host clock, first memset to the return of the synchronisation"""
+        self.arm(trim=False)
+        self.s.sync(None)
+        self.idle = time.perf_counter() - self.s.t0
+        return self.idle
+
+    def check(self, what, issue_a, issue_b):
+        """issue_a() on the null stream behind the stall, issue_b() on the caller's stream; returns (verdict of A, verdict of B,
+        issue_a's value, issue_b's value).  A: "blocked" (returned only after the stall: safe by construction, B is not judged),
+        "no scratch" (the pool's counters did not move: nothing to hand off) or "queued"."""
+        assert self.idle is not None, "measure_idle() first"
+        self.arm()
+        try:
+            s0 = self.stats()
+            ra = issue_a()
+            a_after = self.probe()
+            s1 = self.stats()
+            rb = issue_b()
+            s2 = self.stats()
+            since = time.perf_counter() - self.s.t0
+            b_after = self.probe()
+            if a_after:
+                va, vb = "blocked", "not judged"
+            elif s1["hits"] + s1["misses"] == s0["hits"] + s0["misses"]:
+                va, vb = "no scratch", "not judged"
+            else:
+                va, vb = "queued", handoff_verdict(s1["hits"], s2["hits"], b_after, since, self.idle, what)
+        finally:
+            self.drain()
+        self.verdicts.append((what, va, vb))
+        return va, vb, ra, rb
+
+    def close(self):
+        self.s.close()
+
+
+def lockstep(fn, handoff, per_name=2, timeout=120.0, special=None):
+    """Two runs of one case written for the null stream, A on this thread and B on a second one, of which only one runs at a
+    time.  Each run makes its own arrays and holds them across its calls; where both have reached the same compute entry
+    point with stream None (the first `per_name` calls of each name), A's call is issued on the stalled null stream and B's
+    on the caller's stream through handoff.check, both streams are drained, and each run goes on with its own status.  Every
+    other call of either run goes to the null stream as written.  special: name -> (is_null(args), on_stream(args, stream)) for
+    an entry point that takes its stream elsewhere than last (caf_scf_fam: in its descriptor).  Returns (A's result, B's result, [(name, verdict of A,
+    verdict of B)])."""
+    import queue
+    import threading
+
+    from pydsproutines_amd import _lib
+
+    real = _lib.load()
+    special = special or {}
+    compute = frozenset(compute_entry_points()) | frozenset(special)
+    posts, answers = queue.Queue(), queue.Queue()  # B -> A: ("call", name, fn, args) | ("done", result) | ("error", exc); A -> B: status
+    abort = object()
+    state = {"b": None, "next": None, "seen": {"A": {}, "B": {}}}
+    verdicts = []
+
+    def on_stream(name, args):
+        if name in special:
+            return special[name][1](args, handoff.stream)
+        return tuple(args[:-1]) + (handoff.stream,)
+
+    def routed(name, f, args):
+        if not (special[name][0](args) if name in special else (args and _is_null(args[-1]))):
+            return f(*args)
+        side = "B" if threading.get_ident() == state["b"] else "A"
+        seen = state["seen"][side]
+        seen[name] = seen.get(name, 0) + 1
+        if seen[name] > per_name:
+            return f(*args)
+        if side == "B":
+            posts.put(("call", name, f, args))
+            rc = answers.get(timeout=timeout)
+            if rc is abort:
+                raise RuntimeError("the other run of the pair failed")
+            return rc
+        nxt = state["next"]
+        if nxt[0] == "error":
+            raise nxt[1]
+        assert nxt[0] == "call" and nxt[1] == name, "the two runs of one case diverge: %s here, %r there" % (name, nxt[:2])
+        b_f, b_args = nxt[2], nxt[3]
+        va, vb, ra, rb = handoff.check(name, lambda: f(*args), lambda: b_f(*on_stream(name, b_args)))
+        verdicts.append((name, va, vb))
+        answers.put(rb)
+        state["next"] = posts.get(timeout=timeout)  # B runs on, to its next such call or to its end
+        return ra
+
+    class P:
+        def __getattr__(self, name):
+            f = getattr(real, name)
+            if name not in compute:
+                return f
+            return lambda *args: routed(name, f, args)
+
+    def second():
+        state["b"] = threading.get_ident()
+        try:
+            posts.put(("done", fn()))
+        except BaseException as e:  # (reaches the test through A)
+            posts.put(("error", e))
+
+    orig_load = _lib.load
+    _lib.load = lambda: proxy
+    proxy = P()
+    th = threading.Thread(target=second)
+    try:
+        th.start()
+        state["next"] = posts.get(timeout=timeout)
+        out_a = fn()
+        nxt = state["next"]
+        if nxt[0] == "error":
+            raise nxt[1]
+        assert nxt[0] == "done", "the second run still had %s to issue when the first had ended" % nxt[1]
+        return out_a, nxt[1], verdicts
+    finally:
+        answers.put(abort)
+        th.join(timeout)
+        _lib.load = orig_load

@@ -63,7 +63,12 @@ def _same(got, want, what):
 def test_values(case):
     Np, L, P, B, cj, co, sm, cells = case
     x, g, refs = R.value_refs(case)
-    got = _fam(x, Np, L, P, g, cj, co, full=cells)
+    check_values(case, refs, _fam(x, Np, L, P, g, cj, co, full=cells))
+
+
+def check_values(case, refs, got):
+    """the outputs of one value case against its float64 restatement (also held by tests/test_gpu_pool_streams.py)"""
+    Np, L, P, B, cj, co, sm, cells = case
     worst = dict(scf=0.0, psd=0.0)
     undecided = 0
     for r, ref in enumerate(refs):
