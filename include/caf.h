@@ -992,6 +992,60 @@ CAF_EXPORT int32_t caf_scf_fam(const caf_scf_desc* desc, const caf_scf_outputs* 
 CAF_EXPORT int32_t caf_scf_geometry(int32_t num_channels, int32_t hop, int32_t num_hops, int32_t* m, int64_t* num_alpha,
                                     int64_t* min_samples, int32_t* threads, int64_t* lds_bytes, int64_t* scratch_bytes_per_row);
 
+/* ---- any-ratio resampling of ragged batches (filterRoutines.py: resampleRows; demodulationRoutines.py: conditionBursts;
+ *      caf_resample.hip).  Added without a version bump, detected by symbol. -------------------------------------------------
+ * Per row r: x_r[n], complex64, valid for 0 <= n < L_r (a sample outside reads as 0); nu_r, the carrier to remove in cycles per
+ * sample; t0_r, the input-sample position of output 0 (any real value); step_r > 0, input samples per output sample; w_r >= 1,
+ * input samples per unit of the pulse argument; M_r >= 0, the outputs to produce.  One pulse table for the call: p[0 .. 2 H Q]
+ * float32, H the half width in units, Q the entries per unit; h(u) = 0 for |u| >= H and elsewhere the linear interpolation of p
+ * at position (u + H) Q.
+ *   t_m    = t0_r + m step_r                                                                      (float64, one fma)
+ *   y_r[m] = (1 / w_r) sum_{n : |t_m - n| < H w_r, 0 <= n < L_r} x_r[n] e^{-j 2 pi nu_r n} h((t_m - n) / w_r),   0 <= m < M_r
+ *   y_r[m] = 0                                                                                     for M_r <= m < out_pitch
+ * In float64 operations: H w_r is rounded once; n runs from max(floor(t_m - H w_r) + 1, 0) to min(ceil(t_m + H w_r) - 1,
+ * L_r - 1); the table position is q = fma(t_m - n, Q / w_r, H Q) with Q / w_r rounded once, clamped to 0 .. 2 H Q, its entry
+ * i = min(floor(q), 2 H Q - 1) and its fraction f = q - i.  In float32: the phasor (from nu_r n reduced exactly to a fraction
+ * of a turn, so nu = 1e6 + 0.25 loses nothing), the mixing product, the lerp p[i] + f (p[i + 1] - p[i]), the products, the sum
+ * over n upwards, and the final product with the float32 nearest 1 / w_r.
+ * Limits: 1 <= H <= 16; 2 <= Q <= 1024, any integer; H Q <= 8192; 1 <= w_r <= 64; 2^-6 <= step_r <= 64; |t0_r| < 2^31;
+ * |nu_r| <= 2^20; 0 <= L_r <= pitch < 2^31; 0 <= M_r <= out_pitch < 2^31; rows >= 1.  Everything else (NaN included) returns
+ * CAF_ERR_INVALID with a caf_last_error() text before anything touches a device.
+ * h_nu, h_t0, h_step, h_width (float64), h_lengths and h_counts (int32) are HOST arrays of `rows` entries, as the job arrays of
+ * caf_kmeans_lloyd are; h_lengths may be NULL (every row has `pitch` samples).  They are checked, copied into a staging block
+ * the library keeps, uploaded into a pooled block on the call's stream and given back to the pool in stream order (when an
+ * event behind the launch has completed); the caller's arrays are free again on return, and no step is read from device memory
+ * unchecked.  d_x (rows, pitch) and d_y (rows, out_pitch) are complex64 on the device and must not overlap; every element of
+ * d_y is written.  One launch; the grid is over (row, tile of outputs) with the tile of caf_resample_geometry at the call's
+ * largest step and width.  No atomics: a row gives the same bits alone or at any place in any batch, whatever the other rows'
+ * steps and widths make of the tile, and on every run.  CAF_RESAMPLE_DEBUG=1 prints one line per call on stderr
+ * (`[caf resample] rows=... tile=... threads=... lds=... support=...`, support = floor(2 H max w) + 1 terms).
+ * The stream is a field of the descriptor: all device work of the call is queued on desc->stream and nowhere else, as for every
+ * entry point that ends in `void* stream`, and the call does not wait for it; tests/test_gpu_resample.py holds it to that behind
+ * a stalled stream. */
+typedef struct caf_resample_desc {
+    const float* d_x;         /* (rows, pitch) complex64 */
+    int64_t rows, pitch;
+    const int32_t* h_lengths; /* HOST (rows): L_r, or NULL = pitch */
+    const double* h_nu;       /* HOST (rows): cycles per sample */
+    const double* h_t0;       /* HOST (rows): input position of output 0 */
+    const double* h_step;     /* HOST (rows): input samples per output */
+    const double* h_width;    /* HOST (rows): input samples per unit of the pulse argument */
+    const int32_t* h_counts;  /* HOST (rows): M_r */
+    const float* d_table;     /* (2 H Q + 1) float32, device */
+    int32_t half_width;       /* H */
+    int32_t phases;           /* Q */
+    float* d_y;               /* (rows, out_pitch) complex64 */
+    int64_t out_pitch;
+    void* stream;
+} caf_resample_desc;
+
+CAF_EXPORT int32_t caf_resample_rows(const caf_resample_desc* desc);
+/* tile: the outputs of a workgroup at these sizes (a power of two up to 1024: the largest whose table and slice of
+ * (tile - 1) max_step + 2 H max_width samples fit 160 KiB of LDS); threads per workgroup; bytes of dynamic LDS.  Every output is
+ * optional (NULL).  Sizes that caf_resample_rows refuses: CAF_ERR_INVALID.  No device work. */
+CAF_EXPORT int32_t caf_resample_geometry(int32_t half_width, int32_t phases, double max_step, double max_width, int32_t* tile,
+                                         int32_t* threads, int64_t* lds_bytes);
+
 /* ---- batched k-means and cluster scores (clusterRoutines.py: ClusterEngine, ClusterEngine2D, AngularClusterEngine;
  *      caf_cluster.hip) ---------------------------------------------------------------------------------------------------
  * Everything is float64.  d_x: (P, pitch, D) row-major, P problems of up to `pitch` points in D dimensions.  d_lengths:

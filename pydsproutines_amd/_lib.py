@@ -247,6 +247,26 @@ class CafScfOutputs(ct.Structure):
     ]
 
 
+class CafResampleDesc(ct.Structure):
+    _fields_ = [
+        ("d_x", ct.c_void_p),
+        ("rows", ct.c_int64),
+        ("pitch", ct.c_int64),
+        ("h_lengths", ct.c_void_p),
+        ("h_nu", ct.c_void_p),
+        ("h_t0", ct.c_void_p),
+        ("h_step", ct.c_void_p),
+        ("h_width", ct.c_void_p),
+        ("h_counts", ct.c_void_p),
+        ("d_table", ct.c_void_p),
+        ("half_width", ct.c_int32),
+        ("phases", ct.c_int32),
+        ("d_y", ct.c_void_p),
+        ("out_pitch", ct.c_int64),
+        ("stream", ct.c_void_p),
+    ]
+
+
 CAF_TRAJ_STATIONARY = 0
 CAF_TRAJ_CONSTANT_VELOCITY = 1
 CAF_TRAJ_INTERPOLATED = 2
@@ -399,6 +419,8 @@ _SIGNATURES = {
     "caf_scf_fam": [ct.POINTER(CafScfDesc), ct.POINTER(CafScfOutputs)],
     "caf_scf_geometry": [_I32, _I32, _I32, ct.POINTER(_I32), ct.POINTER(_I64), ct.POINTER(_I64), ct.POINTER(_I32), ct.POINTER(_I64),
                          ct.POINTER(_I64)],
+    "caf_resample_rows": [ct.POINTER(CafResampleDesc)],
+    "caf_resample_geometry": [_I32, _I32, ct.c_double, ct.c_double, ct.POINTER(_I32), ct.POINTER(_I32), ct.POINTER(_I64)],
     "caf_cluster_geometry": [_I64, _I32, _I32] + [ct.POINTER(_I32)] * 3 + [ct.POINTER(_I64)] * 3,
     "caf_kmeans_seed": [_P, _I64, _I64, _I32, _P, _P, ct.POINTER(_I32), ct.POINTER(_I32), _I64, _I32, _P, _P, _P, _P],
     "caf_kmeans_lloyd": [_P, _I64, _I64, _I32, _P, _P, ct.POINTER(_I32), ct.POINTER(_I32), _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P],

@@ -723,6 +723,45 @@ def demodulateBursts(d_xbatch, osr: int, m, preambles=None, searchStart: int = 0
                              svd_metric=out["svd"], best=out.get("best"), payload=out.get("payload"), count=out.get("count"))
 
 
+def conditionBursts(d_xbatch, lengths, offset, baud, fs=1.0, osr=4, table=None, matched=False, beta=0.35):
+    """The bridge from estimateBursts to demodulateBursts: every row of the ragged complex64 batch (rows, n) is shifted by its own
+    -offset and resampled from its own fs / baud samples per symbol to `osr`, in one launch (filterRoutines.resampleRows with
+    nu = offset / fs and step = fs / (baud osr)).  width = max(1, step) with `table` (a pulse table of half width H = 8, 16 Q + 1 entries; default kaiserSincTable()), or with
+    matched=True width = fs / baud and rrcTable(beta, 8, 512): the matched filter of root-raised-cosine bursts.  A row whose offset
+    or baud is NaN (no line found) gets length 0 and zeros.  Returns (d_y, lengths_out): d_y goes straight into one
+    demodulateBursts(d_y, osr, m_per_row, lengths=lengths_out) call whatever the rows' original rates."""
+    from .filterRoutines import resampleRows, rrcTable
+
+    cupyRequireDtype(np.complex64, d_xbatch)
+    if d_xbatch.ndim == 1:
+        d_xbatch = d_xbatch.reshape((1, -1))
+    if d_xbatch.ndim != 2:
+        raise ValueError("Input must be 1D or 2D array.")
+    rows, n = d_xbatch.shape
+    osr, fs = int(osr), float(fs)
+    if not 1 <= osr <= 32:
+        raise ValueError("osr must be within 1 .. 32.")
+    if not (np.isfinite(fs) and fs > 0):
+        raise ValueError("fs must be positive.")
+    lengths = np.ascontiguousarray(np.broadcast_to(np.asarray(lengths, np.int32), (rows,)))
+    offset = np.array(np.broadcast_to(np.asarray(offset, np.float64), (rows,)))
+    baud = np.array(np.broadcast_to(np.asarray(baud, np.float64), (rows,)))
+    dead = ~(np.isfinite(offset) & np.isfinite(baud) & (baud > 0))
+    offset[dead], baud[dead] = 0.0, fs / osr  # (step 1: any accepted value, the row produces nothing)
+    step = fs / (baud * osr)
+    if matched:
+        if table is not None:
+            raise ValueError("matched=True brings its own table.")
+        width, table, H, Q = fs / baud, rrcTable(beta, 8, 512), 8, 512
+    else:
+        width, H, Q = np.maximum(1.0, step), (None if table is None else 8), (None if table is None else (np.size(table) - 1) // 16)
+    with np.errstate(all="ignore"):
+        m = np.clip(np.floor((lengths - 1) / step) + 1, 0, 2.0 ** 31 - 1).astype(np.int32)
+    m[dead | (lengths < 1)] = 0
+    res = resampleRows(d_xbatch, step, np.where(dead, 0, lengths).astype(np.int32), offset / fs, 0.0, width, table, H, Q, m, max(osr, int(m.max())))
+    return res.y, res.lengths
+
+
 # %% CP2FSK
 def _cp2fsk_tones(h, up):
     """(2, up) complex128: row 0 the tone of bit 0, exp(-j pi h n / up), row 1 the tone of bit 1, its conjugate"""

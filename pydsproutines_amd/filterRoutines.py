@@ -6,6 +6,8 @@ Semantics pinned by the reference itself: FIR == scipy.signal.lfilter(taps, 1, x
 (benchmark_upfirdnkernels.py:58-67), moving average == lfilter(ones(L)/L)
 (filterRoutines.py:1256), moving complex sum == |np.convolve(x, ones(L), 'valid')|^2 (:1358),
 WOLA channeliser == filterRoutines.wola (:578-632) and its streaming wrapper Channeliser (:636-690),
+any-ratio resampling == resampleRows (include/caf.h: caf_resample_rows) with the table makers kaiserSincTable / rrcTable,
+resample_poly == scipy.signal.resample_poly on complex64 rows, resampleFactorWizard (:1090-1117),
 burst detection == cupyThresholdEdges / cupyGatherEdges / BurstDetector / energyDetection (:701-1088) with the
 median of cupyx.scipy.signal.medfilt (== scipy.signal.medfilt) as ``medfilt``.
 CUDA launch-tuning kwargs are accepted and ignored (except THREADS_PER_BLOCK / edgesMaxPerBlock of cupyThresholdEdges,
@@ -13,6 +15,8 @@ which set its output layout).
 """
 
 import ctypes as ct
+import math
+from collections import namedtuple
 
 import numpy as np
 
@@ -581,3 +585,180 @@ def energyDetection(ampSq, medfiltlen, snrReqLinear=4.0, noiseIndices=None, spli
 
 __all__ = ["CupyKernelFilter", "cupyMultiMovingAverage", "cupyMovingAverage", "cupyComplexMovingSum", "DeviceArray", "wola",
            "Channeliser", "medfilt", "cupyThresholdEdges", "cupyGatherEdges", "BurstDetector", "energyDetection"]
+
+
+# ---- any-ratio resampling (csrc/caf_resample.hip) -------------------------------------------------------------------------------
+Resampled = namedtuple("Resampled", "y lengths")
+
+
+def resampleFactorWizard(fs: int, rsfs: int):
+    """(up, down) integer factors from a starting sample rate to a target sample rate (ref: filterRoutines.py:1090-1117)."""
+    fs = int(fs)
+    rsfs = int(rsfs)
+    l = np.lcm(fs, rsfs)
+    up = l // fs
+    down = l // rsfs
+    return int(up), int(down)
+
+
+def _table_axis(H, Q):
+    H, Q = int(H), int(Q)
+    if not (1 <= H <= 16 and 2 <= Q <= 1024 and H * Q <= 8192):
+        raise ValueError("A pulse table needs 1 <= H <= 16, 2 <= Q <= 1024 and H Q <= 8192.")
+    return (np.arange(2 * H * Q + 1, dtype=np.float64) - H * Q) / Q
+
+
+def kaiserSincTable(H=8, Q=512, beta=8.0, cutoff=1.0):
+    """p[0 .. 2 H Q] float32: cutoff sinc(cutoff u) I0(beta sqrt(1 - (u / H)^2)) / I0(beta) at u = -H .. H in steps of 1 / Q,
+    computed in float64 and rounded once.  cutoff 1 passes everything below the lower of the two rates."""
+    u = _table_axis(H, Q)
+    if not (beta >= 0 and 0 < cutoff <= 1):
+        raise ValueError("kaiserSincTable: beta >= 0 and 0 < cutoff <= 1.")
+    win = np.i0(float(beta) * np.sqrt(np.maximum(0.0, 1.0 - (u / int(H)) ** 2))) / np.i0(float(beta))
+    return (float(cutoff) * np.sinc(float(cutoff) * u) * win).astype(np.float32)
+
+
+def rrcTable(beta, H, Q):
+    """p[0 .. 2 H Q] float32: the root-raised-cosine pulse of roll-off beta at u = -H .. H symbols in steps of 1 / Q, both
+    removable singularities (u = 0, |u| = 1 / (4 beta)) as limits, scaled so that sum p^2 / Q = 1 (unit energy per symbol): with
+    width = fs / baud the resampler is then also the matched filter."""
+    u = _table_axis(H, Q)
+    beta = float(beta)
+    if not 0 <= beta <= 1:
+        raise ValueError("rrcTable: 0 <= beta <= 1.")
+    h = np.empty_like(u)
+    zero = u == 0
+    edge = np.zeros_like(zero) if beta == 0 else np.isclose(np.abs(u), 1.0 / (4.0 * beta), rtol=0, atol=1e-9)
+    reg = ~(zero | edge)
+    v = u[reg]
+    h[reg] = (np.sin(np.pi * v * (1 - beta)) + 4 * beta * v * np.cos(np.pi * v * (1 + beta))) / (np.pi * v * (1 - (4 * beta * v) ** 2))
+    h[zero] = 1 - beta + 4 * beta / np.pi
+    if beta > 0:
+        h[edge] = beta / math.sqrt(2.0) * ((1 + 2 / np.pi) * math.sin(np.pi / (4 * beta)) + (1 - 2 / np.pi) * math.cos(np.pi / (4 * beta)))
+    h /= math.sqrt(float(np.sum(h * h)) / int(Q))
+    return h.astype(np.float32)
+
+
+def resample_geometry(H, Q, max_step, max_width):
+    """dict(tile, threads, lds_bytes) of a resampleRows call whose largest step and width are these; ValueError for sizes that are
+    refused (1 <= H <= 16, 2 <= Q <= 1024, H Q <= 8192, 2^-6 <= step <= 64, 1 <= width <= 64)."""
+    return dict(zip(("tile", "threads", "lds_bytes"), _lib.query("caf_resample_geometry", int(H), int(Q), float(max_step), float(max_width))))
+
+
+_DEFAULT_TABLE = []
+
+
+def _per_row(v, rows, dtype, what):
+    a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dtype), (rows,))) if np.ndim(v) == 0 else np.ascontiguousarray(v, dtype=dtype)
+    if a.shape != (rows,):
+        raise ValueError("resampleRows: %s is a scalar or has one entry per row." % what)
+    return a
+
+
+def resampleRows(d_x, step, lengths=None, nu=0.0, t0=0.0, width=None, table=None, H=None, Q=None, out_lengths=None, out_pitch=None):
+    """Every row of d_x, a complex64 DeviceArray (rows, n) or (n,), mixed down by nu (cycles per sample), resampled at `step` input
+    samples per output from input position t0 and filtered through the pulse table, in one launch (include/caf.h:
+    caf_resample_rows).  step, nu, t0, width: scalars or one float64 per row; lengths: the valid samples of each row (default n).
+    width: input samples per unit of the pulse argument, default max(1, step) (the cutoff follows the lower of the two rates).
+    table: float32 host array or DeviceArray of 2 H Q + 1 entries with its H and Q, default kaiserSincTable().  out_lengths: the
+    outputs of each row, default floor((L - 1 - t0) / step) + 1 clipped to >= 0; out_pitch: default their maximum.
+    Returns Resampled(y (rows, out_pitch) complex64 DeviceArray, zero beyond each row's count; lengths int32 host array)."""
+    if not isinstance(d_x, DeviceArray):
+        raise TypeError("Must be a device array (pydsproutines_amd.devarray.DeviceArray).")
+    requireDtype(np.complex64, d_x)
+    if d_x.ndim == 1:
+        d_x = d_x.reshape(1, -1)
+    if d_x.ndim != 2:
+        raise ValueError("resampleRows: d_x must be (n,) or (rows, n).")
+    rows, n = d_x.shape
+    h_step = _per_row(step, rows, np.float64, "step")
+    h_nu = _per_row(nu, rows, np.float64, "nu")
+    h_t0 = _per_row(t0, rows, np.float64, "t0")
+    h_w = np.maximum(1.0, h_step) if width is None else _per_row(width, rows, np.float64, "width")
+    h_len = np.full(rows, n, np.int32) if lengths is None else _per_row(lengths, rows, np.int32, "lengths")
+    if table is None:
+        if H is not None or Q is not None:
+            raise ValueError("resampleRows: H and Q belong to a table; the default table has its own.")
+        if not _DEFAULT_TABLE:
+            _DEFAULT_TABLE.append(kaiserSincTable())
+        table, H, Q = _DEFAULT_TABLE[0], 8, 512
+    elif H is None or Q is None:
+        raise ValueError("resampleRows: a table comes with its H and Q.")
+    H, Q = int(H), int(Q)
+    if out_lengths is None:
+        with np.errstate(all="ignore"):
+            m = np.floor((h_len - 1 - h_t0) / h_step) + 1
+        if not np.all(np.isfinite(m)):
+            raise ValueError("resampleRows: step and t0 must be finite.")
+        h_m = np.clip(m, 0, 2.0 ** 31 - 1).astype(np.int32)
+    else:
+        h_m = _per_row(out_lengths, rows, np.int32, "out_lengths")
+    out_pitch = max(1, int(h_m.max())) if out_pitch is None else int(out_pitch)
+    with _lib.held(None, _lib.IF_UPLOADED) as h:
+        d_t = h.put(table, np.float32)
+        requireDtype(np.float32, d_t)
+        if d_t.shape != (2 * H * Q + 1,):
+            raise ValueError("resampleRows: the table has 2 H Q + 1 entries.")
+        _lib.require_device()
+        if out_pitch < 1 or out_pitch >= 2 ** 31:
+            raise ValueError("resampleRows: 1 <= out_pitch < 2^31.")
+        d_y = empty((rows, out_pitch), np.complex64)
+        desc = _lib.CafResampleDesc(d_x=d_x.ptr, rows=rows, pitch=n, h_lengths=h_len.ctypes.data, h_nu=h_nu.ctypes.data, h_t0=h_t0.ctypes.data,
+                                    h_step=h_step.ctypes.data, h_width=h_w.ctypes.data, h_counts=h_m.ctypes.data, d_table=d_t.ptr,
+                                    half_width=H, phases=Q, d_y=d_y.ptr, out_pitch=out_pitch, stream=None)
+        _lib.call("caf_resample_rows", desc)
+    return Resampled(d_y, h_m)
+
+
+def resample_poly(d_x, up, down, taps=None):
+    """scipy.signal.resample_poly(x, up, down, window=taps) along the rows of a complex64 DeviceArray (rows, n) or (n,), zero
+    padding, on caf_upfirdn with scipy's own filter padding and trimming.  taps=None: scipy's design, firwin(20 max(up, down) + 1,
+    1 / max(up, down), window=("kaiser", 5.0)), computed on the host.  The taps are float32 on the device."""
+    if not isinstance(d_x, DeviceArray):
+        raise TypeError("Must be a device array (pydsproutines_amd.devarray.DeviceArray).")
+    requireDtype(np.complex64, d_x)
+    if up != int(up) or down != int(down):
+        raise ValueError("up and down must be integers")
+    up, down = int(up), int(down)
+    if up < 1 or down < 1:
+        raise ValueError("up and down must be >= 1")
+    one_row = d_x.ndim == 1
+    d_x2 = d_x.reshape(1, -1) if one_row else d_x
+    if d_x2.ndim != 2:
+        raise ValueError("resample_poly: d_x must be (n,) or (rows, n).")
+    g = math.gcd(up, down)
+    up //= g
+    down //= g
+    if up == down == 1:
+        return d_x.copy()
+    rows, n_in = d_x2.shape
+    n_out = n_in * up
+    n_out = n_out // down + bool(n_out % down)
+    if taps is None:
+        from scipy.signal import firwin  # lazily, as estimateBaud imports scipy.signal
+
+        max_rate = max(up, down)
+        half_len = 10 * max_rate
+        hh = firwin(2 * half_len + 1, 1.0 / max_rate, window=("kaiser", 5.0)).astype(np.float32) * np.float32(up)
+    else:
+        hh = np.array(taps, dtype=np.float64)
+        if hh.ndim > 1:
+            raise ValueError("window must be 1-D")
+        half_len = (hh.size - 1) // 2
+        hh = (hh * up).astype(np.float32)
+    n_pre_pad = down - half_len % down
+    n_post_pad = 0
+    n_pre_remove = (half_len + n_pre_pad) // down
+    size = CupyKernelFilter.getUpfirdnSize
+    while size(n_in, hh.size + n_pre_pad + n_post_pad, up, down) < n_out + n_pre_remove:
+        n_post_pad += 1
+    hh = np.concatenate((np.zeros(n_pre_pad, np.float32), hh, np.zeros(n_post_pad, np.float32)))
+    full = size(n_in, hh.size, up, down)
+    _lib.require_device()
+    with _lib.held(None, _lib.IF_UPLOADED) as h:
+        d_h = h.put(hh, np.float32)
+        d_full = empty((rows, full), np.complex64)
+        _lib.call("caf_upfirdn", d_x2, rows, n_in, d_h, hh.size, up, down, d_full, None, full, stream=None)
+        d_y = empty((rows, n_out), np.complex64)
+        _lib.call("caf_copy_slices_to_matrix", d_full, rows * full, None, 1, n_pre_remove, full, n_out, rows, d_y, stream=None)
+    return d_y.reshape(n_out) if one_row else d_y
