@@ -648,6 +648,57 @@ CAF_EXPORT int32_t caf_crb_map(const caf_locate_desc* desc, const double* d_reco
 /* the launch geometry (points per workgroup, records per staged chunk) and the threshold of an unobservable point */
 CAF_EXPORT int32_t caf_crb_map_geometry(int32_t* points_per_workgroup, int32_t* records_per_chunk, double* singular_threshold);
 
+/* ---- Direct position determination (localizationRoutines.py: gridSearchCAF_direct, DPDMixin; caf_dpd.hip).  Added after ABI 1.10
+ * without a version bump, detected by symbol.  CAF surfaces are added up over the grids that caf_locate_grid searches, with no
+ * per-pair decision.  Record k = (s1, s2, v1, v2) (slots 0..11 of the 16 doubles; the rest are not read) comes with map k.  For a
+ * grid point p, in float64 with k_locate's operations, contraction off:
+ *   x = rho2 - rho1,  y = u2 - u1,  u_i = (p - s_i).v_i / rho_i,   a = (x - r0) inv_dr,  b = (y - d0) inv_dd.
+ * The lookup is in range when 0 <= a <= nd - 1 and 0 <= b <= nf - 1 (a NaN coordinate is out of range).  In range:
+ * i = min(floor(a), nd - 2), t = a - i, j and s from b in the same way, and with lerp(p, q, t) = fma(t, q - p, p)
+ *   value = lerp(lerp(S[i, j], S[i, j + 1], s), lerp(S[i + 1, j], S[i + 1, j + 1], s), t),   S[i, j] = d_surface[i stride_d + j stride_f];
+ * out of range: value = fill, and the record is no hit.  score[p] = sum_k w_k value_k, in the order of k, one fma per record.
+ * A NaN among the four corners of the touched cell makes the score NaN.  The library knows nothing of seconds, hertz or carriers.
+ * desc->grid.mode: CAF_LOCATE_TD maps have nf == 1 and nd >= 2 (velocities, d0 and inv_dd are never read, one lerp),
+ * CAF_LOCATE_FD maps nd == 1 and nf >= 2, CAF_LOCATE_TDFD maps nd >= 2 and nf >= 2.  Every load lies inside [0, nd) x [0, nf) of
+ * its map for every input; offsets are 64-bit, strides may be negative. */
+typedef struct caf_dpd_map {
+    const float* d_surface; /* DEVICE: the element (0, 0) of the map, float32                                            */
+    int32_t nd, nf;         /* entries along a (range difference) and along b (range-rate difference)                   */
+    int64_t stride_d;       /* in elements: rows of a (S, F) surface, of the (F, S) transpose and windows are all views */
+    int64_t stride_f;
+    double r0, inv_dr;      /* a = (x - r0) inv_dr                                                                      */
+    double d0, inv_dd;      /* b = (y - d0) inv_dd                                                                      */
+    double w;               /* the weight of the map in the score                                                       */
+    double fill;            /* the value of a lookup out of range                                                       */
+} caf_dpd_map;
+/* grid: source, n and the tables as for caf_locate_grid; grid.cost_f32 chooses the type of d_score.  d_records, K, d_set_starts
+ * (clamped), B as for caf_locate_grid: B score grids over the same points in one launch.  h_maps: HOST, K maps, checked before
+ * anything touches a device (sizes for the mode; finite r0, inv_dr, d0, inv_dd, w, fill; no NULL surface; no zero stride of an
+ * axis with more than one entry; K <= 2^20), then copied into a staging block the library keeps, uploaded into a pooled block on
+ * desc->stream and given back to the pool when an event behind the launch has completed: the caller's array is free again on
+ * return.  Outputs, each optional: d_score (B, N) float64, or float32 (the float64 score rounded once); d_hits (B, N) int32,
+ * the records of the set that were in range; d_max_val (B) float64 and d_max_idx (B) int64, the maximum of each set's scores
+ * and the FIRST index that has it.  NaN never wins; a set with nothing but NaN reports (NaN, -1).  No atomics: a set gives the
+ * same bits alone and anywhere in a batch, for any choice of outputs, on every run.  All device work of the call is queued on
+ * desc->stream and nowhere else, and the call does not wait for it. */
+typedef struct caf_dpd_desc {
+    caf_locate_desc grid;
+    const double* d_records;     /* DEVICE (K, 16) */
+    int64_t K;
+    const int64_t* d_set_starts; /* DEVICE (B + 1), or NULL: B = 1 */
+    int32_t B;
+    int32_t reserved;
+    const caf_dpd_map* h_maps;   /* HOST (K) */
+    void* d_score;
+    int32_t* d_hits;
+    double* d_max_val;
+    int64_t* d_max_idx;
+    void* stream;
+} caf_dpd_desc;
+CAF_EXPORT int32_t caf_dpd_grid(const caf_dpd_desc* desc);
+/* the launch geometry: points per workgroup and records per staged chunk (the sizes at which the kernel changes path) */
+CAF_EXPORT int32_t caf_dpd_geometry(int32_t* points_per_workgroup, int32_t* records_per_chunk);
+
 /* ---- Lines of position on an oblate spheroid (hyperboloidRoutines.py: Hyperboloid.intersectOblateSpheroid; sphereRoutines.py:
  * Sphere.intersectOblateSpheroid).  Added after ABI 1.10 without a version bump, detected by symbol.  Everything is float64,
  * contraction off, no atomics.  A job is 16 doubles, mu(3) e0(3) e1(3) e2(3) a c p_min p_max, and describes the family of circles

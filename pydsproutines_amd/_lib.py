@@ -159,6 +159,39 @@ class CafLocateDesc(ct.Structure):
     ]
 
 
+class CafDpdMap(ct.Structure):
+    _fields_ = [
+        ("d_surface", ct.c_void_p),
+        ("nd", ct.c_int32),
+        ("nf", ct.c_int32),
+        ("stride_d", ct.c_int64),
+        ("stride_f", ct.c_int64),
+        ("r0", ct.c_double),
+        ("inv_dr", ct.c_double),
+        ("d0", ct.c_double),
+        ("inv_dd", ct.c_double),
+        ("w", ct.c_double),
+        ("fill", ct.c_double),
+    ]
+
+
+class CafDpdDesc(ct.Structure):
+    _fields_ = [
+        ("grid", CafLocateDesc),
+        ("d_records", ct.c_void_p),
+        ("K", ct.c_int64),
+        ("d_set_starts", ct.c_void_p),
+        ("B", ct.c_int32),
+        ("reserved", ct.c_int32),
+        ("h_maps", ct.c_void_p),
+        ("d_score", ct.c_void_p),
+        ("d_hits", ct.c_void_p),
+        ("d_max_val", ct.c_void_p),
+        ("d_max_idx", ct.c_void_p),
+        ("stream", ct.c_void_p),
+    ]
+
+
 class CafLopDesc(ct.Structure):
     _fields_ = [
         ("kind", ct.c_int32),
@@ -383,6 +416,8 @@ _SIGNATURES = {
     "caf_locate_rtt_geometry": [ct.POINTER(_I32), ct.POINTER(_I32)],
     "caf_crb_map": [ct.POINTER(CafLocateDesc), _P, _I64, _P, _I32, _I32, ct.POINTER(ct.c_double), _P, _P, _P, _P, _P, _P, _P, _P],
     "caf_crb_map_geometry": [ct.POINTER(_I32), ct.POINTER(_I32), ct.POINTER(ct.c_double)],
+    "caf_dpd_grid": [ct.POINTER(CafDpdDesc)],
+    "caf_dpd_geometry": [ct.POINTER(_I32), ct.POINTER(_I32)],
     "caf_lop_points": [ct.POINTER(CafLopDesc), _P, _I64, _P, _P, _P, _P, _P, _P, _P],
     "caf_lop_range": [ct.POINTER(CafLopDesc), _P, _I64, _P, _P, _P],
     "caf_lop_geometry": [ct.POINTER(_I32)] * 4,

@@ -18,11 +18,12 @@
 // slice fit the 160 KiB of LDS.  No atomics; the order of an output's sum depends on (t_m, w) alone, so a row gives the same
 // bits alone, anywhere in a batch, for every T, on every run.  Every load is checked against L_r; every element of d_y up to
 // out_pitch is written.
-// The rows' records (host arrays, checked here first) ride the call's stream: a pinned staging block, hipMemcpyAsync into a
-// pooled device block, the launch, an event.  Both blocks stay with their lane until that event has completed -- asked, never
-// waited for, by the calls that follow -- and only then does the device block go back to the pool: stream order, with no
-// synchronisation on either the null stream or a caller's.
+// The rows' records (host arrays, checked here first) ride the call's stream (caf_lane.h): a pinned staging block,
+// hipMemcpyAsync into a pooled device block, the launch, an event.  Both blocks stay with their lane until that event has
+// completed -- asked, never waited for, by the calls that follow -- and only then does the device block go back to the pool:
+// stream order, with no synchronisation on either the null stream or a caller's.
 #include "caf_internal.h"
+#include "caf_lane.h"
 #include "caf_phase.h"
 
 #include <cmath>
@@ -39,7 +40,6 @@ namespace {
 constexpr int RS_THREADS = 256;
 constexpr int RS_MAX_TILE = 1024;
 constexpr int64_t RS_LDS = 160 * 1024;
-constexpr int RS_MAX_LANES = 32;
 
 struct RsRow {
     double nu, t0, step;
@@ -149,95 +149,6 @@ bool rs_debug() {
     return e && e[0] == '1';
 }
 
-// ---- the rows' records on their way to the device and back to the pool ------------------------------------------------------
-struct RsLane {
-    int dev = 0;
-    void* pinned = nullptr;
-    int64_t cap = 0;
-    hipEvent_t ev = nullptr;
-    void* d_rows = nullptr;  // the pooled block of the call in flight
-    bool busy = false;
-};
-std::mutex g_rs_mu;
-std::vector<RsLane*> g_rs_lanes;  // (kept for the life of the process)
-
-// caller holds g_rs_mu: a lane whose event has completed gives its device block back and is idle again
-void rs_settle(RsLane* l, bool wait) {
-    if (!l->busy || !l->d_rows) return;
-    if (wait) {
-        (void)hipEventSynchronize(l->ev);
-    } else if (hipEventQuery(l->ev) != hipSuccess) {
-        (void)hipGetLastError();  // (hipErrorNotReady is the answer, not a failure)
-        return;
-    }
-    (void)pool_free(l->d_rows);
-    l->d_rows = nullptr;
-    l->busy = false;
-}
-
-int rs_lane_acquire(int dev, int64_t bytes, RsLane** out) {
-    std::lock_guard<std::mutex> lk(g_rs_mu);
-    RsLane* idle = nullptr;
-    int mine = 0;
-    for (RsLane* l : g_rs_lanes) {
-        if (l->dev != dev) continue;
-        ++mine;
-        rs_settle(l, false);
-        if (!l->busy && (!idle || (idle->cap < bytes && l->cap > idle->cap))) idle = l;
-    }
-    if (!idle && mine >= RS_MAX_LANES) {  // that many calls in flight: wait for the oldest
-        for (RsLane* l : g_rs_lanes)
-            if (l->dev == dev && l->d_rows) {
-                rs_settle(l, true);
-                idle = l;
-                break;
-            }
-    }
-    if (!idle) {
-        idle = new RsLane;
-        idle->dev = dev;
-        if (hipEventCreateWithFlags(&idle->ev, hipEventDisableTiming) != hipSuccess) {
-            (void)hipGetLastError();
-            delete idle;
-            set_error("caf_resample_rows: hipEventCreate failed");
-            return CAF_ERR_HIP;
-        }
-        g_rs_lanes.push_back(idle);
-    }
-    if (idle->cap < bytes) {
-        if (idle->pinned) (void)hipHostFree(idle->pinned);
-        idle->pinned = nullptr, idle->cap = 0;
-        int64_t c = 4096;
-        while (c < bytes) c *= 2;
-        const hipError_t e = hipHostMalloc(&idle->pinned, (size_t)c, hipHostMallocDefault);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            idle->pinned = nullptr;
-            set_error(std::string("caf_resample_rows: hipHostMalloc: ") + hipGetErrorString(e));
-            return CAF_ERR_NOMEM;
-        }
-        idle->cap = c;
-    }
-    idle->busy = true;  // (taken: no other thread fills it; d_rows is set once the block exists)
-    *out = idle;
-    return CAF_OK;
-}
-
-// the call failed before its event was recorded: nothing of it may still run when the blocks go back
-void rs_lane_abandon(RsLane* l, void* d_rows, hipStream_t st) {
-    (void)hipStreamSynchronize(st);
-    (void)hipGetLastError();
-    if (d_rows) (void)pool_free(d_rows);
-    std::lock_guard<std::mutex> lk(g_rs_mu);
-    l->busy = false;
-}
-
-// the event is on the stream: from here on the lane settles by it
-void rs_lane_in_flight(RsLane* l, void* d_rows) {
-    std::lock_guard<std::mutex> lk(g_rs_mu);
-    l->d_rows = d_rows;
-}
-
 }  // namespace
 
 }  // namespace caf
@@ -287,8 +198,8 @@ int32_t caf_resample_rows(const caf_resample_desc* desc) {
     CAF_HIP_TRY(hipGetDevice(&dev));
     if (const int rc = allow_dynamic_lds(reinterpret_cast<const void*>(k_resample), (size_t)lds)) return rc;
     const int64_t bytes = rows * (int64_t)sizeof(RsRow);
-    RsLane* lane = nullptr;
-    if (const int rc = rs_lane_acquire(dev, bytes, &lane)) return rc;
+    Lane* lane = nullptr;
+    if (const int rc = lane_acquire("caf_resample_rows", dev, bytes, &lane)) return rc;
     RsRow* h = (RsRow*)lane->pinned;
     for (int64_t r = 0; r < rows; ++r) {
         const double w = desc->h_width[r];
@@ -299,7 +210,7 @@ int32_t caf_resample_rows(const caf_resample_desc* desc) {
     }
     void* d_rows = nullptr;
     if (const int rc = pool_alloc(&d_rows, bytes, st == nullptr)) {
-        rs_lane_abandon(lane, nullptr, st);
+        lane_abandon(lane, nullptr, st);
         return rc;
     }
     RsArgs a{};
@@ -314,11 +225,11 @@ int32_t caf_resample_rows(const caf_resample_desc* desc) {
     if (e == hipSuccess) e = hipEventRecord(lane->ev, st);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        rs_lane_abandon(lane, d_rows, st);
+        lane_abandon(lane, d_rows, st);
         set_error(std::string("caf_resample_rows: ") + hipGetErrorString(e));
         return CAF_ERR_HIP;
     }
-    rs_lane_in_flight(lane, d_rows);
+    lane_in_flight(lane, d_rows);
     if (rs_debug())
         std::fprintf(stderr, "[caf resample] rows=%lld tile=%d threads=%d lds=%lld support=%d\n", (long long)rows, T, RS_THREADS,
                      (long long)lds, rs_support((int)H, max_width));

@@ -30,6 +30,13 @@ of the sheet's (or the sphere's) parameter on which the curve exists, ``caf_lop_
 ends by default, and the host stitches the ordered polyline.  The small range, Doppler, gradient and tangent-plane helpers of the
 reference are host NumPy, as there.
 
+Direct position determination (``CAFMap``, ``cafMap``, ``gridSearchCAF_direct``, ``DPDMixin``): the CAF surfaces themselves are
+added up over the grid instead of one peak per sensor pair.  For every grid point ``caf_dpd_grid`` (csrc/caf_dpd.hip) forms the
+range difference and the range-rate difference of each pair as the searches above do, looks the pair's float32 surface up there by
+bilinear interpolation in float64 and sums the weighted values in the order of the maps; the emitter is the largest score.  No
+per-pair decision is taken and no sigma is guessed.  Not provided: nearest-neighbour lookup, non-linear combining such as
+-log(1 - QF^2) (transform the surface first), non-uniform bin axes, and LDS tiling of the surfaces.
+
 Not provided: ``plot``, ``SatellitePairTDFDMixin`` (needs an orbit propagator: skyfield and sgp4), ``hyperbolaGradDesc`` and
 ``generateHyperbolaXY`` (they step along the curve with scipy.optimize; the closed form of hyperboloidRoutines.py supersedes them),
 and the blind RTT bound as a device map.  There is no CPU path: without a GPU every search raises RuntimeError (argument checks
@@ -37,6 +44,7 @@ come first).  The CRB functions are host NumPy, as in the reference; ``crbMap`` 
 every grid point on the device (crbRoutines.py).
 """
 
+import ctypes as ct
 from enum import Enum
 
 import numpy as np
@@ -52,7 +60,8 @@ __all__ = ["gridSearchTDOA", "gridSearchFDOA", "gridSearchTDOA_direct", "gridSea
            "LatLonGridLocalizerBlindRTT", "locate_rtt_geometry", "WGS84Coefficients", "get_wgs84_tangent_plane_normal",
            "get_wgs84_tangent_plane_north_east", "calculateRangeRate", "calculateDoppler", "rangeOfArrival", "rangeDifferenceOfArrival",
            "rangeOfArrivalGradient", "hyperboloidGradient", "hyperbolaTangentXY", "removeDownlinkRangeDiff", "removeDownlinkDopplerDiff",
-           "linesOfPosition", "rangeCircles", "LinesOfPosition"]
+           "linesOfPosition", "rangeCircles", "LinesOfPosition", "CAFMap", "cafMap", "gridSearchCAF_direct", "DPDMixin", "GridLocalizerDPD",
+           "LatLonGridLocalizerDPD", "dpd_geometry"]
 
 LIGHTSPD = 299792458.0
 WGS84_A = 6378137.0            # the two defining constants of WGS84: semi-major axis (m) ...
@@ -798,6 +807,219 @@ class LatLonGridLocalizerBlindRTT(BlindRTTMixin, LatLonGridLocalizer):
 
 class LatLonGridLocalizerTDFD(TDFDMixin, LatLonGridLocalizer):
     pass
+
+
+# ---- direct position determination: CAF surfaces over the grid (csrc/caf_dpd.hip) --------------------------------------------------
+def dpd_geometry():
+    """(points per workgroup, records per staged chunk) of the DPD kernel: the sizes at which it changes path."""
+    return _lib.query("caf_dpd_geometry")
+
+
+def _vec3(a, name):
+    a = np.asarray(a, dtype=np.float64).reshape(-1)
+    if a.size != 3 or not np.all(np.isfinite(a)):
+        raise ValueError("%s is one finite vector of length 3." % name)
+    return a
+
+
+class CAFMap:
+    """One sensor pair's surface and where it lies: entry (i, j) of ``surface`` is the value at the range difference
+    r0 + i dr (m, |p - s2| - |p - s1|) and the range-rate difference d0 + j dd (m/s, u2 - u1 with u = (p - s).v / |p - s|).
+    surface: a float32 DeviceArray view, 2-D (nd, nf) for a TDFD map (v1, v2 required), 1-D for a TD map (no velocities) or an FD
+    map (with velocities).  ``shape`` and ``strides`` (in elements) describe a window or a transpose whose entry (0, 0) is the
+    first element of ``surface``: shape=(nd, nf), strides=(stride_d, stride_f).  A lookup outside the map counts ``fill``."""
+
+    def __init__(self, surface, r0, dr, d0, dd, s1, s2, v1=None, v2=None, weight=1.0, fill=0.0, shape=None, strides=None):
+        if not isinstance(surface, DeviceArray):
+            raise TypeError("surface must be a device array (pydsproutines_amd.devarray.DeviceArray).")
+        if surface.dtype != np.dtype(np.float32):
+            raise TypeError("surface must be float32, found %s." % surface.dtype)
+        if (v1 is None) != (v2 is None):
+            raise ValueError("v1 and v2 are given together or not at all.")
+        moving = v1 is not None
+        if shape is None:
+            if surface.ndim == 2:
+                shape, dflt = surface.shape, (surface.shape[1], 1)
+            elif surface.ndim == 1:
+                shape, dflt = ((1, surface.shape[0]), (0, 1)) if moving else ((surface.shape[0], 1), (1, 0))
+            else:
+                raise ValueError("surface is a 1-D or 2-D view, found %d dimensions." % surface.ndim)
+            strides = dflt if strides is None else strides
+        elif strides is None:
+            raise ValueError("a shape needs its strides (in elements).")
+        nd, nf = (int(v) for v in shape)
+        sd, sf = (int(v) for v in strides)
+        if nd < 1 or nf < 1 or nd >= 2 ** 31 or nf >= 2 ** 31:
+            raise ValueError("the map needs 1 <= nd, nf < 2^31.")
+        if nd >= 2 and nf >= 2:
+            self.mode = "tdfd"
+        elif nd >= 2:
+            self.mode = "td"
+        elif nf >= 2:
+            self.mode = "fd"
+        else:
+            raise ValueError("a map of one entry has no axis to interpolate along.")
+        if (self.mode != "td") != moving:
+            raise ValueError("a %s map %s." % (self.mode.upper(), "needs v1 and v2" if not moving else "takes no velocities"))
+        if (nd > 1 and sd == 0) or (nf > 1 and sf == 0):
+            raise ValueError("the stride of an axis with more than one entry must not be 0.")
+        ends = [(nd - 1) * sd * (sd < 0) + (nf - 1) * sf * (sf < 0), (nd - 1) * sd * (sd > 0) + (nf - 1) * sf * (sf > 0)]
+        if ends[0] < 0 or ends[1] >= surface.size:
+            raise ValueError("the window of shape %r and strides %r does not fit the %d elements of surface." % ((nd, nf), (sd, sf), surface.size))
+        num = dict(r0=r0, dr=dr, d0=d0, dd=dd, weight=weight, fill=fill)
+        for k, v in num.items():
+            num[k] = float(v)
+            if not np.isfinite(num[k]):
+                raise ValueError("%s must be finite." % k)
+        if (nd > 1 and num["dr"] == 0.0) or (nf > 1 and num["dd"] == 0.0):
+            raise ValueError("the step of an axis with more than one entry must not be 0.")
+        self.surface, self.nd, self.nf, self.stride_d, self.stride_f = surface, nd, nf, sd, sf
+        self.r0, self.dr, self.d0, self.dd, self.weight, self.fill = (num[k] for k in ("r0", "dr", "d0", "dd", "weight", "fill"))
+        self.inv_dr = 1.0 / self.dr if nd > 1 else 0.0
+        self.inv_dd = 1.0 / self.dd if nf > 1 else 0.0
+        self.s1, self.s2 = _vec3(s1, "s1"), _vec3(s2, "s2")
+        self.v1, self.v2 = (_vec3(v1, "v1"), _vec3(v2, "v2")) if moving else (np.zeros(3), np.zeros(3))
+
+
+def cafMap(surface2d, shift_start, fs, bins, grid, fc, s1, s2, v1, v2, template_start=0, weight=1.0, fill=0.0, major="delay"):
+    """The CAFMap of one CAFPlan surface: ``res.surface[t]`` (S, F) with major="delay", ``res.surface_t[t]`` (F, S) with
+    major="freq".  Row s of the delay axis is the sample shift_start + s of the received signal; with the template cut at
+    template_start from sensor 1's signal that is a TDOA of (shift_start + s - template_start) / fs = (|p - s2| - |p - s1|) / c.
+    Bin k is an FDOA of k fs / grid, and FDOA / fc c = u2 - u1, the range-rate difference of the map.  ``bins`` must be
+    uniformly spaced (two or more); s1 is the template's sensor."""
+    if major not in ("delay", "freq"):
+        raise ValueError("major is 'delay' ((S, F), res.surface) or 'freq' ((F, S), res.surface_t).")
+    if not isinstance(surface2d, DeviceArray) or surface2d.ndim != 2:
+        raise TypeError("surface2d must be a 2-D device array: one (S, F) or (F, S) surface of a CAFPlan result.")
+    bins = np.asarray(bins, dtype=np.float64).reshape(-1)
+    ns, nb = surface2d.shape if major == "delay" else surface2d.shape[::-1]
+    if bins.size != nb:
+        raise ValueError("the surface has %d bins, bins has %d entries." % (nb, bins.size))
+    if bins.size < 2 or bins[1] == bins[0] or np.any(np.diff(bins) != bins[1] - bins[0]):
+        raise ValueError("bins must be uniformly spaced, two or more (a non-uniform bin axis is not provided).")
+    fs, fc, grid = float(fs), float(fc), float(grid)
+    if not (fs > 0 and fc > 0 and grid > 0):
+        raise ValueError("fs, fc and grid must be positive.")
+    per_bin = fs / grid / fc * LIGHTSPD
+    strides = (nb, 1) if major == "delay" else (1, ns)
+    return CAFMap(surface2d, (float(shift_start) - float(template_start)) / fs * LIGHTSPD, LIGHTSPD / fs, bins[0] * per_bin,
+                  (bins[1] - bins[0]) * per_bin, s1, s2, v1, v2, weight=weight, fill=fill, shape=(ns, nb), strides=strides)
+
+
+def _is_map_batch(maps):
+    """one set: a sequence of CAFMap; B sets: a sequence of such sequences"""
+    return len(maps) > 0 and not isinstance(maps[0], CAFMap)
+
+
+def _dpd(source, sets, score=None, hits=False, argmax=False):
+    """One launch of caf_dpd_grid on the null stream.  sets: a list of lists of CAFMap of one mode.  score: None, np.float64 or
+    np.float32.  Returns (d_score (B, N), d_hits (B, N) int32, d_max_val (B,), d_max_idx (B,)), None for what was not asked."""
+    sets = [list(s) for s in sets]
+    maps = [m for s in sets for m in s]
+    if not sets or any(len(s) < 1 for s in sets):
+        raise ValueError("every set needs at least one CAFMap.")
+    if not all(isinstance(m, CAFMap) for m in maps):
+        raise TypeError("maps holds CAFMap objects (a list of lists of them for a batch of sets).")
+    if len({m.mode for m in maps}) != 1:
+        raise ValueError("the maps of one call are all TD, all FD or all TDFD, found %s." % sorted({m.mode for m in maps}))
+    if len(sets) > 65535:
+        raise ValueError("at most 65535 sets of maps per call.")
+    if score is not None and np.dtype(score) not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise ValueError("the score grid is float64 or float32.")
+    k, b = len(maps), len(sets)
+    rec = np.zeros((k, _REC), np.float64)
+    h_maps = (_lib.CafDpdMap * k)()
+    for n, m in enumerate(maps):
+        rec[n, 0:3], rec[n, 3:6], rec[n, 6:9], rec[n, 9:12] = m.s1, m.s2, m.v1, m.v2
+        h_maps[n] = _lib.CafDpdMap(m.surface.ptr, m.nd, m.nf, m.stride_d, m.stride_f, m.r0, m.inv_dr, m.d0, m.inv_dd, m.weight, m.fill)
+    starts = np.concatenate(([0], np.cumsum([len(s) for s in sets]))).astype(np.int64)
+    _lib.require_device()
+    desc = _lib.CafDpdDesc()
+    desc.grid = source.desc(_MODES[maps[0].mode], score is not None and np.dtype(score) == np.dtype(np.float32))
+    with _lib.held(None, _lib.CALLER) as h:
+        d_rec = h.put(rec)
+        d_ss = h.put(starts) if b > 1 else None
+        d_score = empty((b, source.n), np.dtype(score)) if score is not None else None
+        d_hits = empty((b, source.n), np.int32) if hits else None
+        d_val = empty((b,), np.float64) if argmax else None
+        d_idx = empty((b,), np.int64) if argmax else None
+        desc.d_records, desc.K, desc.d_set_starts, desc.B = d_rec.ptr, k, d_ss.ptr if d_ss is not None else None, b
+        desc.h_maps = ct.addressof(h_maps)
+        for name, a in (("d_score", d_score), ("d_hits", d_hits), ("d_max_val", d_val), ("d_max_idx", d_idx)):
+            setattr(desc, name, a.ptr if a is not None else None)
+        desc.stream = None
+        _lib.call("caf_dpd_grid", desc)
+    return d_score, d_hits, d_val, d_idx
+
+
+def gridSearchCAF_direct(maps, gridmat, device=False, hits=False):
+    """The DPD score of every row of gridmat (N x 3), float64: sum over the maps of weight times the map's surface, bilinearly
+    interpolated at the range difference and range-rate difference that the row predicts for the map's sensor pair (``fill``
+    outside the map).  hits=True returns (score, hits) with the int32 count of maps that were in range at every row.
+    device=True returns DeviceArrays.  The emitter is the largest score."""
+    src = _Source.points(gridmat)
+    d_score, d_hits = _dpd(src, [maps], score=np.float64, hits=hits)[:2]
+    out = [d.reshape(src.n) for d in (d_score, d_hits) if d is not None]
+    out = out if device else [d.get() for d in out]
+    return tuple(out) if hits else out[0]
+
+
+class DPDMixin:
+    def _dpd_source(self):
+        if np.ndim(self.gridmat) != 2 or np.shape(self.gridmat)[1] != 3:
+            raise ValueError("Ensure gridmat has 3 columns.")
+        return self._source()
+
+    def run(self, maps, device=False):
+        """The DPD score of every grid point (length N, float64), as gridSearchCAF_direct; a list of B lists of maps gives
+        (B, N) in one launch.  device=True leaves the grid on the device (a DeviceArray)."""
+        batch = _is_map_batch(maps)
+        src = self._dpd_source()
+        d_score = _dpd(src, maps if batch else [maps], score=np.float64)[0]
+        d_score = d_score if batch else d_score.reshape(src.n)
+        return d_score if device else d_score.get()
+
+    def _dpd_locate(self, maps):
+        batch = _is_map_batch(maps)
+        src = self._dpd_source()
+        _, _, d_val, d_idx = _dpd(src, maps if batch else [maps], argmax=True)
+        idx, val = d_idx.get(), d_val.get()
+        pts = np.full((idx.size, 3), np.nan)
+        ok = idx >= 0
+        pts[ok] = src.point(idx[ok])
+        return batch, pts, val, idx
+
+    def locate(self, maps):
+        """The arg max of run() without its grid: (point, value, index).  With a list of B lists of maps all B sets are searched
+        in one launch: (B, 3), (B,), (B,).  The first index wins a tie; NaN scores never win; nothing but NaN gives
+        (NaN point, NaN, -1)."""
+        batch, pts, val, idx = self._dpd_locate(maps)
+        return (pts, val, idx) if batch else (pts[0], float(val[0]), int(idx[0]))
+
+
+class GridLocalizerDPD(DPDMixin, GridLocalizer):
+    @classmethod
+    def fromXYMesh(cls, xrange, yrange, z=0.0):
+        """A flat mesh p(i, j) = (xrange[j], yrange[i], z), flat index i len(xrange) + j, searched from its two axes: the N x 3
+        matrix (kept as gridmat) is never uploaded."""
+        src = _Source.xy(xrange, yrange, z)
+        self = cls(src.matrix(), xrange, yrange)
+        self._src, self._src_of = src, self.gridmat
+        return self
+
+
+class LatLonGridLocalizerDPD(DPDMixin, LatLonGridLocalizer):
+    def locate(self, maps):
+        """DPDMixin.locate and where that is: (point, value, index, lat, lon); NaN where nothing was found."""
+        batch, pts, val, idx = self._dpd_locate(maps)
+        nlon = np.asarray(self.lonlist).size
+        ok = idx >= 0
+        lat, lon = np.full(idx.size, np.nan), np.full(idx.size, np.nan)
+        lat[ok] = np.asarray(self.latlist, dtype=np.float64)[idx[ok] // nlon]
+        lon[ok] = np.asarray(self.lonlist, dtype=np.float64)[idx[ok] % nlon]
+        if batch:
+            return pts, val, idx, lat, lon
+        return pts[0], float(val[0]), int(idx[0]), float(lat[0]), float(lon[0])
 
 
 # ---- the reference's small helpers (host NumPy) ------------------------------------------------------------------------------------
