@@ -699,6 +699,63 @@ CAF_EXPORT int32_t caf_dpd_grid(const caf_dpd_desc* desc);
 /* the launch geometry: points per workgroup and records per staged chunk (the sizes at which the kernel changes path) */
 CAF_EXPORT int32_t caf_dpd_geometry(int32_t* points_per_workgroup, int32_t* records_per_chunk);
 
+/* ---- CFAR detection on CAF surfaces (xcorrRoutines.py: cfarDetect; caf_cfar.hip).  Added after ABI 1.10 without a version bump,
+ * detected by symbol.  For the cell (i, j) of a map, v = S[i, j] = d_surface[i stride_d + j stride_f], Hd = gd + td, Hf = gf + tf:
+ *   ring: the cells (i + a, j + b) with |a| <= Hd and |b| <= Hf, not both |a| <= gd and |b| <= gf, 0 <= i + a < nd (the delay
+ *     axis never wraps), the column in range (with wrap_f it is taken modulo nf, and 2 Hf + 1 <= nf is required), the value finite.
+ *     R = the float64 sum of the ring in a fixed order, n = its size.
+ *   noise: CAF_CFAR_CA: R / n, one float64 division (NaN for n = 0).  CAF_CFAR_GO / _SO: half A is the ring cells whose offset on
+ *     split_axis is negative, half B those where it is positive (offset 0 is in neither); the larger (GO) or smaller (SO) of
+ *     R_A / n_A and R_B / n_B over the halves that are not empty (NaN if both are), n = n_A + n_B.
+ *   a detection: v finite, n >= min_cells, v >= floor, (double) v > alpha * noise (one product), and v the local maximum of its
+ *     (2 md + 1) x (2 mf + 1) window under the same range and wrap rules: v > q for a neighbour q that precedes (i, j) in row-major
+ *     (i, j) order, v >= q for one that follows, non-finite neighbours skipped -- a plateau gives its first cell exactly once.
+ *   di: with p = S[i - 1, j], q = S[i + 1, j] as doubles: 0 if either is out of range or non-finite or den = (p - 2 v) + q >= 0,
+ *     else (0.5 (p - q)) / den clamped to [-0.5, 0.5] and rounded to float32 once; dj alike along frequency, honouring wrap_f.
+ *   noise = the float64 noise rounded once, ratio = (double) v / noise rounded once, cells = n.
+ * Map b's detections go to d_det[b, 0 .. min(count, cap)) in row-major (i, j) order, d_count[b] is the full count, records past
+ * the count are not written.  d_noise, where given, gets every cell's noise, NaN where n < min_cells.  No atomics: a map gives
+ * the same bits alone and anywhere in a batch, for any choice of outputs, on every run. */
+#define CAF_CFAR_CA 0
+#define CAF_CFAR_GO 1
+#define CAF_CFAR_SO 2
+typedef struct caf_cfar_map {
+    const float* d_surface; /* DEVICE: the element (0, 0) of the map, float32                                            */
+    int32_t nd, nf;         /* delays and frequencies, each >= 1                                                        */
+    int64_t stride_d;       /* in elements, not 0 on an axis with more than one entry, may be negative: (S, F) surfaces, */
+    int64_t stride_f;       /* (F, S) rows of surface_t and windows of either are all views                             */
+    double alpha, floor;    /* finite, alpha > 0                                                                        */
+    float* d_noise;         /* DEVICE (nd, nf) compact row-major float32, or NULL                                       */
+} caf_cfar_map;
+typedef struct caf_cfar_det {
+    int32_t i, j;
+    float value, noise, ratio, di, dj;
+    int32_t cells;
+} caf_cfar_det; /* 32 bytes */
+/* h_maps: HOST, B maps (1 <= B <= 2^20, sizes may differ), checked before anything touches a device, then staged, uploaded into a
+ * pooled block on desc->stream and given back to the pool when an event behind the launches has completed: the caller's array is
+ * free again on return.  Limits: gd, gf, td, tf >= 0; Hd, Hf <= 32; td + tf >= 1; 0 <= md <= Hd, 0 <= mf <= Hf, md + mf >= 1;
+ * GO and SO need a half width >= 1 on split_axis; min_cells >= 0; cap >= 0, and d_det with a cap above 0; at most 2^31 - 1 tiles
+ * of 32 x 32 cells per call.  d_count may be NULL.  All device work of the call is queued on desc->stream and nowhere else; the
+ * call waits for nothing and reads no count back. */
+typedef struct caf_cfar_desc {
+    const caf_cfar_map* h_maps; /* HOST (B) */
+    int32_t B;
+    int32_t gd, gf, td, tf;     /* guard and training half widths */
+    int32_t md, mf;             /* half widths of the local-maximum window */
+    int32_t mode;               /* CAF_CFAR_CA, _GO, _SO */
+    int32_t split_axis;         /* 0 = delay, 1 = frequency; read for GO and SO */
+    int32_t wrap_f, min_cells;
+    caf_cfar_det* d_det;        /* DEVICE (B, cap) */
+    int64_t cap;
+    int64_t* d_count;           /* DEVICE (B): the true count, also beyond cap */
+    void* stream;
+} caf_cfar_desc;
+CAF_EXPORT int32_t caf_cfar_surface(const caf_cfar_desc* desc);
+/* the launch geometry at half widths (Hd, Hf): the cells of a tile on each axis (the sizes at which the kernel changes path), the
+ * threads of a workgroup and the most LDS it takes, in bytes (GO / SO split on frequency; CA and a split on delay take less) */
+CAF_EXPORT int32_t caf_cfar_geometry(int32_t Hd, int32_t Hf, int32_t* tile_d, int32_t* tile_f, int32_t* threads, int64_t* lds_bytes);
+
 /* ---- Lines of position on an oblate spheroid (hyperboloidRoutines.py: Hyperboloid.intersectOblateSpheroid; sphereRoutines.py:
  * Sphere.intersectOblateSpheroid).  Added after ABI 1.10 without a version bump, detected by symbol.  Everything is float64,
  * contraction off, no atomics.  A job is 16 doubles, mu(3) e0(3) e1(3) e2(3) a c p_min p_max, and describes the family of circles

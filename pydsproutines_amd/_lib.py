@@ -192,6 +192,53 @@ class CafDpdDesc(ct.Structure):
     ]
 
 
+class CafCfarMap(ct.Structure):
+    _fields_ = [
+        ("d_surface", ct.c_void_p),
+        ("nd", ct.c_int32),
+        ("nf", ct.c_int32),
+        ("stride_d", ct.c_int64),
+        ("stride_f", ct.c_int64),
+        ("alpha", ct.c_double),
+        ("floor", ct.c_double),
+        ("d_noise", ct.c_void_p),
+    ]
+
+
+class CafCfarDet(ct.Structure):
+    _fields_ = [
+        ("i", ct.c_int32),
+        ("j", ct.c_int32),
+        ("value", ct.c_float),
+        ("noise", ct.c_float),
+        ("ratio", ct.c_float),
+        ("di", ct.c_float),
+        ("dj", ct.c_float),
+        ("cells", ct.c_int32),
+    ]
+
+
+class CafCfarDesc(ct.Structure):
+    _fields_ = [
+        ("h_maps", ct.c_void_p),
+        ("B", ct.c_int32),
+        ("gd", ct.c_int32),
+        ("gf", ct.c_int32),
+        ("td", ct.c_int32),
+        ("tf", ct.c_int32),
+        ("md", ct.c_int32),
+        ("mf", ct.c_int32),
+        ("mode", ct.c_int32),
+        ("split_axis", ct.c_int32),
+        ("wrap_f", ct.c_int32),
+        ("min_cells", ct.c_int32),
+        ("d_det", ct.c_void_p),
+        ("cap", ct.c_int64),
+        ("d_count", ct.c_void_p),
+        ("stream", ct.c_void_p),
+    ]
+
+
 class CafLopDesc(ct.Structure):
     _fields_ = [
         ("kind", ct.c_int32),
@@ -310,6 +357,9 @@ CAF_LOCATE_MESH_XY = 2
 CAF_LOCATE_TD = 1
 CAF_LOCATE_FD = 2
 CAF_LOCATE_TDFD = 3
+CAF_CFAR_CA = 0
+CAF_CFAR_GO = 1
+CAF_CFAR_SO = 2
 CAF_CRB_RANGE, CAF_CRB_RANGE_SUM, CAF_CRB_RANGE_DIFF, CAF_CRB_RATE_DIFF, CAF_CRB_AOA3D = 1, 2, 3, 4, 5
 CAF_CRB_FREE, CAF_CRB_FIXED, CAF_CRB_RADIAL, CAF_CRB_WGS84 = 0, 1, 2, 3
 CAF_LOP_HYPERBOLOID, CAF_LOP_SPHERE = 0, 1
@@ -418,6 +468,8 @@ _SIGNATURES = {
     "caf_crb_map_geometry": [ct.POINTER(_I32), ct.POINTER(_I32), ct.POINTER(ct.c_double)],
     "caf_dpd_grid": [ct.POINTER(CafDpdDesc)],
     "caf_dpd_geometry": [ct.POINTER(_I32), ct.POINTER(_I32)],
+    "caf_cfar_surface": [ct.POINTER(CafCfarDesc)],
+    "caf_cfar_geometry": [_I32, _I32, ct.POINTER(_I32), ct.POINTER(_I32), ct.POINTER(_I32), ct.POINTER(_I64)],
     "caf_lop_points": [ct.POINTER(CafLopDesc), _P, _I64, _P, _P, _P, _P, _P, _P, _P],
     "caf_lop_range": [ct.POINTER(CafLopDesc), _P, _I64, _P, _P, _P],
     "caf_lop_geometry": [ct.POINTER(_I32)] * 4,

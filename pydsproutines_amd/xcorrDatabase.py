@@ -166,6 +166,25 @@ class XcorrDB:
         tbl.insertMany(rows, commitNow=True)
         return len(rows)
 
+    def store_detections(self, tblname, det, freqs_hz, fs, time_sec=0, tidx=0, cutoutlen=0, shift_start=0, desc=None):
+        """Type 0: one row per detection of xcorrRoutines.cfarDetect (a CFAR_DET array), with the column meaning of store_peaks:
+        qf2 the cell's value, td its delay in seconds and fd its frequency in Hz, sub-cell offsets included."""
+        from .xcorrRoutines import detectionsToPeaks
+
+        tbl = self._tables[tblname]
+        if tbl.xctype != self.TYPE_PEAKVALUES:
+            raise ValueError("table %s is not of type 0" % tblname)
+        det = np.asarray(det)
+        fr = np.asarray(freqs_hz, dtype=np.float64)
+        td, fd = detectionsToPeaks(det, shift_start, fs, fr)
+        rows = [{"time_sec": int(time_sec), "tidx": int(tidx), "cutoutlen": int(cutoutlen), "td_scan_start": shift_start / fs,
+                 "td_scan_step": 1.0 / fs, "fd_scan_start": float(fr[0]), "fd_scan_numsteps": int(fr.size),
+                 "fd_scan_step": float(fr[1] - fr[0]) if fr.size > 1 else 0.0, "desc": desc, "qf2": float(det["value"][k]),
+                 "td": float(td[k]), "fd": float(fd[k])} for k in range(det.size)]
+        if rows:
+            tbl.insertMany(rows, commitNow=True)
+        return len(rows)
+
     def store_rows(self, tblname, result, fs, template=0, time_sec=0, tidx=0, cutoutlen=0, shift_start=0, fd_scan=(0.0, 0, 0.0),
                    desc=None):
         """Type 1: the per-delay traces of one template (qf2 as float64, freqIdx as uint32: the dtypes the schema

@@ -1263,3 +1263,166 @@ def computeGroupXcorrCZTcomplexity(m, L, n, K=1):
     """ref: xcorrRoutines.py:2100-2121."""
     Lc = next_fast_len(L + n)
     return K * m * 2 * Lc * np.log2(Lc)
+
+
+# ------------------------------------------------------------------------------------------
+# CFAR detection on CAF surfaces (csrc/caf_cfar.hip; DESIGN.md 4.27)
+# ------------------------------------------------------------------------------------------
+CFAR_DET = np.dtype([("i", "<i4"), ("j", "<i4"), ("value", "<f4"), ("noise", "<f4"), ("ratio", "<f4"), ("di", "<f4"), ("dj", "<f4"),
+                     ("cells", "<i4")])
+_CFAR_MODES = {"ca": _lib.CAF_CFAR_CA, "go": _lib.CAF_CFAR_GO, "so": _lib.CAF_CFAR_SO}
+
+
+class Detections:
+    """What cfarDetect returns.  det: a host structured array (CFAR_DET: i, j, value, noise, ratio, di, dj, cells) in row-major
+    (i, j) order, at most ``cap`` records; count: the number of detections, also beyond cap; truncated: count > cap; noise: the
+    (nd, nf) float32 noise map on the device, or None.  For a batch of maps each member is a list with one entry per map."""
+
+    __slots__ = ("det", "count", "truncated", "noise")
+
+    def __init__(self, det, count, truncated, noise):
+        self.det, self.count, self.truncated, self.noise = det, count, truncated, noise
+
+    def __iter__(self):
+        return iter((self.det, self.count, self.truncated, self.noise))
+
+    def __repr__(self):
+        return "Detections(count=%r, truncated=%r)" % (self.count, self.truncated)
+
+
+class CFARView:
+    """A (delay, frequency) view of a float32 device array for cfarDetect: entry (i, j) is element offset + i strides[0] +
+    j strides[1] of ``array`` (strides in elements, negative ones allowed): a window, a transpose, a flipped axis."""
+
+    def __init__(self, array, shape, strides, offset=0):
+        if not isinstance(array, DeviceArray):
+            raise TypeError("array must be a device array (pydsproutines_amd.devarray.DeviceArray).")
+        if array.dtype != np.dtype(np.float32):
+            raise TypeError("array must be float32, found %s." % array.dtype)
+        nd, nf = (int(v) for v in shape)
+        sd, sf = (int(v) for v in strides)
+        offset = int(offset)
+        if nd < 1 or nf < 1 or nd >= 2 ** 31 or nf >= 2 ** 31:
+            raise ValueError("a view needs 1 <= nd, nf < 2^31.")
+        if (nd > 1 and sd == 0) or (nf > 1 and sf == 0):
+            raise ValueError("the stride of an axis with more than one entry must not be 0.")
+        first = offset + (nd - 1) * sd * (sd < 0) + (nf - 1) * sf * (sf < 0)
+        last = offset + (nd - 1) * sd * (sd > 0) + (nf - 1) * sf * (sf > 0)
+        if first < 0 or last >= array.size:
+            raise ValueError("the view of shape %r, strides %r and offset %d does not fit the %d elements of array."
+                             % ((nd, nf), (sd, sf), offset, array.size))
+        self.array, self.nd, self.nf, self.stride_d, self.stride_f, self.offset = array, nd, nf, sd, sf, offset
+
+    @property
+    def ptr(self):
+        return self.array.ptr + 4 * self.offset
+
+
+def _cfar_views(surface, major):
+    """(the views of a call, whether the caller gave one map)"""
+    if major not in ("delay", "freq"):
+        raise ValueError("major is 'delay' ((S, F), res.surface) or 'freq' ((F, S), res.surface_t).")
+
+    def view(a):
+        if isinstance(a, CFARView):
+            return a
+        if not isinstance(a, DeviceArray):
+            raise TypeError("a surface is a device array (pydsproutines_amd.devarray.DeviceArray) or a CFARView.")
+        if a.ndim != 2:
+            raise ValueError("a map is a 2-D view, found %d dimensions." % a.ndim)
+        if major == "delay":
+            return CFARView(a, a.shape, (a.shape[1], 1))
+        return CFARView(a, a.shape[::-1], (1, a.shape[1]))
+
+    if isinstance(surface, (list, tuple)):
+        if not surface:
+            raise ValueError("an empty list of maps.")
+        return [view(a) for a in surface], False
+    if isinstance(surface, DeviceArray) and surface.ndim == 3:
+        if surface.shape[0] < 1:
+            raise ValueError("an empty batch of maps.")
+        return [view(surface[t]) for t in range(surface.shape[0])], False
+    return [view(surface)], True
+
+
+def _cfar_ring(guard, train):
+    (gd, gf), (td, tf) = (tuple(int(v) for v in guard), tuple(int(v) for v in train))
+    return (2 * (gd + td) + 1) * (2 * (gf + tf) + 1) - (2 * gd + 1) * (2 * gf + 1)
+
+
+def cfarAlpha(pfa, n):
+    """The cell-averaging CFAR constant n (pfa^(-1/n) - 1): a cell of exponentially distributed noise -- which QF^2 of noise
+    is -- exceeds alpha times the mean of n such cells with probability pfa."""
+    pfa, n = float(pfa), int(n)
+    if not 0.0 < pfa < 1.0 or n < 1:
+        raise ValueError("cfarAlpha needs 0 < pfa < 1 and n >= 1.")
+    return n * (pfa ** (-1.0 / n) - 1.0)
+
+
+def cfar_geometry(guard=(2, 2), train=(6, 6)):
+    """(tile_d, tile_f, threads, lds_bytes) of the CFAR kernel at these half widths: the cells of a workgroup's tile on each axis
+    (the sizes at which the kernel changes path), its threads and its LDS"""
+    return _lib.query("caf_cfar_geometry", int(guard[0]) + int(train[0]), int(guard[1]) + int(train[1]))
+
+
+def cfarDetect(surface, guard=(2, 2), train=(6, 6), nms=(1, 1), pfa=1e-6, alpha=None, floor=0.0, mode="ca", split_axis=0, wrap_f=False,
+               min_cells=None, cap=4096, noise=False, major="delay"):
+    """CFAR detection on QF^2 surfaces: the cells that exceed ``alpha`` times the mean of their ring of training cells and are the
+    first maximum of their (2 nms[0] + 1) x (2 nms[1] + 1) window (include/caf.h has the definition cell by cell).
+
+    surface: a float32 DeviceArray (S, F) -- one map --, (T, S, F) -- T maps --, or a list of 2-D DeviceArrays or CFARViews, whose
+    sizes may differ.  major="freq" reads every 2-D array as (F, S): the rows of ``res.surface_t``.  guard, train, nms: half
+    widths (delay, frequency).  alpha=None takes cfarAlpha(pfa, n) at the ring size n of an interior cell.  mode: "ca", or "go" /
+    "so" with the ring split on ``split_axis`` (0 delay, 1 frequency).  wrap_f: the frequency axis is circular.  min_cells: the
+    smallest ring a decision is taken from (default: half an interior ring, so the corners of a map decide nothing).  cap: records
+    kept per map.  noise=True also returns the noise maps.  The call runs on the null stream (caf_cfar_surface itself takes a stream
+    in its descriptor); the counts are read back once the launches are done.
+    Returns Detections(det, count, truncated, noise): for one map its values, for a batch a list per member."""
+    views, single = _cfar_views(surface, major)
+    if mode not in _CFAR_MODES:
+        raise ValueError("mode is 'ca', 'go' or 'so'.")
+    n_ring = _cfar_ring(guard, train)
+    if alpha is None:
+        alpha = cfarAlpha(pfa, n_ring) if n_ring >= 1 else 0.0  # (no ring: the library words the refusal)
+    if min_cells is None:
+        min_cells = max(1, n_ring // 2)
+    cap = int(cap)
+    nb = len(views)
+    h_maps = (_lib.CafCfarMap * nb)()
+    _lib.require_device()
+    d_noise = [empty((v.nd, v.nf), np.float32) for v in views] if noise else [None] * nb
+    for b, v in enumerate(views):
+        h_maps[b] = _lib.CafCfarMap(v.ptr, v.nd, v.nf, v.stride_d, v.stride_f, float(alpha), float(floor), d_noise[b].ptr if noise else None)
+    d_det = empty((nb, max(cap, 0), CFAR_DET.itemsize), np.uint8) if cap > 0 else None
+    d_count = empty((nb,), np.int64)
+    desc = _lib.CafCfarDesc()
+    desc.h_maps, desc.B = ct.addressof(h_maps), nb
+    desc.gd, desc.gf, desc.td, desc.tf = int(guard[0]), int(guard[1]), int(train[0]), int(train[1])
+    desc.md, desc.mf, desc.mode, desc.split_axis = int(nms[0]), int(nms[1]), _CFAR_MODES[mode], int(split_axis)
+    desc.wrap_f, desc.min_cells = int(bool(wrap_f)), int(min_cells)
+    desc.d_det, desc.cap, desc.d_count = (d_det.ptr if d_det is not None else None), cap, d_count.ptr
+    desc.stream = None
+    _lib.call("caf_cfar_surface", desc)
+    count = [int(c) for c in d_count.get()]
+    det = []
+    for b in range(nb):
+        k = min(count[b], cap)
+        det.append(d_det[b][:k].get().view(CFAR_DET).reshape(k) if k else np.zeros(0, CFAR_DET))
+    truncated = [c > cap for c in count]
+    if single:
+        return Detections(det[0], count[0], truncated[0], d_noise[0])
+    return Detections(det, count, truncated, d_noise if noise else None)
+
+
+def detectionsToPeaks(det, shift_start, fs, freqs_hz):
+    """(delays in seconds, frequencies in Hz) of a list of detections, sub-cell offsets included: row i of a surface is the
+    sample shift_start + i of the received signal, column j the frequency freqs_hz[j] (between two columns: linear)."""
+    det = np.asarray(det)
+    fr = np.asarray(freqs_hz, dtype=np.float64).reshape(-1)
+    if det.size and (det["j"].min() < 0 or det["j"].max() >= fr.size):
+        raise ValueError("freqs_hz has %d entries, the detections reach column %d." % (fr.size, int(det["j"].max())))
+    delays = (float(shift_start) + det["i"].astype(np.float64) + det["di"].astype(np.float64)) / float(fs)
+    j, dj = det["j"].astype(np.int64), det["dj"].astype(np.float64)
+    other = np.clip(j + np.where(dj < 0, -1, 1), 0, max(fr.size - 1, 0))  # (the column the offset leans towards; none beyond the ends)
+    freqs = fr[j] + np.abs(dj) * (fr[other] - fr[j]) if det.size else np.zeros(0)
+    return delays, freqs
