@@ -111,6 +111,43 @@ __device__ __forceinline__ void lds_rows16c(uint32_t m0, const float2 (&v)[16]) 
     lds_rows8<0, S, 2 * S, 3 * S, 4 * S, 5 * S, 6 * S, 7 * S>(m0 + FP_IM, v[0].y, v[1].y, v[2].y, v[3].y, v[4].y, v[5].y, v[6].y, v[7].y);
     lds_rows8<0, S, 2 * S, 3 * S, 4 * S, 5 * S, 6 * S, 7 * S>(m0 + FP_IM + 8 * S, v[8].y, v[9].y, v[10].y, v[11].y, v[12].y, v[13].y, v[14].y, v[15].y);
 }
+// four consecutive complex values (registers K .. K + 3 of exchange 1) -> their rows of both planes, in one statement: the
+// same bytes as lds_rows16c<FP_P1> writes for them, from the same two M0 bases per plane (m0 for rows 0 .. 7, m0 + 8 S for
+// rows 8 .. 15: M0 plus the immediate reaches 65 535 bytes).  M0 is written in the statement that uses it, as everywhere:
+// the compiler promises nothing about M0 between two statements of ours, so a group pays two scalar moves -- 8 per thread
+// and pass against 4 in lds_rows16c.  (Groups of two, 16 moves: C2 13.09 against 13.04 ms, profiles/r29.)
+template <int K>
+__device__ __forceinline__ void lds_rows4c_x1(uint32_t m0, const float2 (&v)[16]) {
+    constexpr int S = FP_P1, KB = K & 8, O = (K - KB) * S;
+    static_assert(K % 4 == 0 && K >= 0 && K < 16 && O + 3 * S + 256 <= 65536, "a group inside one half of a plane");
+    asm volatile(
+        "s_mov_b32 m0, %0\n\ts_nop 0\n\t"
+        "ds_write_addtid_b32 %2 offset:%10\n\tds_write_addtid_b32 %4 offset:%11\n\t"
+        "ds_write_addtid_b32 %6 offset:%12\n\tds_write_addtid_b32 %8 offset:%13\n\t"
+        "s_mov_b32 m0, %1\n\ts_nop 0\n\t"
+        "ds_write_addtid_b32 %3 offset:%10\n\tds_write_addtid_b32 %5 offset:%11\n\t"
+        "ds_write_addtid_b32 %7 offset:%12\n\tds_write_addtid_b32 %9 offset:%13"
+        :
+        : "s"(m0 + KB * S), "s"(m0 + FP_IM + KB * S), "v"(v[K].x), "v"(v[K].y), "v"(v[K + 1].x), "v"(v[K + 1].y), "v"(v[K + 2].x),
+          "v"(v[K + 2].y), "v"(v[K + 3].x), "v"(v[K + 3].y), "n"(O), "n"(O + S), "n"(O + 2 * S), "n"(O + 3 * S)
+        : "memory");
+}
+// The second half of pass 1, behind the barrier that protects the image: v[n1] *= w^n1 by the recurrence p <- p * wj, four
+// values at a time, each group's rows written as soon as it is twiddled (v[0] carries no twiddle: the first group goes out
+// after three of the fifteen steps).  A scheduling barrier on either side of every group of writes: left alone, the
+// compiler gathers all the multiplies in front of all the writes again.
+template <int K = 0>
+__device__ __forceinline__ void twiddle_write_x1(uint32_t m0, float2 (&v)[16], float2& p, const float2 wj) {
+#pragma unroll
+    for (int n1 = K < 1 ? 1 : K; n1 < K + 4; ++n1) {
+        if (n1 > 1) p = cmul(p, wj);
+        v[n1] = cmul(v[n1], p);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    lds_rows4c_x1<K>(m0, v);
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (K + 4 < 16) twiddle_write_x1<K + 4>(m0, v, p, wj);
+}
 // exchange 2: row n2 starts at fp_row2(n2)
 __device__ __forceinline__ void lds_rows16c_x2(uint32_t m0, const float2 (&v)[16]) {
     lds_rows8<fp_row2(0), fp_row2(1), fp_row2(2), fp_row2(3), fp_row2(4), fp_row2(5), fp_row2(6), fp_row2(7)>(
@@ -383,28 +420,25 @@ __device__ __forceinline__ void fused_item(float2* __restrict__ s_d, const float
         // ---- pass 1: P = X * Hc_h ; DFT16 over a ; twiddle w^n1 ; write A[n1][m2] ----
         // One butterfly at a time (32 live data registers).  pr is dead after this pass and is refilled
         // with the next hypothesis' products during pass 4, the low-pressure phase.
-        // The register-only part (DFT16 + twiddles) runs BEFORE the barrier that protects the LDS image, so it
-        // overlaps with slower waves still finishing pass 4 of the previous hypothesis.
+        // The butterfly itself runs BEFORE the barrier that protects the LDS image, so it overlaps with slower waves still
+        // finishing pass 4 of the previous hypothesis.  The twiddles run BEHIND it, four values at a time, each group's rows
+        // written as soon as it is twiddled: a row write holds its SIMD for 2 cycles and the LDS for 2, so with the twiddles
+        // in front of the barrier and a thread's 32 writes back to back the vector ALUs had nothing to issue while the LDS
+        // took the workgroup's 512 rows -- now the 116 multiply instructions issue in that time.  The same operations on the
+        // same values in the same order: the same bits.  One box, A/B/A/B (profiles/r29): C2 13.24 -> 13.04 ms, without
+        // the surface 8.75 -> 8.58; 4 / 8 / 12 of the values still twiddled in front of the barrier: 13.28 / 13.38 / 13.33.
         float2 v1[BPT][16];
 #pragma unroll
-        for (int j = 0; j < BPT; ++j) {
-#pragma unroll
-            for (int a = 0; a < 16; ++a) v1[j][a] = pr[j][a];
-            idft16(v1[j]);
-            float2 p = w[j];
-            // opaque to the optimiser: otherwise the 15 powers (and the LDS twiddles below) are hoisted out
-            // of the hypothesis loop as loop invariants and cost ~180 persistent registers
-            asm volatile("" : "+v"(p.x), "+v"(p.y));
-            const float2 wj = p;
-            v1[j][1] = cmul(v1[j][1], p);
-#pragma unroll
-            for (int n1 = 2; n1 < 16; ++n1) {
-                p = cmul(p, wj);
-                v1[j][n1] = cmul(v1[j][n1], p);
-            }
-        }
+        for (int a = 0; a < 16; ++a) v1[0][a] = pr[0][a];
+        idft16(v1[0]);
+        float2 p = w[0];
+        // opaque to the optimiser: otherwise the 15 powers (and the LDS twiddles below) are hoisted out
+        // of the hypothesis loop as loop invariants and cost ~180 persistent registers
+        asm volatile("" : "+v"(p.x), "+v"(p.y));
+        const float2 wj = p;
         __syncthreads();  // previous hypothesis' pass-4 reads are done (and the LDS tables are in place)
-        lds_rows16c<FP_P1>(m0_x1, v1[0]);  // value n1 -> region n1, row = this wave, position = lane
+        __builtin_amdgcn_sched_barrier(0);  // (nothing of what follows moves in front of the barrier)
+        twiddle_write_x1(m0_x1, v1[0], p, wj);  // value n1 -> region n1, row = this wave, position = lane
         __syncthreads();
         row_of(more ? h + 1 : h);  // unconditional refill (the last one is redundant): no select keeps pr alive
         // Modes 2+ (no |y|^2 tiles: running maxima, finished rows, complex rows, hypothesis-major rows) have 20 registers
